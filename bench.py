@@ -21,6 +21,14 @@ this process is one rank.  `python bench.py --gpus N` with N > 1 and no
 WORLD_SIZE starts the N ranks itself as a CHILD torch.distributed.run (decided
 before anything here imports torch or touches the GPU) and relays rank 0's line.
 
+A plain run sets up, warms up, times --steps rounds and prints the line (the
+headline `value` and `ms_per_step`, plus figures derived from the timed rounds'
+own counters).  Everything that takes runs of its own -- the per-kernel timing
+pass and roofline, the live PMC children, the CPU baseline and reference
+calibration, the compat path and the end-to-end training legs -- runs only with
+--full.  --dump-outputs DIR writes what the last timed round computed (see
+dump_outputs) so that two builds can be compared output for output.
+
 Prints ONE JSON line on rank 0.  Exit code: 0 only if every leg finished; a
 failed or timed-out e2e leg still prints the line (with `e2e.error`) and exits 3.
 """
@@ -102,7 +110,16 @@ def parse():
     ap.add_argument("--selftest-dist", choices=("ok", "e2e-fail", "e2e-hang"), default=None,
                     help="no GPU work at all: rendezvous (gloo), reductions, the guarded e2e leg with a stand-in body, "
                          "the single JSON line and the shutdown path -- what tests/test_bench_launch.py runs on CPU")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: per-kernel timing pass + roofline, live PMC traffic, "
+                         "CPU baseline, compat path and the end-to-end training legs (the --no-* / --e2e-* options "
+                         "above select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed round computed as DIR/<name>.npy (float64)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def get_graph(args, rank, barrier):
@@ -174,6 +191,69 @@ def kernel_bytes_device_layout(name, m, P, layer=0, last=False, nxt=None):
         return (C * 1 + (U + m["in_total"]) * 4 + U * 4 + m["in_total"] * 4 + min(F, m["in_total"]) * 4
                 + F * (4 + 4) + m["node_lists"] * 4 + F * 4 + (0 if last else U * 16))
     return 0
+
+
+DUMP_MAX_BYTES = 60 << 20   # --dump-outputs: under 64 MB in all (.npy headers included)
+LIST_NAMES = ("in_nodes", "out_nodes", "owned_out_nodes", "self_ids_in", "self_ids_out", "to_ids", "from_ids",
+              "indptr", "indices", "owned_degree", "t_indptr", "t_indices")   # the engine's list kinds, in index order
+
+
+def dump_outputs(eng, slot, out_dir, max_bytes=DUMP_MAX_BYTES):
+    """What a caller of the timed path receives from its last round (result slot `slot`), as float64 .npy files
+    (node ids and counts are exact in float64):
+      stream_counts      [S, L, 4]     per stream and layer: frontier, next frontier, draws, sampled edges
+      stream_rng         [S, 2]        per stream: mt19937 position before and after the sample
+      stream_list_sizes  [S, L, K, P]  per stream, layer and list kind: the length of every part's list
+      streams            [n]           the streams whose lists follow, in the order they are concatenated
+      l<l>_<kind>        the non-empty lists of layer l, every part of every chosen stream back to back
+      frontier<l>        the frontier of layer l (l = L: the last layer's next frontier) of every chosen stream
+    The streams are taken in a fixed seeded order for as long as their lists fit in `max_bytes`; should even the
+    first not fit, every list array is cut to the same fixed seeded sample of its positions."""
+    from cslicer import _abi
+    S, L, P = eng.n_streams, eng.n_layers, eng.n_parts
+    metas = [eng.meta(s, slot) for s in range(S)]
+    arrays = {
+        "stream_counts": np.array([[[m.layer[l].frontier, m.layer[l].next_frontier, m.layer[l].draws,
+                                     m.layer[l].sampled_edges] for l in range(L)] for m in metas], dtype=np.float64),
+        "stream_rng": np.array([[m.rng_begin, m.rng_end] for m in metas], dtype=np.float64),
+        "stream_list_sizes": np.array([[[[m.layer[l].off[k][g + 1] - m.layer[l].off[k][g] for g in range(P)]
+                                         for k in range(_abi.NUM_LISTS)] for l in range(L)] for m in metas],
+                                      dtype=np.float64),
+    }
+
+    def n_values(m):
+        return (sum(int(m.layer[l].off[k][P]) for l in range(L) for k in range(_abi.NUM_LISTS))
+                + sum(int(m.layer[l].frontier) for l in range(L)) + int(m.layer[L - 1].next_frontier))
+
+    room = (max_bytes - sum(a.nbytes for a in arrays.values()) - 8 * S) // 8
+    chosen, used = [], 0
+    for s in np.random.default_rng(0).permutation(S):
+        n = n_values(metas[s])
+        if chosen and used + n > room:
+            break
+        chosen.append(int(s))
+        used += n
+    lists = {}
+    for s in chosen:
+        m = metas[s]
+        for l in range(L):
+            for k in range(_abi.NUM_LISTS):
+                if int(m.layer[l].off[k][P]):
+                    lists.setdefault("l%d_%s" % (l, LIST_NAMES[k]), []).extend(
+                        eng.copy_list(l, k, g, s, slot, m) for g in range(P))
+        for l in range(L + 1):
+            lists.setdefault("frontier%d" % l, []).append(eng.copy_frontier(l, s, slot, m))
+    keep = min(1.0, room / max(used, 1))
+    for name, parts in lists.items():
+        a = np.concatenate(parts).astype(np.float64)
+        if keep < 1.0:
+            a = a[np.sort(np.random.default_rng(1).permutation(a.shape[0])[:int(a.shape[0] * keep)])]
+        arrays[name] = a
+    arrays["streams"] = np.array(chosen, dtype=np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return arrays
 
 
 def compat_leg(indptr, indices, args, B, samples=384, workers=32):
@@ -539,6 +619,8 @@ def main():
     total_edges = shard.sum_over_ranks(edges1 - edges0, dist, red_dev)
     iters = int(shard.sum_over_ranks(iters1 - iters0, dist, red_dev))
     value = total_edges / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, (args.warmup + args.steps - 1) % NS, args.dump_outputs)
 
     out = {
         "metric": "sampled_edges_per_sec",
@@ -728,7 +810,7 @@ def main():
     live_pmc_kernel = None
     if rank == 0:
         # ---- per-kernel HIP-event timing pass (engine's own stream) for the roofline
-        if not args.no_kernel_timing:
+        if args.full and not args.no_kernel_timing:
             eng.timing_enable(True)
             t_ev = time.perf_counter()
             for k in range(args.steps):
@@ -792,7 +874,7 @@ def main():
         out["path_roofline"]["frac"] = out["path_roofline"]["achieved_GBs"] / HBM_PEAK_GBS
 
         # ---- CPU baseline: the oracle (port of the reference algorithm) on host cores
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             from oracle import oracle as orc
             host = host_cpu_info()
             cores = host["usable_cpus"]      # every CPU this process may use (affinity mask / cgroup quota)
@@ -861,7 +943,7 @@ def main():
                 "profiles/pmc_rdsize.sh)" % launches)
         except Exception as ex:   # the committed PMC summary quoted above stays
             out["roofline"]["traffic_live_error"] = repr(ex)[:200]
-    if rank == 0 and world == 1 and not args.no_compat:
+    if args.full and rank == 0 and world == 1 and not args.no_compat:
         try:
             out["compat_path"] = compat_leg(indptr, indices, args, B)
         except Exception as ex:   # optional evidence, never fatal
@@ -873,7 +955,7 @@ def main():
     if dist is not None:
         out["dist"] = {"backend": dist.get_backend(), "world_size": dist.get_world_size(),
                        "launcher": "torch.distributed.run"}
-    if args.e2e_steps > 0 and (world == 1 or not args.no_e2e_multi):
+    if args.full and args.e2e_steps > 0 and (world == 1 or not args.no_e2e_multi):
         if world == 1:
             out["e2e"] = e2e_leg()
             if args.hub_probe:

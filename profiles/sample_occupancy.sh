@@ -6,7 +6,7 @@ OUT=$R/gpurun_out/sample_occupancy.log
 : > $OUT
 for pad in 0 8192 16384 24576 32768; do
   echo "== CSL_SAMPLE_LDS_PAD=$pad" >> $OUT
-  CSL_SAMPLE_LDS_PAD=$pad python3 $R/bench.py --steps 20 --warmup 5 --e2e-steps 0 --e2e-gat-steps 0 --no-cpu-baseline --no-compat --no-live-pmc 2>/dev/null | python3 -c "
+  CSL_SAMPLE_LDS_PAD=$pad python3 $R/bench.py --full --steps 20 --warmup 5 --e2e-steps 0 --e2e-gat-steps 0 --no-cpu-baseline --no-compat --no-live-pmc 2>/dev/null | python3 -c "
 import sys, json
 for line in sys.stdin:
     line=line.strip()

@@ -3,6 +3,8 @@ field the driver's contract asks for, with consistent values."""
 import json
 import os
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -65,12 +67,88 @@ def test_bench_flags_parse():
                      ["--no-e2e-multi", "--e2e-timeout", "30"],
                      ["--serial-rounds", "--no-cpu-baseline", "--no-kernel-timing", "--e2e-steps", "0"],
                      ["--no-compat", "--no-tuned-gemms", "--e2e-streams", "16", "--same-batch"],
-                     ["--gpus", "2", "--selftest-dist", "ok"]):
+                     ["--gpus", "2", "--selftest-dist", "ok"],
+                     ["--gpus", "1", "--steps", "7", "--warmup", "0", "--full", "--dump-outputs", "out"]):
             sys.argv = ["bench.py"] + argv
             a = mod.parse()
             assert a.steps > 0 and a.mode in ("strict", "graph")
+        assert a.steps == 7 and a.full and a.dump_outputs == "out"
+        sys.argv = ["bench.py"]
+        a = mod.parse()
+        assert not a.full and a.dump_outputs is None       # a plain run is the headline only
+        import pytest
+        for bad in (["--steps", "0"], ["--warmup", "-1"]):
+            sys.argv = ["bench.py"] + bad
+            with pytest.raises(SystemExit):
+                mod.parse()
     finally:
         sys.argv = old
+
+
+class _FakeEngine:
+    """Stand-in for cslicer._abi.Engine with the members bench.dump_outputs uses: 8 streams, 2 layers, 2 parts,
+    three non-empty list kinds whose lengths grow with the stream."""
+    n_streams, n_layers, n_parts = 8, 2, 2
+    KINDS = (0, 1, 6)
+
+    def meta(self, stream, slot):
+        from cslicer import _abi
+        m = _abi.SampleMeta()
+        m.rng_begin, m.rng_end = 1000 * stream, 1000 * stream + 77
+        for l in range(self.n_layers):
+            lm = m.layer[l]
+            lm.frontier, lm.next_frontier, lm.draws, lm.sampled_edges = 10 * (l + 1), 20 * (l + 1), 5 + stream, 3 + l
+            for k in self.KINDS:
+                for g in range(self.n_parts):
+                    lm.off[k][g + 1] = lm.off[k][g] + (stream + 1) * (l + 1) * 100 + k
+        return m
+
+    def copy_list(self, layer, kind, part, stream, slot, meta):
+        lm = meta.layer[layer]
+        n = lm.off[kind][part + 1] - lm.off[kind][part]
+        return np.arange(n, dtype=np.int64) + 100000 * stream + 1000 * kind + 10 * part + layer
+
+    def copy_frontier(self, layer, stream, slot, meta):
+        n = meta.layer[layer].frontier if layer < self.n_layers else meta.layer[self.n_layers - 1].next_frontier
+        return np.arange(n, dtype=np.int64) * 3 + stream
+
+
+def test_dump_outputs_on_a_stand_in_engine(tmp_path):
+    """bench.dump_outputs: float64 files that are exactly the lists the engine hands out, every stream's counters,
+    never more than the byte cap, and the same files for the same round."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    eng = _FakeEngine()
+    a = bench.dump_outputs(eng, 0, str(tmp_path / "all"), max_bytes=1 << 20)
+    files = sorted(os.listdir(tmp_path / "all"))
+    assert files == sorted(name + ".npy" for name in a)
+    for name in a:
+        got = np.load(tmp_path / "all" / (name + ".npy"))
+        assert got.dtype == np.float64 and np.array_equal(got, a[name])
+    assert a["stream_counts"].shape == (8, 2, 4) and a["stream_list_sizes"].shape == (8, 2, 12, 2)
+    assert sorted(a["streams"].astype(int)) == list(range(8))          # everything fits: every stream
+    order = a["streams"].astype(int)
+    want = np.concatenate([eng.copy_list(1, 6, g, s, 0, eng.meta(s, 0)) for s in order for g in range(2)])
+    assert np.array_equal(a["l1_from_ids"], want.astype(np.float64))
+    assert "l0_indptr" not in a and a["frontier2"].shape[0] == 8 * 40
+
+    # a cap that holds a few streams: a prefix of the same order, within the cap, identical on a second call
+    cap = 150000
+    b = bench.dump_outputs(eng, 0, str(tmp_path / "cap"), max_bytes=cap)
+    b2 = bench.dump_outputs(eng, 0, str(tmp_path / "cap2"), max_bytes=cap)
+    n = len(b["streams"])
+    assert 1 <= n < 8 and np.array_equal(b["streams"], order[:n])
+    assert sum(x.nbytes for x in b.values()) <= cap
+    assert all(np.array_equal(b[k], b2[k]) for k in b)
+
+    # a cap below one stream's lists: one stream, every list cut to a sample of its values
+    c = bench.dump_outputs(eng, 0, str(tmp_path / "tiny"), max_bytes=12000)
+    assert len(c["streams"]) == 1 and sum(x.nbytes for x in c.values()) <= 12000
+    s = int(c["streams"][0])
+    full = np.concatenate([eng.copy_list(0, 0, g, s, 0, eng.meta(s, 0)) for g in range(2)])
+    assert 0 < c["l0_in_nodes"].shape[0] < full.shape[0] and np.isin(c["l0_in_nodes"], full).all()
 
 
 def test_split_k_linear_on_cpu():
