@@ -915,9 +915,14 @@ class FeatureRows(object):
         self.table, self.rows = table, rows
 
 
-def gat_input_ok(H, F, fanout):
-    """whether GatInputLayer covers a layer of H heads on F input features whose rows have <= fanout edges"""
-    return H in (1, 2, 4, 8) and F % 4 == 0 and 4 <= F <= 128 and 0 < fanout <= int(_lib().csl_gat_in_max_degree())
+GAT_IN_MAX_WIDTH = 256   # H * D: the rows csl_elu_bwd_colsum_f32 (the layer's backward epilogue) covers
+
+
+def gat_input_ok(H, F, fanout, D=None):
+    """whether GatInputLayer covers a layer of H heads x D outputs on F input features whose rows have <= fanout edges
+    (D = None: the edge kernels' limits alone; a caller that is about to build the layer passes its D)"""
+    return (H in (1, 2, 4, 8) and F % 4 == 0 and 4 <= F <= 128 and (D is None or 0 < H * D <= GAT_IN_MAX_WIDTH)
+            and 0 < fanout <= int(_lib().csl_gat_in_max_degree()))
 
 
 def _gemm_batched(transa, transb, m, n, k, a, lda, sa, b, ldb, sb, c, ldc, sc, batch):
@@ -943,9 +948,12 @@ class GatInputLayer(torch.autograd.Function):
     @staticmethod
     def forward(ctx, table, rows, weight, attn_l, attn_r, bias, indptr, indices, self_ids_in, n_out, n_edges, max_deg, slope,
                 elu, row_pad, pad_out):
-        """max_deg: no row of the CSR has more edges (the slicer's fanout of the layer)"""
+        """max_deg: no row of the CSR has more edges (the slicer's fanout of the layer; a longer row's output and the
+        attention gradients come out NaN)"""
         H, D = attn_l.shape
         F, Cw = table.shape[1], H * D
+        if Cw > GAT_IN_MAX_WIDTH:
+            raise ValueError("GatInputLayer: H * D = %d > %d has no backward kernel (gat_input_ok)" % (Cw, GAT_IN_MAX_WIDTH))
         table, weight = _f32(table), _f32(weight).contiguous()
         al, ar, b = _f32(attn_l).contiguous(), _f32(attn_r).contiguous(), _f32(bias).contiguous()
         indptr, indices, self_ids_in = _i32(indptr), _i32(indices), _i32(self_ids_in)

@@ -68,7 +68,8 @@ class Trainer(object):
             # it runs aggregate-then-project on the raw feature rows (aggr.GatInputLayer: no source gradient at all)
             F_in = features.shape[1] if feat_dim is None and not callable(features) else feat_dim
             self.gat_input = (not splitgnn._NO_GAT_INPUT and not splitgnn._NO_LOCAL_FUSE and F_in is not None
-                              and aggr.gat_input_ok(heads, F_in, fanouts[-1]))
+                              and aggr.gat_input_ok(heads, F_in, fanouts[-1],
+                                                    hidden if len(fanouts) > 1 else (n_classes + 3) // 4 * 4))
             eng_flags = _abi.FLAG_TRANSPOSE | (0 if self.gat_input else _abi.FLAG_TRANSPOSE_ALL)
         self.eng = _abi.Engine(indptr, indices, n_parts=self.P, fanouts=fanouts, max_batch=batch,
                                n_streams=streams, n_slots=self.SLOTS, device=device, mode=_abi.MODE_GRAPH,
@@ -109,6 +110,8 @@ class Trainer(object):
         # the fused single-GPU GraphSAGE step as one native call per minibatch (CSLICER_PY_STEP=1: the same kernels
         # issued from Python through an autograd node, A/B switch and what the tests compare it with)
         self.native, self.grad_sync = None, None
+        # rank path, autograd step: called with the flat gradient right after its all-reduce (what the optimizer applies)
+        self.on_reduced_grads = None
         if (by_source and F % 4 == 0 and hidden % 4 == 0 and not os.environ.get("CSLICER_PY_STEP")
                 and not splitgnn._NO_LOCAL_FUSE):
             self.native = aggr.SageStep(self.model, splitgnn.ROW_PAD, splitgnn.SPLIT_K)
@@ -230,6 +233,8 @@ class Trainer(object):
             flat = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1)
                               for p in self.model.parameters()])
             self.dist.all_reduce(flat)                    # replicated weights: sum of per-rank gradients
+            if self.on_reduced_grads is not None:
+                self.on_reduced_grads(flat)
             _roctx.pop()
             _roctx.push("optimizer")
             self.opt.step(flat_grads=flat)                # the reduced buffer is used in place

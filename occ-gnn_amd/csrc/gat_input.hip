@@ -86,6 +86,7 @@ __device__ __forceinline__ float leaky(const float x, const float slope) { retur
 // group in the second pass: 0.9 ms for the 110 k rows of config 5's deepest layer at two waves per SIMD.)
 struct RowIdx {
   int e0, deg, sid;
+  bool over;    // the row has more than ME edges: the instance cannot hold it, its results are poisoned with NaN
   int xrow_q;   // lane q: feature row of edge q (of edge 0 for q >= deg)
   int srow;     // feature row of the destination itself (0 if it has none)
 };
@@ -93,11 +94,15 @@ __device__ __forceinline__ RowIdx load_row_idx(const int* __restrict__ indptr, c
                                                const int* __restrict__ self_ids, const int* __restrict__ rowmap,
                                                const long long r, const bool rowok, const int q, const int me) {
   RowIdx ri;
-  ri.e0 = 0, ri.deg = 0, ri.sid = -1;
+  ri.e0 = 0, ri.deg = 0, ri.sid = -1, ri.over = false;
   if (rowok) {
     ri.e0 = indptr[r];
     ri.deg = indptr[r + 1] - ri.e0;
-    if (ri.deg > me) ri.deg = me;   // (memory safety only: the host side refuses longer rows)
+    // the host picks the instance from the caller's max_deg and does not read indptr: a longer row is cut to the ME edges
+    // the registers hold (memory safety) and flagged, so that its output / the gradients it feeds become NaN, not a
+    // softmax over a subset of its edges
+    ri.over = ri.deg > me;
+    if (ri.over) ri.deg = me;
     ri.sid = self_ids[r];
   }
   const int src = indices[q < ri.deg ? ri.e0 + q : (ri.deg > 0 ? ri.e0 : 0)];   // unconditional, always a valid entry
@@ -107,7 +112,7 @@ __device__ __forceinline__ RowIdx load_row_idx(const int* __restrict__ indptr, c
 }
 
 // forward: agg[r, h, :] = sum_e alpha[e, h] x[src_e];  alpha[e, h] (its sign bit: the logit was <= 0) is kept for the
-// backward.  Rows with more than GATIN_MAX_DEG edges are refused by the host side (the slicer's fanout bounds them).
+// backward.  A row with more than ME edges (a max_deg below the true one) gets agg[r] = NaN: no host-side check, no sync.
 template <int H, int ME>
 __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(ME <= 16 ? 3 : 1, 8))) void k_gatin_fwd(const int* __restrict__ indptr, const int* __restrict__ indices,
                                                    const int* __restrict__ self_ids, const int* __restrict__ rowmap,
@@ -226,6 +231,11 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(ME <= 16 ? 
     }
   }
   if (rowok && on) {
+    if (ri.over) {
+      const float nan = __builtin_nanf("");
+#pragma unroll
+      for (int h = 0; h < H; h++) acc[h] = make_float4(nan, nan, nan, nan);
+    }
 #pragma unroll
     for (int h = 0; h < H; h++) *reinterpret_cast<float4*>(agg + (r * H + h) * F + col) = acc[h];
   }
@@ -234,7 +244,8 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(ME <= 16 ? 
 }
 
 // backward: from dagg[r, h, :] (row stride ld_r, head stride ld_h) and the kept alpha, the gradients of v_l and v_r as
-// per-block partial sums part_l / part_r [blocks][H * F] (second stage: csl_reduce_multi_f32).
+// per-block partial sums part_l / part_r [blocks][H * F] (second stage: csl_reduce_multi_f32).  A row with more than ME
+// edges poisons its block's partial sums with NaN (and with them g_vl / g_vr), as the forward poisons its output row.
 //   dalpha[e, h] = <dagg[r, h], x[src_e]>      dlogit = alpha (dalpha - sum_e alpha dalpha)      draw = dlogit * leaky'
 //   dv_l[h] += draw[e, h] x[src_e]             dv_r[h] += (sum_e draw[e, h]) x[self(r)]
 template <int H, int ME>
@@ -320,7 +331,8 @@ __global__ __launch_bounds__(BLK) void k_gatin_bwd(const int* __restrict__ indpt
 #pragma unroll
     for (int c = 0; c < NG; c++) {
       // (the sign bit of alpha: the logit was <= 0; -0.0f keeps it for a weight that underflowed)
-      const float dr = fabsf(av[c]) * (dal[c] - tsum) * ((__float_as_uint(av[c]) >> 31) ? slope : 1.f);
+      float dr = fabsf(av[c]) * (dal[c] - tsum) * ((__float_as_uint(av[c]) >> 31) ? slope : 1.f);
+      if (ri.over) dr = __builtin_nanf("");
       s_dr[g][c * 32 + q] = dr;
       der += dr;
     }

@@ -118,3 +118,5 @@ def test_gat_input_layer_host_side_contract():
     assert L.csl_gat_in_layer_fwd_f32(null, null, null, null, null, 100, 100, null, null, null, null, 8, 12, 0.2, 1, 10, 10, 10,
                                       null, null, null, 96, null, st) == -1
     assert aggr.gat_input_ok(8, 100, 10) and not aggr.gat_input_ok(8, 100, 33) and not aggr.gat_input_ok(3, 100, 10)
+    # H * D > 256: the backward's epilogue (csl_elu_bwd_colsum_f32) refuses such rows, so the layer must not be chosen
+    assert aggr.gat_input_ok(4, 100, 10, 64) and not aggr.gat_input_ok(8, 100, 10, 64)

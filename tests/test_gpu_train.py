@@ -166,7 +166,7 @@ def _rank_main(rank, world, port, q, overlap=False, kind="sage", table=False):
     try:
         _rank_body(rank, world, q, overlap, kind, dist, table)
     except Exception as ex:      # the parent must hear about it instead of waiting for the queue
-        q.put((rank, "error: " + repr(ex), None))
+        q.put((rank, "error: " + repr(ex), None, None))
         raise
 
 
@@ -192,13 +192,16 @@ def _rank_body(rank, world, q, overlap, kind, dist, table=False):
     if table:
         assert len(asked) == 2 and all(bool((wl[o] == rank).all()) and len(o) == int((wl == rank).sum()) for o in asked)
     t.set_nodes(perm)
+    first_grads = []    # the first step's flat gradient after the all-reduce (GAT: the autograd rank step)
+    t.on_reduced_grads = lambda flat: first_grads.append(flat.detach().cpu().clone()) if not first_grads else None
     losses = t.run(4)
+    assert bool(first_grads) == (kind == "gat")
     tl = torch.tensor(losses, dtype=torch.float64)
     dist.all_reduce(tl)     # global minibatch loss = sum of the ranks' shares
     w = torch.cat([p.detach().reshape(-1).cpu() for p in t.model.parameters()])
     t.close()
     dist.barrier()
-    q.put((rank, tl.tolist(), w.numpy()))
+    q.put((rank, tl.tolist(), w.numpy(), first_grads[0].numpy() if first_grads else None))
     dist.destroy_process_group()
 
 
@@ -239,6 +242,7 @@ def test_two_ranks_match_single_process_two_parts(overlap, kind, table, world):
     opt = torch.optim.Adam(model.parameters(), lr=1e-2)
     ft, lt = torch.from_numpy(feats).to(dev), torch.from_numpy(labels).to(dev)
     ref_losses = []
+    ref_grads = None
     for r in range(2):
         eng.submit_round(r * 2, 128, 2, slot=r & 1)
         for s in range(2):
@@ -252,6 +256,9 @@ def test_two_ranks_match_single_process_two_parts(overlap, kind, table, world):
             loss = loss / 128
             opt.zero_grad()
             loss.backward()
+            if ref_grads is None:
+                ref_grads = [(p.grad if p.grad is not None else torch.zeros_like(p)).detach().cpu().reshape(-1)
+                             for p in model.parameters()]
             opt.step()
             ref_losses.append(float(loss))
     w_ref = torch.cat([p.detach().reshape(-1).cpu() for p in model.parameters()]).numpy()
@@ -261,9 +268,23 @@ def test_two_ranks_match_single_process_two_parts(overlap, kind, table, world):
     # the node-by-node reference), its gradients agree with the node-by-node form to 1e-4 of the largest entry
     # (test_fused_gat_rank_layer_matches_its_autograd_form) -- and Adam at lr 1e-2 turns noise-level gradient entries into
     # lr-sized steps, so the trajectories agree to 1e-3, not 1e-5
-    for rank, losses, w in res:
+    for rank, losses, w, g in res:
         if kind == "gat":
             np.testing.assert_allclose(losses, ref_losses, rtol=1e-3, atol=1e-6)
+            # the first step's all-reduced gradient, per parameter tensor, against the single-process reference's: unlike
+            # the weights after Adam (below) this bounds what every rank actually applies.  (A row's softmax sees er only
+            # through the leaky ReLU's kink, so a layer's attn_r gradient can be zero up to rounding -- the last layer's is
+            # here, in both computations: it is measured against the scale of the same layer's attn_l gradient.)
+            ref_by_name = {name: gr.numpy() for (name, _), gr in zip(model.named_parameters(), ref_grads)}
+            at = 0
+            for name, gr in ref_by_name.items():
+                scale = float(np.abs(gr).max())
+                if name.endswith("attn_r"):
+                    scale = max(scale, float(np.abs(ref_by_name[name[:-1] + "l"]).max()))
+                d_g = float(np.abs(g[at:at + gr.size] - gr).max())
+                assert d_g <= 1e-4 * scale, (rank, name, d_g, scale)
+                at += gr.size
+            assert at == g.size
             # Weights: Adam divides every entry's gradient by its own magnitude, so an entry whose gradient is 1e-4 of the
             # tensor's largest (padded class columns, a nearly empty rank's share: a sixth of the entries here) moves by lr
             # times the RELATIVE rounding difference of the two summation orders; four steps bound the walk by 4 lr, the mean
