@@ -12,6 +12,9 @@ reader cslicer/dataset.cpp:18-113):
     <dir>/labels.bin          int32[N]                 (unused by the slicer)
     <dir>/partition_map_opt.bin int32[N]               (loaded, ignored: the
                               reference uses v % 4, cslicer/pyfrontend.cpp:57)
+    <dir>/train_idx.bin       int64[...]  optional training / evaluation node
+    <dir>/val_idx.bin         int64[...]  split, with csum_train / csum_test
+                              in meta.txt (convert_dgl_dataset.py:107-112)
 
 The reference reader skips a final line that has no trailing newline
 (dataset.cpp:75), so the writer always terminates every line with '\n'.
@@ -114,8 +117,12 @@ def synth_preset(name, seed=0):
 
 
 def write_l0(path, indptr, indices, features=None, labels=None, partition=None,
-             feature_dim=None, num_classes=2):
-    """Write an L0 dataset directory readable by the reference's Dataset class."""
+             feature_dim=None, num_classes=2, train_idx=None, val_idx=None):
+    """Write an L0 dataset directory readable by the reference's Dataset class.  train_idx / val_idx (both or
+    neither): the node split, written as train_idx.bin / val_idx.bin (int64) with their sums csum_train / csum_test
+    in meta.txt, as the reference's converter does (convert_dgl_dataset.py:107-112)."""
+    if (train_idx is None) != (val_idx is None):
+        raise ValueError("write_l0: pass both train_idx and val_idx, or neither")
     os.makedirs(path, exist_ok=True)
     indptr = np.ascontiguousarray(indptr, dtype=np.int64)
     indices = np.ascontiguousarray(indices, dtype=np.int64)
@@ -141,10 +148,22 @@ def write_l0(path, indptr, indices, features=None, labels=None, partition=None,
         "feature_dim": int(features.shape[1]),
         "csum_features": int(features.sum(dtype=np.float64)),
         "csum_labels": int(labels.sum(dtype=np.int64)),
+    }
+    if train_idx is not None:
+        train_idx = np.ascontiguousarray(train_idx, dtype=np.int64)
+        val_idx = np.ascontiguousarray(val_idx, dtype=np.int64)
+        for name, idx in (("train_idx", train_idx), ("val_idx", val_idx)):
+            if idx.ndim != 1 or (idx.size and (idx.min() < 0 or idx.max() >= n)):
+                raise ValueError("write_l0: %s must be node ids in [0, %d)" % (name, n))
+        train_idx.tofile(os.path.join(path, "train_idx.bin"))
+        val_idx.tofile(os.path.join(path, "val_idx.bin"))
+        meta["csum_train"] = int(train_idx.sum(dtype=np.int64))
+        meta["csum_test"] = int(val_idx.sum(dtype=np.int64))
+    meta.update({
         "csum_offsets": int(indptr.sum(dtype=np.int64)),
         "csum_edges": int(indices.sum(dtype=np.int64)),
         "num_classes": int(num_classes),
-    }
+    })
     with open(os.path.join(path, "meta.txt"), "w") as f:
         for k, v in meta.items():
             f.write("%s=%d\n" % (k, v))
@@ -183,6 +202,29 @@ def read_l0(path, mmap=True, check=True):
         if int(np.sum(indices, dtype=np.int64)) != meta["csum_edges"]:
             raise ValueError("indices checksum mismatch in %s" % path)
     return indptr, indices, meta
+
+
+def read_splits(path):
+    """(train_idx, val_idx) int64 of an L0 directory, or None when it has no split files.  The sums are checked
+    against meta.txt's csum_train / csum_test where it has them (a mismatch raises ValueError)."""
+    tp, vp = os.path.join(path, "train_idx.bin"), os.path.join(path, "val_idx.bin")
+    have = os.path.exists(tp), os.path.exists(vp)
+    if not any(have):
+        return None
+    if not all(have):
+        raise ValueError("%s has only one of train_idx.bin / val_idx.bin" % path)
+    meta = read_meta(path)
+    out = []
+    for f, key in ((tp, "csum_train"), (vp, "csum_test")):
+        if os.path.getsize(f) % 8:
+            raise ValueError("%s is not an int64 array" % f)
+        idx = np.fromfile(f, dtype=np.int64)
+        if key in meta and int(idx.sum(dtype=np.int64)) != meta[key]:
+            raise ValueError("%s checksum mismatch in %s" % (os.path.basename(f), path))
+        if "num_nodes" in meta and idx.size and (idx.min() < 0 or idx.max() >= meta["num_nodes"]):
+            raise ValueError("%s holds node ids outside [0, num_nodes)" % f)
+        out.append(idx)
+    return out[0], out[1]
 
 
 def from_edge_list(num_nodes, src, dst, symmetric=False, rows="in"):

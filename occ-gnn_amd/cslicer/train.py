@@ -366,7 +366,32 @@ class Trainer(object):
         return ("avg forward time: %.6f sec\nbatch slice time: %.6f sec\ncache refresh time: %.6f sec"
                 % (self.t_forward / n, self.t_slice / n, 0.0))
 
+    # -- evaluation: full-neighbour, layer-wise inference of the model as trained (cslicer.infer)
+    def _infer_args(self):
+        if self.rank_path:
+            raise NotImplementedError(
+                "evaluation runs full-neighbour inference, which needs every node's feature row in one process: the "
+                "split-parallel rank path (world > 1) holds only its own rows; evaluate a single-process or "
+                "data-parallel trainer")
+        return self.model, self.eng.indptr, self.eng.indices, self.feat
+
+    def predict(self, nodes=None, chunk_rows=None):
+        """float32 logits [len(nodes) (or N), n_classes] of the current weights by full-neighbour inference
+        (cslicer.infer.full_inference), enqueued on the training stream after every step already enqueued.  It neither
+        submits to the engine nor draws random numbers nor touches the optimizer state."""
+        from . import infer
+        return infer.full_inference(*self._infer_args(), nodes=nodes, chunk_rows=chunk_rows or infer.CHUNK_ROWS)
+
+    def evaluate(self, nodes, chunk_rows=None):
+        """{"accuracy", "loss", "n"} of the current weights on `nodes` (argmax accuracy, mean cross-entropy against the
+        trainer's labels) by full-neighbour inference; see predict()."""
+        from . import infer
+        return infer.evaluate(*self._infer_args(), nodes=nodes, labels=self.labels,
+                              chunk_rows=chunk_rows or infer.CHUNK_ROWS)
+
     def close(self):
+        from . import infer
+        infer.release(self.eng.indptr, self.eng.indices)   # the graph evaluation kept on the device, if any
         self.eng.close()
 
 
@@ -455,20 +480,8 @@ def synthetic_node_data(num_nodes, feat_dim, n_classes, seed=0, rows=None):
     return feats, labels
 
 
-def main(argv=None):
-    """Command line with the argument names of the reference's python/train.py:109-131 (same spelling, same
-    defaults where they apply); one process per GPU under torchrun, or a single process.
-
-        python -m cslicer.train --graph synthetic --model-name gcn --fan-out 5,10,15 --batch-size 1024
-        python -m torch.distributed.run --nproc-per-node 4 --master-addr 127.0.0.1 -m cslicer.train --graph <L0 dir>
-
-    --fan-out follows the reference (DGL) convention, input side first (python/train.py:128,
-    batch_slice_multi_gpu.py:202): the LAST number is the hop from the seeds.  --graph: an L0 directory
-    (cslicer.l0), a preset name (arxiv-like, products-like, papers-like) or `synthetic`.
-    Accepted and ignored (no counterpart here): --cache-per (features are resident in HBM), --num-workers,
-    --dropout, --debug, --log-every, --eval-every."""
+def _parser():
     import argparse
-    import os
     ap = argparse.ArgumentParser("split-parallel training on MI355X")
     ap.add_argument("--graph", type=str, default="synthetic")
     ap.add_argument("--log-every", type=int, default=20)
@@ -490,7 +503,47 @@ def main(argv=None):
                     help="(extra) node ownership: `mod` = v %% world (pyfrontend.cpp:57), `file` = the L0 directory's "
                          "partition_map_opt.bin (the METIS map of python/utils/sampler.py:64-134; its values must be "
                          "< the number of ranks)")
-    a = ap.parse_args(argv)
+    ap.add_argument("--eval-split", choices=("none", "file", "holdout"), default="none",
+                    help="(extra) node split for evaluation: none, the L0 directory's train_idx.bin / val_idx.bin, or a "
+                         "seeded 80/20 holdout")
+    return ap
+
+
+def _split(a, n):
+    """(train nodes, evaluation nodes) of --eval-split; (None, None) for `none`"""
+    from . import l0
+    if a.eval_split == "none":
+        return None, None
+    if a.eval_split == "file":
+        if a.graph == "synthetic" or a.graph in l0.PRESETS:
+            raise SystemExit("--eval-split file needs an L0 directory")
+        sp = l0.read_splits(a.graph)
+        if sp is None:
+            raise SystemExit("--eval-split file: %s has no train_idx.bin / val_idx.bin" % a.graph)
+        return sp
+    perm = np.random.default_rng(0).permutation(n)          # seeded, as the reference converter's 80/20 split
+    cut = int(n * 0.8)
+    return np.sort(perm[:cut]), np.sort(perm[cut:])
+
+
+def main(argv=None):
+    """Command line with the argument names of the reference's python/train.py:109-131 (same spelling, same
+    defaults where they apply); one process per GPU under torchrun, or a single process.
+
+        python -m cslicer.train --graph synthetic --model-name gcn --fan-out 5,10,15 --batch-size 1024
+        python -m torch.distributed.run --nproc-per-node 4 --master-addr 127.0.0.1 -m cslicer.train --graph <L0 dir>
+
+    --fan-out follows the reference (DGL) convention, input side first (python/train.py:128,
+    batch_slice_multi_gpu.py:202): the LAST number is the hop from the seeds.  --graph: an L0 directory
+    (cslicer.l0), a preset name (arxiv-like, products-like, papers-like) or `synthetic`.
+    Accepted and ignored (no counterpart here): --cache-per (features are resident in HBM), --num-workers,
+    --dropout, --debug, --log-every.
+    --eval-split (extra): `none` (default) trains on every node and never evaluates; `file` trains on the L0 directory's
+    train_idx.bin and evaluates val_idx.bin; `holdout` trains on a seeded 80 % of the nodes and evaluates the other
+    20 %.  With a split the model is evaluated by full-neighbour inference every --eval-every epochs and after the last
+    one (single process only)."""
+    import os
+    a = _parser().parse_args(argv)
     from . import l0
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -522,6 +575,10 @@ def main(argv=None):
         n_classes = meta["num_classes"]
         if a.partition == "file":
             workload = np.fromfile(os.path.join(a.graph, "partition_map_opt.bin"), dtype=np.int32)
+    if a.eval_split != "none" and world > 1:
+        raise SystemExit("--eval-split runs full-neighbour inference in one process (every feature row); it is not "
+                         "available with one process per part")
+    train_nodes, eval_nodes = _split(a, indptr.shape[0] - 1)
     fan = tuple(int(x) for x in a.fan_out.split(","))[::-1]          # engine order: layer 0 = hop from the seeds
     if len(fan) != a.num_layers:
         fan = fan[:a.num_layers] if len(fan) > a.num_layers else fan
@@ -532,12 +589,21 @@ def main(argv=None):
                  workload=workload, feat_dim=fdim)
     n = indptr.shape[0] - 1
     for epoch in range(a.num_epochs):
-        tr.set_nodes(np.random.default_rng(epoch).permutation(n))
+        if train_nodes is None:
+            tr.set_nodes(np.random.default_rng(epoch).permutation(n))
+        else:
+            tr.set_nodes(train_nodes[np.random.default_rng(epoch).permutation(train_nodes.shape[0])])
         steps = tr.n_batches if a.max_steps <= 0 else min(a.max_steps, tr.n_batches)
         t0 = time.time()
         losses = tr.run(steps)
         if rank == 0:
             print("epoch %d: %d minibatches in %.2f s, loss %.4f -> %.4f" % (epoch, steps, time.time() - t0, losses[0], losses[-1]))
+        if eval_nodes is not None and ((epoch + 1) % max(a.eval_every, 1) == 0 or epoch + 1 == a.num_epochs):
+            t0 = time.time()
+            ev = tr.evaluate(eval_nodes)
+            if rank == 0:
+                # the key of the reference's trainers (pa_cache_multi_gpu.py:252)
+                print("Eval Acc %.4f | loss %.4f | %d nodes in %.2f s" % (ev["accuracy"], ev["loss"], ev["n"], time.time() - t0))
     if rank == 0:
         print(tr.report())
     tr.close()

@@ -1,0 +1,434 @@
+// infer.hip -- full-neighbour, layer-wise inference of the two models (include/cslicer_infer.h), gfx950.
+//
+// The training kernels are shaped for sampled rows (at most one fanout long); a full neighbourhood is power-law, so here a
+// row is a list of work ITEMS of at most SEG edges (the split rule for skewed gathers: lists longer than a fixed share are
+// summed in chunks by separate waves, and a second pass adds each destination's partials in chunk order).  One wave per
+// item; the wave's 64 lanes form G groups of 64 / G lanes, a group covers one source row (lane q of a group holds float4
+// column q of a 64 / G-float4 column tile), and each lane keeps U independent row loads in flight per step: G * U edges of
+// the item are read at once.  The groups' sums are combined by a fixed xor butterfly, the hub partials in part order:
+// no atomics, every result is bitwise reproducible.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+
+#include "cslicer_hip.h"
+#include "cslicer_infer.h"
+
+namespace {
+
+constexpr int BLK = 256;
+constexpr int WPB = BLK / 64;   // waves (items) per block
+constexpr int SEG = CSL_INFER_SEG;
+constexpr int U = 8;            // row loads in flight per lane and step
+constexpr int GAT_LAST_MAX_C = 4096;  // H * D of a last layer: its head mean stages a row per wave in LDS (64 KiB a block)
+constexpr long long GAT_MAX_C = 1ll << 24;  // H * D of a hidden layer (nothing staged; column indices stay int)
+
+__device__ __forceinline__ float4 f4zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
+__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ void st4(float* p, const float4 v) { *reinterpret_cast<float4*>(p) = v; }
+__device__ __forceinline__ void add4(float4& a, const float4 b) { a.x += b.x, a.y += b.y, a.z += b.z, a.w += b.w; }
+__device__ __forceinline__ void scale4(float4& a, const float s) { a.x *= s, a.y *= s, a.z *= s, a.w *= s; }
+__device__ __forceinline__ void fma4(float4& a, const float s, const float4 b) {
+  a.x += s * b.x, a.y += s * b.y, a.z += s * b.z, a.w += s * b.w;
+}
+__device__ __forceinline__ float4 shfl_xor4(const float4 v, const int d) {
+  return make_float4(__shfl_xor(v.x, d), __shfl_xor(v.y, d), __shfl_xor(v.z, d), __shfl_xor(v.w, d));
+}
+__device__ __forceinline__ float elu1(const float v) { return v > 0.f ? v : expm1f(v); }
+
+// ---------------------------------------------------------------- GraphSAGE
+
+// the end of a row: aggregate-first writes the operand [x[v] | mean], project-first act(x[v, :W) + mean + bias)
+__device__ __forceinline__ void sage_finish(const float* __restrict__ x, long long ldx, int W, int proj,
+                                            const float* __restrict__ bias, int relu, float* __restrict__ out, long long ldo,
+                                            long long k, int row, int deg, int c4, float4 acc) {
+  const float d = (float)(deg > 0 ? deg : 1);
+  acc.x /= d, acc.y /= d, acc.z /= d, acc.w /= d;
+  const float4 self = ld4(x + (long long)row * ldx + 4 * c4);
+  if (!proj) {
+    st4(out + k * ldo + 4 * c4, self);
+    st4(out + k * ldo + W + 4 * c4, acc);
+    return;
+  }
+  float4 y = self;
+  add4(y, acc);
+  if (bias) add4(y, ld4(bias + 4 * c4));
+  if (relu) y.x = fmaxf(y.x, 0.f), y.y = fmaxf(y.y, 0.f), y.z = fmaxf(y.z, 0.f), y.w = fmaxf(y.w, 0.f);
+  st4(out + k * ldo + 4 * c4, y);
+}
+
+template <int G>
+__global__ __launch_bounds__(BLK) void k_infer_sage(const int* __restrict__ indptr, const int* __restrict__ indices,
+                                                    const int4* __restrict__ items, long long n_items, long long pos0,
+                                                    long long part0, const float* __restrict__ x, long long ldx, int W,
+                                                    int proj, const float* __restrict__ bias, int relu,
+                                                    float* __restrict__ partial, float* __restrict__ out, long long ldo) {
+  constexpr int LG = 64 / G;
+  const int lane = threadIdx.x & 63, g = lane / LG, q = lane % LG;
+  const long long it = (long long)blockIdx.x * WPB + (threadIdx.x >> 6);
+  if (it >= n_items) return;                                   // (wave-uniform)
+  const int4 item = items[it];
+  const int row = item.x, e0 = item.z, part = item.w;
+  const int rend = indptr[row + 1];
+  const int e1 = part < 0 ? rend : (int)min((long long)e0 + SEG, (long long)rend);
+  const int W4 = W / 4;
+  const long long noff = proj ? W : 0;                         // the neighbour operand's first column in x
+  for (int t0 = 0; t0 < W4; t0 += LG) {
+    const int c4 = t0 + q;
+    const bool on = c4 < W4;
+    float4 acc = f4zero();
+    for (int eb = e0; eb < e1; eb += 64) {
+      const int nb = min(64, e1 - eb);
+      const int mine = lane < nb ? indices[eb + lane] : 0;     // 64 edges' sources, one coalesced load
+      for (int j = 0; j < nb; j += G * U) {
+        float4 v[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+          const int jj = j + u * G + g;
+          const int src = __shfl(mine, jj & 63);
+          v[u] = (on && jj < nb) ? ld4(x + (long long)src * ldx + noff + 4 * c4) : f4zero();
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) add4(acc, v[u]);
+      }
+    }
+#pragma unroll
+    for (int d = LG; d < 64; d <<= 1) add4(acc, shfl_xor4(acc, d));
+    if (g == 0 && on) {
+      if (part >= 0)
+        st4(partial + (long long)(part - part0) * W + 4 * c4, acc);
+      else
+        sage_finish(x, ldx, W, proj, bias, relu, out, ldo, (long long)item.y - pos0, row, rend - indptr[row], c4, acc);
+    }
+  }
+}
+
+// one wave per hub row: its partials added in part order, then the row's end
+__global__ __launch_bounds__(BLK) void k_infer_sage_hubs(const int* __restrict__ indptr, const int4* __restrict__ hubs,
+                                                         long long n_hubs, long long pos0, long long part0,
+                                                         const float* __restrict__ x, long long ldx, int W, int proj,
+                                                         const float* __restrict__ bias, int relu,
+                                                         const float* __restrict__ partial, float* __restrict__ out,
+                                                         long long ldo) {
+  const int lane = threadIdx.x & 63;
+  const long long hi = (long long)blockIdx.x * WPB + (threadIdx.x >> 6);
+  if (hi >= n_hubs) return;
+  const int4 hub = hubs[hi];
+  const int W4 = W / 4;
+  const long long p0 = (long long)hub.z - part0;
+  for (int c4 = lane; c4 < W4; c4 += 64) {
+    float4 acc = f4zero();
+    int p = 0;
+    for (; p + U <= hub.w; p += U) {
+      float4 v[U];
+#pragma unroll
+      for (int u = 0; u < U; u++) v[u] = ld4(partial + (p0 + p + u) * W + 4 * c4);
+#pragma unroll
+      for (int u = 0; u < U; u++) add4(acc, v[u]);
+    }
+    for (; p < hub.w; p++) add4(acc, ld4(partial + (p0 + p) * W + 4 * c4));
+    sage_finish(x, ldx, W, proj, bias, relu, out, ldo, (long long)hub.y - pos0, hub.x, indptr[hub.x + 1] - indptr[hub.x],
+                c4, acc);
+  }
+}
+
+// ---------------------------------------------------------------- GAT
+
+// merge softmax state (m2, s2, n2) into (m, s, n)
+__device__ __forceinline__ void lse_merge(float& m, float& s, float4& n, const float m2, const float s2, const float4 n2) {
+  const float M = fmaxf(m, m2);
+  const float a = expf(m - M), b = expf(m2 - M);
+  s = s * a + s2 * b;
+  scale4(n, a);
+  fma4(n, b, n2);
+  m = M;
+}
+
+// the end of a row: hidden layers ELU(n / s + bias) in place of the output row; the last layer stages n / s + bias of the
+// row in the wave's LDS region (the head mean follows once every column tile is there)
+__device__ __forceinline__ void gat_finish(const float* __restrict__ bias, int last, float* __restrict__ out, long long ldo,
+                                           float* stage, long long k, int c4, float s, float4 n) {
+  float4 y = s > 0.f ? make_float4(n.x / s, n.y / s, n.z / s, n.w / s) : f4zero();
+  if (bias) add4(y, ld4(bias + 4 * c4));
+  if (last) {
+    st4(stage + 4 * c4, y);
+    return;
+  }
+  st4(out + k * ldo + 4 * c4, make_float4(elu1(y.x), elu1(y.y), elu1(y.z), elu1(y.w)));
+}
+
+__device__ __forceinline__ void gat_head_mean(const float* stage, int H, int D, int n_cls, float* __restrict__ out,
+                                              long long ldo, long long k, int lane) {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  for (int j = lane; j < n_cls; j += 64) {
+    float t = 0.f;
+    for (int h = 0; h < H; h++) t += stage[h * D + j];
+    out[k * ldo + j] = t / (float)H;
+  }
+}
+
+template <int G>
+__global__ __launch_bounds__(BLK) void k_infer_gat(const int* __restrict__ indptr, const int* __restrict__ indices,
+                                                   const int4* __restrict__ items, long long n_items, long long pos0,
+                                                   long long part0, const float* __restrict__ z, const float* __restrict__ el,
+                                                   const float* __restrict__ er, int H, int D, float slope,
+                                                   const float* __restrict__ bias, int last, int n_cls,
+                                                   float* __restrict__ partial, long long pld, float* __restrict__ out,
+                                                   long long ldo) {
+  extern __shared__ float lds[];
+  constexpr int LG = 64 / G;
+  const int lane = threadIdx.x & 63, g = lane / LG, q = lane % LG;
+  const long long it = (long long)blockIdx.x * WPB + (threadIdx.x >> 6);
+  if (it >= n_items) return;
+  const int4 item = items[it];
+  const int row = item.x, e0 = item.z, part = item.w;
+  const int rend = indptr[row + 1];
+  const int e1 = part < 0 ? rend : (int)min((long long)e0 + SEG, (long long)rend);
+  const int C = H * D, C4 = C / 4, Dq = D / 4;
+  float* stage = lds + (threadIdx.x >> 6) * C;
+  for (int t0 = 0; t0 < C4; t0 += LG) {
+    const int c4 = t0 + q;
+    const bool on = c4 < C4;
+    const int h = on ? c4 / Dq : 0;
+    const float erv = er[(long long)row * H + h];
+    float m = -1e30f, s = 0.f;
+    float4 n = f4zero();
+    for (int eb = e0; eb < e1; eb += 64) {
+      const int nb = min(64, e1 - eb);
+      const int mine = lane < nb ? indices[eb + lane] : 0;
+      for (int j = 0; j < nb; j += G * U) {
+        float sc[U];
+        float4 v[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+          const int jj = j + u * G + g;
+          const int src = __shfl(mine, jj & 63);
+          const bool ok = on && jj < nb;
+          const float l = ok ? el[(long long)src * H + h] + erv : 0.f;
+          sc[u] = ok ? (l > 0.f ? l : l * slope) : -INFINITY;
+          v[u] = ok ? ld4(z + (long long)src * C + 4 * c4) : f4zero();
+        }
+        float mb = m;
+#pragma unroll
+        for (int u = 0; u < U; u++) mb = fmaxf(mb, sc[u]);
+        const float a = expf(m - mb);
+        s *= a;
+        scale4(n, a);
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+          const float p = expf(sc[u] - mb);
+          s += p;
+          fma4(n, p, v[u]);
+        }
+        m = mb;
+      }
+    }
+#pragma unroll
+    for (int d = LG; d < 64; d <<= 1) {
+      const float m2 = __shfl_xor(m, d), s2 = __shfl_xor(s, d);
+      lse_merge(m, s, n, m2, s2, shfl_xor4(n, d));
+    }
+    if (g == 0 && on) {
+      if (part >= 0) {
+        float* pr = partial + (long long)(part - part0) * pld;
+        st4(pr + 4 * c4, n);
+        if (c4 % Dq == 0) pr[C + h] = m, pr[C + H + h] = s;
+      } else {
+        gat_finish(bias, last, out, ldo, stage, (long long)item.y - pos0, c4, s, n);
+      }
+    }
+  }
+  if (last && part < 0) gat_head_mean(stage, H, D, n_cls, out, ldo, (long long)item.y - pos0, lane);
+}
+
+__global__ __launch_bounds__(BLK) void k_infer_gat_hubs(const int4* __restrict__ hubs, long long n_hubs, long long pos0,
+                                                        long long part0, int H, int D, const float* __restrict__ bias,
+                                                        int last, int n_cls, const float* __restrict__ partial, long long pld,
+                                                        float* __restrict__ out, long long ldo) {
+  extern __shared__ float lds[];
+  const int lane = threadIdx.x & 63;
+  const long long hi = (long long)blockIdx.x * WPB + (threadIdx.x >> 6);
+  if (hi >= n_hubs) return;
+  const int4 hub = hubs[hi];
+  const int C = H * D, C4 = C / 4, Dq = D / 4;
+  float* stage = lds + (threadIdx.x >> 6) * C;
+  const long long p0 = (long long)hub.z - part0;
+  for (int c4 = lane; c4 < C4; c4 += 64) {
+    const int h = c4 / Dq;
+    float m = -1e30f, s = 0.f;
+    float4 n = f4zero();
+    for (int p = 0; p < hub.w; p++) {
+      const float* pr = partial + (p0 + p) * pld;
+      lse_merge(m, s, n, pr[C + h], pr[C + H + h], ld4(pr + 4 * c4));
+    }
+    gat_finish(bias, last, out, ldo, stage, (long long)hub.y - pos0, c4, s, n);
+  }
+  if (last) gat_head_mean(stage, H, D, n_cls, out, ldo, (long long)hub.y - pos0, lane);
+}
+
+// ---------------------------------------------------------------- evaluation head
+
+__global__ __launch_bounds__(BLK) void k_infer_eval_rows(const float* __restrict__ L, long long ld, long long n, int C,
+                                                         const long long* __restrict__ labels, long long* __restrict__ pred,
+                                                         float* __restrict__ loss_row) {
+  const int lane = threadIdx.x & 63;
+  const long long k = (long long)blockIdx.x * WPB + (threadIdx.x >> 6);
+  if (k >= n) return;
+  const float* r = L + k * ld;
+  float v = -INFINITY;
+  int bj = C;
+  for (int j = lane; j < C; j += 64) {
+    const float x = r[j];
+    if (bj == C || x > v) v = x, bj = j;               // a lane's columns ascend: the first maximum is kept
+  }
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const float v2 = __shfl_xor(v, d);
+    const int j2 = __shfl_xor(bj, d);
+    if (j2 < C && (bj == C || v2 > v || (v2 == v && j2 < bj))) v = v2, bj = j2;
+  }
+  float t = 0.f;
+  for (int j = lane; j < C; j += 64) t += expf(r[j] - v);
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) t += __shfl_xor(t, d);
+  if (lane == 0) {
+    const long long y = labels[k];
+    pred[k] = bj;
+    loss_row[k] = (y >= 0 && y < C) ? v + logf(t) - r[y] : NAN;
+  }
+}
+
+__global__ __launch_bounds__(BLK) void k_infer_eval_sum(const long long* __restrict__ pred,
+                                                        const long long* __restrict__ labels,
+                                                        const float* __restrict__ loss_row, long long n,
+                                                        double* __restrict__ loss_sum, long long* __restrict__ correct) {
+  __shared__ double sl[BLK];
+  __shared__ long long sc[BLK];
+  double l = 0.0;
+  long long c = 0;
+  for (long long k = threadIdx.x; k < n; k += BLK) {
+    l += (double)loss_row[k];
+    c += pred[k] == labels[k];
+  }
+  sl[threadIdx.x] = l;
+  sc[threadIdx.x] = c;
+  __syncthreads();
+  for (int w = BLK / 2; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) sl[threadIdx.x] += sl[threadIdx.x + w], sc[threadIdx.x] += sc[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *loss_sum = sl[0], *correct = sc[0];
+}
+
+// ---------------------------------------------------------------- host side
+
+bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+int done() { return hipGetLastError() == hipSuccess ? CSL_OK : CSL_E_HIP; }
+unsigned blocks_of(long long n) { return (unsigned)((n + WPB - 1) / WPB); }
+
+// G groups of 64 / G lanes: the smallest group that holds a column tile of min(C4, 64) float4s (at most 16 groups)
+int groups_for(int C4) {
+  int lg = 4;
+  while (lg < 64 && lg < C4) lg <<= 1;
+  return 64 / lg;
+}
+
+// the checks shared by both layer kernels: a plan slice that is there when it is used
+bool plan_ok(const int32_t* indptr, const int32_t* indices, const int32_t* items, int64_t n_items, const int32_t* hubs,
+             int64_t n_hubs, int64_t pos0, int64_t part0, const void* partial) {
+  if (n_items < 0 || n_hubs < 0 || pos0 < 0 || part0 < 0 || n_items >= (1ll << 31) * WPB || n_hubs >= (1ll << 31) * WPB)
+    return false;
+  if (n_items && (!indptr || !indices || !items || !al16(items))) return false;
+  if (n_hubs && (!indptr || !hubs || !al16(hubs) || !partial || !al16(partial))) return false;
+  return true;
+}
+
+#define LAUNCH_G(G, KERNEL, grid, shmem, ...)                                                                   \
+  switch (G) {                                                                                                \
+    case 1: hipLaunchKernelGGL(KERNEL<1>, dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break;              \
+    case 2: hipLaunchKernelGGL(KERNEL<2>, dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break;              \
+    case 4: hipLaunchKernelGGL(KERNEL<4>, dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break;              \
+    case 8: hipLaunchKernelGGL(KERNEL<8>, dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break;              \
+    default: hipLaunchKernelGGL(KERNEL<16>, dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break;            \
+  }
+
+}  // namespace
+
+extern "C" {
+
+int32_t csl_infer_seg(void) { return SEG; }
+
+int csl_infer_sage_f32(const int32_t* indptr, const int32_t* indices, const int32_t* items, int64_t n_items,
+                       const int32_t* hubs, int64_t n_hubs, int64_t pos0, int64_t part0, const float* x, int64_t ldx,
+                       int32_t W, int32_t proj, const float* bias, int32_t relu, float* partial, float* out, int64_t ldo,
+                       void* stream) {
+  if (!plan_ok(indptr, indices, items, n_items, hubs, n_hubs, pos0, part0, partial)) return CSL_E_INVALID;
+  if (W < 4 || W % 4 != 0 || ldx % 4 != 0 || ldo % 4 != 0 || ldx < (proj ? 2 * (int64_t)W : W) ||
+      ldo < (proj ? W : 2 * (int64_t)W))
+    return CSL_E_INVALID;
+  if (n_items == 0 && n_hubs == 0) return CSL_OK;
+  if (!x || !out || !al16(x) || !al16(out) || (bias && !al16(bias))) return CSL_E_INVALID;
+  hipStream_t st = (hipStream_t)stream;
+  const int G = groups_for(W / 4);
+  const int rl = relu != 0, pj = proj != 0;
+  if (n_items)
+    LAUNCH_G(G, k_infer_sage, blocks_of(n_items), 0, indptr, indices, reinterpret_cast<const int4*>(items),
+             (long long)n_items, (long long)pos0, (long long)part0, x, (long long)ldx, (int)W, pj, bias, rl, partial, out,
+             (long long)ldo);
+  if (n_hubs)
+    hipLaunchKernelGGL(k_infer_sage_hubs, dim3(blocks_of(n_hubs)), dim3(BLK), 0, st, indptr,
+                       reinterpret_cast<const int4*>(hubs), (long long)n_hubs, (long long)pos0, (long long)part0, x,
+                       (long long)ldx, (int)W, pj, bias, rl, partial, out, (long long)ldo);
+  return done();
+}
+
+int64_t csl_infer_gat_partial_ld(int32_t H, int32_t D) {
+  if (H < 1 || D < 4) return CSL_E_INVALID;
+  return (int64_t)H * D + (2 * (int64_t)H + 3) / 4 * 4;
+}
+
+int csl_infer_gat_f32(const int32_t* indptr, const int32_t* indices, const int32_t* items, int64_t n_items,
+                      const int32_t* hubs, int64_t n_hubs, int64_t pos0, int64_t part0, const float* z, const float* el,
+                      const float* er, int32_t H, int32_t D, float slope, const float* bias, int32_t last, int32_t n_cls,
+                      float* partial, float* out, int64_t ldo, void* stream) {
+  if (!plan_ok(indptr, indices, items, n_items, hubs, n_hubs, pos0, part0, partial)) return CSL_E_INVALID;
+  if (H < 1 || D < 4 || D % 4 != 0 || (int64_t)H * D > (last ? GAT_LAST_MAX_C : GAT_MAX_C)) return CSL_E_INVALID;
+  if (last ? (n_cls < 1 || n_cls > D || ldo < n_cls) : (ldo % 4 != 0 || ldo < (int64_t)H * D)) return CSL_E_INVALID;
+  if (n_items == 0 && n_hubs == 0) return CSL_OK;
+  if (!z || !el || !er || !out || !al16(z) || (!last && !al16(out)) || (bias && !al16(bias))) return CSL_E_INVALID;
+  hipStream_t st = (hipStream_t)stream;
+  const int C = H * D;
+  const int G = groups_for(C / 4);
+  const long long pld = csl_infer_gat_partial_ld(H, D);
+  const size_t shmem = last ? (size_t)WPB * C * sizeof(float) : 0;
+  const int ls = last != 0;
+  if (n_items)
+    LAUNCH_G(G, k_infer_gat, blocks_of(n_items), shmem, indptr, indices, reinterpret_cast<const int4*>(items),
+             (long long)n_items, (long long)pos0, (long long)part0, z, el, er, (int)H, (int)D, slope, bias, ls, (int)n_cls,
+             partial, pld, out, (long long)ldo);
+  if (n_hubs)
+    hipLaunchKernelGGL(k_infer_gat_hubs, dim3(blocks_of(n_hubs)), dim3(BLK), shmem, st,
+                       reinterpret_cast<const int4*>(hubs), (long long)n_hubs, (long long)pos0, (long long)part0, (int)H,
+                       (int)D, bias, ls, (int)n_cls, partial, pld, out, (long long)ldo);
+  return done();
+}
+
+int csl_infer_eval_f32(const float* logits, int64_t ld, int64_t n, int32_t C, const int64_t* labels, int64_t* pred,
+                       float* loss_row, double* loss_sum, int64_t* correct, void* stream) {
+  if (n < 0 || C < 1 || ld < C || !loss_sum || !correct) return CSL_E_INVALID;
+  if (n > 0 && (!logits || !labels || !pred || !loss_row)) return CSL_E_INVALID;
+  if (n >= (1ll << 31) * WPB) return CSL_E_INVALID;
+  hipStream_t st = (hipStream_t)stream;
+  if (n > 0)
+    hipLaunchKernelGGL(k_infer_eval_rows, dim3(blocks_of(n)), dim3(BLK), 0, st, logits, (long long)ld, (long long)n,
+                       (int)C, reinterpret_cast<const long long*>(labels), reinterpret_cast<long long*>(pred), loss_row);
+  hipLaunchKernelGGL(k_infer_eval_sum, dim3(1), dim3(BLK), 0, st, reinterpret_cast<const long long*>(pred),
+                     reinterpret_cast<const long long*>(labels), loss_row, (long long)n, loss_sum,
+                     reinterpret_cast<long long*>(correct));
+  return done();
+}
+
+}  // extern "C"
