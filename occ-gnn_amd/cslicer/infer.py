@@ -28,6 +28,8 @@ from . import _abi, aggr, splitgnn
 
 # every symbol include/cslicer_infer.h declares (checked by tests/test_infer_cpu.py)
 SYMBOLS = ["csl_infer_seg", "csl_infer_sage_f32", "csl_infer_gat_partial_ld", "csl_infer_gat_f32", "csl_infer_eval_f32"]
+# every symbol include/cslicer_infer_parts.h declares (checked by tests/test_infer_parts_cpu.py)
+PARTS_SYMBOLS = ["csl_infer_sage_part_f32", "csl_infer_sage_merge_f32", "csl_infer_gat_part_f32", "csl_infer_gat_merge_f32"]
 SEG = 512                 # CSL_INFER_SEG
 CHUNK_ROWS = 1 << 16      # output rows per kernel call / GEMM (bounds the operand and partial scratch)
 GAT_LAST_MAX_C = 4096     # heads x padded classes of an attention model's last layer (csl_infer_gat_f32, last != 0)
@@ -46,6 +48,11 @@ def _lib():
         L.csl_infer_gat_f32.argtypes = [vp, vp, vp, i64, vp, i64, i64, i64, vp, vp, vp, i32, i32, f32, vp, i32, i32, vp, vp,
                                         i64, vp]
         L.csl_infer_eval_f32.argtypes = [vp, i64, i64, i32, vp, vp, vp, vp, vp, vp]
+        L.csl_infer_sage_part_f32.argtypes = [vp, vp, vp, i64, vp, i64, i64, i64, vp, i64, i32, i32, vp, vp, vp]
+        L.csl_infer_sage_merge_f32.argtypes = [vp, vp, i64, i32, vp, vp, i64, i32, i32, vp, i32, vp, i64, vp]
+        L.csl_infer_gat_part_f32.argtypes = [vp, vp, vp, i64, vp, i64, i64, i64, vp, vp, vp, i32, i32, f32, i32, vp, vp,
+                                             vp]
+        L.csl_infer_gat_merge_f32.argtypes = [vp, i64, i32, vp, i32, i32, vp, i32, i32, vp, i64, vp]
         if L.csl_infer_seg() != SEG:
             raise ImportError("libcslicer_hip.so: CSL_INFER_SEG differs from cslicer.infer.SEG")
         _ready = True
@@ -212,8 +219,12 @@ def graph_of(indptr, indices, device):
 
 
 def release(indptr=None, indices=None):
-    """drop the cached graph of (indptr, indices) (all cached graphs when both are None), with its device memory"""
-    _GRAPHS[:] = [e for e in _GRAPHS if not ((indptr is None or e[0] is indptr) and (indices is None or e[1] is indices))]
+    """drop the cached graph of (indptr, indices) (all cached graphs when both are None), with its device memory, and
+    the rank plans of full_inference_parts over it"""
+    def keep(e):
+        return not ((indptr is None or e[0] is indptr) and (indices is None or e[1] is indices))
+    _GRAPHS[:] = [e for e in _GRAPHS if keep(e)]
+    _RANKS[:] = [e for e in _RANKS if keep(e)]
 
 
 # ------------------------------------------------------------------ device steps
@@ -467,3 +478,461 @@ def evaluate(model, indptr, indices, features, nodes, labels, chunk_rows=CHUNK_R
     _, correct, loss = eval_head(logits, lab.to(logits.device))
     n = int(nodes.shape[0])
     return {"accuracy": correct / max(n, 1), "loss": loss / max(n, 1), "n": n}
+
+
+# ------------------------------------------------------------------ split over ranks (include/cslicer_infer_parts.h)
+#
+# One process per part, each holding only the rows of the nodes it owns (the trainer's rank path).  A layer is cut as
+# the training step cuts it: rank q sums, for every destination v, the neighbours of v that q owns (GraphSAGE: the raw
+# sum of Y rows; GAT: the online-softmax state, with er[v] sent by v's owner), the partials go to the owner of v through
+# one all_to_all_single, and the owner merges them in rank order and finishes the row.  Destinations are cut into global
+# chunks of `chunk_rows` positions, derived from replicated data only, so every rank issues the same collectives, empty
+# ones included.  With one part every step is the single-process one and the result is bitwise the same.
+
+def owner_table(N, P, owner=None):
+    """int32 [N] owner of every node: `owner` checked, or v % P"""
+    if owner is None:
+        return (np.arange(N, dtype=np.int64) % P).astype(np.int32)
+    owner = np.ascontiguousarray(owner, dtype=np.int32)
+    if owner.shape != (N,) or (N and (owner.min() < 0 or owner.max() >= P)):
+        raise ValueError("owner must be int32 [%d] with values in [0, %d)" % (N, P))
+    return owner
+
+
+class RankGraph(object):
+    """The host data of one rank of P over one graph and owner table, built once (vectorised numpy, O(E)):
+      lrow  int32 [N]: the row of every node in its owner's tables (its rank among the owner's nodes, ascending)
+      deg   int64 [N]: full neighbour degree
+      vsub_ip / vsub_ix: the rank's local-source CSR in node order: for every v, the neighbours of v this rank owns, in
+            CSR order, as local rows (int64 [N + 1], int32 [E_r])
+      pres  bool [n_own, P]: whether rank q owns a neighbour of the rank's own node (local row order)
+    Peak host bytes: neighbour_csr's 13 E (int64 row ids, keep mask, int32 copy), then 13 E here (int32 owner per edge,
+    the rank's edge mask, an int32 running count), plus about 40 N of node arrays."""
+
+    def __init__(self, indptr, indices, owner, P, rank):
+        ip, ix = neighbour_csr(indptr, indices)
+        N = ip.shape[0] - 1
+        self.N, self.P, self.rank, self.owner = N, int(P), int(rank), owner
+        self.deg = np.diff(ip)
+        self.lrow = np.empty(N, dtype=np.int32)
+        for p in range(self.P):
+            idx = np.flatnonzero(owner == p)
+            self.lrow[idx] = np.arange(idx.shape[0], dtype=np.int32)
+            if p == self.rank:
+                self.own = idx
+        self.n_own = int(self.own.shape[0])
+        eo = owner[ix]                                       # owner of every edge's source
+        mine = eo == self.rank
+        cs = np.zeros(ix.shape[0] + 1, dtype=np.int32)       # (< 2^31 edges: neighbour_csr)
+        np.cumsum(mine, dtype=np.int32, out=cs[1:])
+        self.vsub_ip = np.zeros(N + 1, dtype=np.int64)
+        np.cumsum(cs[ip[1:]].astype(np.int64) - cs[ip[:-1]], out=self.vsub_ip[1:])
+        del cs
+        self.vsub_ix = self.lrow[ix[mine]]
+        del mine
+        own_edges = np.repeat(owner == self.rank, self.deg)
+        self.pres = np.zeros((self.n_own, self.P), dtype=bool)
+        self.pres[np.repeat(np.arange(self.n_own, dtype=np.int64), self.deg[self.own]), eo[own_edges]] = True
+        self._plans = {}
+
+    def plan(self, chunk_rows, nodes=None):
+        """the PartsPlan of the destinations `nodes` (None: every node, cached per chunk_rows)"""
+        if nodes is not None:
+            return PartsPlan(self, nodes, chunk_rows)
+        if chunk_rows not in self._plans:
+            self._plans[chunk_rows] = PartsPlan(self, None, chunk_rows)
+        return self._plans[chunk_rows]
+
+
+class PartsPlan(object):
+    """The exchange plan of one rank for a destination list (positions k, node D[k]) cut into chunks of chunk_rows
+    positions.  Send side: the sub-CSR whose rows are the destinations with a neighbour this rank owns, ordered by
+    (chunk, owner, position), its work list (build_plan: the CSL_INFER_SEG rule) and sub_counts [chunks, P] (rows sent to
+    each owner per chunk).  Receive side: the rank's own destinations in position order, dst int32 [m, 2] {self row,
+    degree}, merge lists ml int32 [m, P] (row of rank q's partial in the chunk's receive buffer, -1: none) and
+    own_counts [chunks, P] (rows received from each rank per chunk).  er_src: for the attention model's first
+    exchange, the self row of the destination of every receive-buffer row (that exchange sends er[v] back along the
+    partials' path).  Rank q's sub_counts[c, p] equals rank p's own_counts[c, q]."""
+
+    def __init__(self, rg, nodes, chunk_rows):
+        P, rank = rg.P, rg.rank
+        D = np.arange(rg.N, dtype=np.int64) if nodes is None else np.asarray(nodes, dtype=np.int64)
+        n = D.shape[0]
+        self.n, self.chunk_rows, self.P = n, int(chunk_rows), P
+        nch = (n + chunk_rows - 1) // chunk_rows
+        self.n_chunks = nch
+        ck = np.arange(n, dtype=np.int64) // chunk_rows
+        od_owner = rg.owner[D]
+        # send side
+        cnt = (rg.vsub_ip[D + 1] - rg.vsub_ip[D])
+        sel = np.flatnonzero(cnt > 0)
+        key = ck[sel] * P + od_owner[sel]
+        order = sel[np.argsort(key, kind="stable")]
+        self.sub_counts = np.bincount(key, minlength=nch * P).reshape(nch, P).astype(np.int64)
+        self.sub_first = np.zeros(nch + 1, dtype=np.int64)
+        np.cumsum(self.sub_counts.sum(1), out=self.sub_first[1:])
+        scnt = cnt[order]
+        sub_ip = np.zeros(order.shape[0] + 1, dtype=np.int64)
+        np.cumsum(scnt, out=sub_ip[1:])
+        self.sub_nodes = D[order]
+        idx = np.repeat(rg.vsub_ip[self.sub_nodes] - sub_ip[:-1], scnt) + np.arange(sub_ip[-1], dtype=np.int64)
+        self.sub_ip, self.sub_ix = sub_ip, rg.vsub_ix[idx]
+        del idx
+        self.work = build_plan(sub_ip)
+        # receive side
+        opos = np.flatnonzero(od_owner == rank)
+        self.opos = opos
+        od = D[opos]
+        m = opos.shape[0]
+        self.m = m
+        self_row = rg.lrow[od]
+        self.dst = np.empty((m, 2), dtype=np.int32)
+        self.dst[:, 0], self.dst[:, 1] = self_row, rg.deg[od]
+        self.own_first = np.searchsorted(opos, np.arange(nch + 1, dtype=np.int64) * chunk_rows).astype(np.int64)
+        pr = rg.pres[self_row]
+        cum = np.zeros((m + 1, P), dtype=np.int64)
+        np.cumsum(pr, axis=0, out=cum[1:])
+        self.own_counts = cum[self.own_first[1:]] - cum[self.own_first[:-1]]
+        seg = np.zeros((nch, P), dtype=np.int64)
+        np.cumsum(self.own_counts[:, :-1], axis=1, out=seg[:, 1:])
+        ci = ck[opos]
+        row = seg[ci] + cum[1:] - cum[self.own_first[ci]] - 1
+        self.ml = np.where(pr, row, -1).astype(np.int32)
+        self.recv_first = np.zeros(nch + 1, dtype=np.int64)
+        np.cumsum(self.own_counts.sum(1), out=self.recv_first[1:])
+        ii, qq = np.nonzero(pr)
+        self.er_src = np.empty(int(self.recv_first[-1]), dtype=np.int64)
+        self.er_src[self.recv_first[ci[ii]] + row[ii, qq]] = self_row[ii]
+        self.dev = None
+
+    def chunks(self):
+        """[(s0, s1, i0, i1, h0, h1, part0, n_parts, o0, o1, r0, r1)] per chunk: its sub-rows, items, hubs and parts,
+        own destinations and receive rows"""
+        w = self.work
+        out = []
+        for c in range(self.n_chunks):
+            s0, s1 = int(self.sub_first[c]), int(self.sub_first[c + 1])
+            h0, h1 = (int(x) for x in np.searchsorted(w["hub_pos"], [s0, s1]))
+            p0, p1 = int(w["part_first"][s0]), int(w["part_first"][s1])
+            out.append((s0, s1, int(w["item_first"][s0]), int(w["item_first"][s1]), h0, h1, p0, p1 - p0,
+                        int(self.own_first[c]), int(self.own_first[c + 1]), int(self.recv_first[c]),
+                        int(self.recv_first[c + 1])))
+        return out
+
+    def device_bytes(self, gat):
+        b = 4 * (self.sub_ip.shape[0] + self.sub_ix.shape[0]) + self.work["items"].nbytes + self.work["hubs"].nbytes
+        return b + self.dst.nbytes + self.ml.nbytes + (self.er_src.nbytes if gat else 0) + 64
+
+    def upload(self, device, gat):
+        if self.dev is None:
+            def up(a):
+                return torch.from_numpy(np.ascontiguousarray(a) if a.size else np.zeros(4, dtype=a.dtype)).to(device)
+            self.dev = {"ip": up(self.sub_ip.astype(np.int32)), "ix": up(self.sub_ix), "items": up(self.work["items"]),
+                        "hubs": up(self.work["hubs"]), "dst": up(self.dst), "ml": up(self.ml)}
+        if gat and "er_src" not in self.dev:
+            self.dev["er_src"] = torch.from_numpy(self.er_src).to(device)
+        return self.dev
+
+    def pack(self, width):
+        """sub-CSR rows per wave of the partial kernels: one.  Two or four rows per wave were measured slower at every
+        width and part count of profiles/infer_parts_bench_products.txt (a slot's narrower column tiles walk the row's
+        edges once per tile)."""
+        return 1
+
+
+_RANKS = []   # [(indptr, indices, key, RankGraph)]: the rank plans of the two most recent (graph, owner, P, rank)
+
+
+def rank_graph(indptr, indices, owner, P, rank):
+    """the RankGraph of (indptr, indices) for `rank` of P with the int32 owner table `owner`, built once and cached beside
+    the graph (release() drops it)"""
+    import hashlib
+    key = (int(P), int(rank), hashlib.blake2b(owner.tobytes(), digest_size=16).hexdigest())
+    for ip, ix, k, rg in _RANKS:
+        if ip is indptr and ix is indices and k == key:
+            return rg
+    rg = RankGraph(indptr, indices, owner, P, rank)
+    _RANKS.insert(0, (indptr, indices, key, rg))
+    del _RANKS[2:]
+    return rg
+
+
+def _gather(comm, vals):
+    """all-gather of a few int64 per rank: [[...] of rank 0, ...]"""
+    dist = comm.dist
+    dev = torch.device("cpu") if dist.get_backend(comm.group) == "gloo" else comm.device
+    t = torch.tensor(vals, dtype=torch.int64, device=dev)
+    out = [torch.empty_like(t) for _ in range(comm.world)]
+    dist.all_gather(out, t, group=comm.group)
+    return [o.cpu().tolist() for o in out]
+
+
+def _exchange(comm, recv, R, send, S, send_counts, recv_counts):
+    """one all_to_all_single of send[:S] (rows grouped by destination rank) into recv[:R]"""
+    comm.exchange_into(recv[:R], send[:S], [int(c) for c in send_counts], [int(c) for c in recv_counts])
+
+
+def _sage_layer_parts(pp, dp, h, conv, relu, comm):
+    """One DistSageConv over the rank's destinations of `pp`; h: [n_own, hp] own rows.  Returns [m, round4(out)]."""
+    L = _lib()
+    st = aggr._stream()
+    dev = h.device
+    W, b = conv.fc.weight.detach().float(), conv.fc.bias.detach().float()
+    out_w, in_w = W.shape[0], W.shape[1] // 2
+    hp, op = h.shape[1], _r4(out_w)
+    chunks = pp.chunks()
+    agg_first = out_w >= in_w
+    if agg_first:
+        wc = torch.zeros((out_w, 2 * hp), dtype=torch.float32, device=dev)
+        wc[:, :in_w], wc[:, hp:hp + in_w] = W[:, :in_w], W[:, in_w:]
+        y = torch.zeros((pp.m, op), dtype=torch.float32, device=dev)
+        cat = torch.empty((min(pp.chunk_rows, max(pp.m, 1)), 2 * hp), dtype=torch.float32, device=dev)
+        Y, ldy, Wy = h, hp, hp
+    else:
+        wp = torch.zeros((2 * op, hp), dtype=torch.float32, device=dev)
+        wp[:out_w, :in_w], wp[op:op + out_w, :in_w] = W[:, :in_w], W[:, in_w:]
+        bp = torch.zeros((op,), dtype=torch.float32, device=dev)
+        bp[:out_w] = b
+        Y = torch.empty((h.shape[0], 2 * op), dtype=torch.float32, device=dev)
+        _project_rows(h, wp, Y, pp.chunk_rows)
+        ldy, Wy = 2 * op, op
+        y = torch.empty((pp.m, op), dtype=torch.float32, device=dev)
+    pack = pp.pack(Wy)
+    S_max = max([c[1] - c[0] for c in chunks] + [1])
+    R_max = max([c[11] - c[10] for c in chunks] + [1])
+    send = torch.empty((S_max, Wy), dtype=torch.float32, device=dev)
+    recv = torch.empty((R_max, Wy), dtype=torch.float32, device=dev)
+    part = _partial(max([c[7] for c in chunks] + [0]), Wy, dev)
+    for c, (s0, s1, i0, i1, h0, h1, p0, npart, o0, o1, r0, r1) in enumerate(chunks):
+        _chk(L.csl_infer_sage_part_f32(_ptr(dp["ip"]), _ptr(dp["ix"]), _ptr(dp["items"], 4 * i0), i1 - i0,
+                                       _ptr(dp["hubs"], 4 * h0) if h1 > h0 else C.c_void_p(0), h1 - h0, s0, p0,
+                                       _ptr(Y, 0 if agg_first else op), ldy, Wy, pack, _ptr(part), _ptr(send), st),
+             "csl_infer_sage_part_f32")
+        _exchange(comm, recv, r1 - r0, send, s1 - s0, pp.sub_counts[c], pp.own_counts[c])
+        if agg_first:
+            _chk(L.csl_infer_sage_merge_f32(_ptr(dp["dst"], 2 * o0), _ptr(dp["ml"], pp.P * o0), o1 - o0, pp.P, _ptr(recv),
+                                            _ptr(h), hp, hp, 0, None, 0, _ptr(cat), 2 * hp, st), "csl_infer_sage_merge_f32")
+            _gemm_into(y[o0:o1, :out_w], cat[:o1 - o0], wc, b, relu)
+        else:
+            _chk(L.csl_infer_sage_merge_f32(_ptr(dp["dst"], 2 * o0), _ptr(dp["ml"], pp.P * o0), o1 - o0, pp.P, _ptr(recv),
+                                            _ptr(Y), 2 * op, op, 1, _ptr(bp), int(relu), _ptr(y, o0 * op), op, st),
+                 "csl_infer_sage_merge_f32")
+    return y
+
+
+def _gat_layer_parts(pp, dp, h, in_map, conv, last, n_cls, comm):
+    """One DistGATConv over the rank's destinations of `pp`; h: [n_own, hp] own rows whose logical column c sits at
+    in_map[c].  Returns (table, column map) as _gat_layer."""
+    L, AL = _lib(), aggr._lib()
+    st = aggr._stream()
+    dev = h.device
+    H, D = conv.H, conv.D
+    Dp = _r4(D)
+    hp = h.shape[1]
+    n_own = h.shape[0]
+    Wt = conv.fc.weight.detach().float().view(H, D, -1)
+    wz = torch.zeros((H, Dp, hp), dtype=torch.float32, device=dev)
+    wz[:, :D, in_map] = Wt
+    wz = wz.view(H * Dp, hp)
+    al = torch.zeros((H, Dp), dtype=torch.float32, device=dev)
+    ar = torch.zeros((H, Dp), dtype=torch.float32, device=dev)
+    bz = torch.zeros((H, Dp), dtype=torch.float32, device=dev)
+    al[:, :D], ar[:, :D], bz[:, :D] = conv.attn_l.detach(), conv.attn_r.detach(), conv.bias.detach().view(H, D)
+    Cz = H * Dp
+    z = torch.empty((n_own, Cz), dtype=torch.float32, device=dev)
+    el = torch.empty((max(n_own, 1), H), dtype=torch.float32, device=dev)
+    er = torch.empty((max(n_own, 1), H), dtype=torch.float32, device=dev)
+    if Dp > 256:
+        wv = wz.view(H, Dp, hp)
+        vl, vr = torch.einsum("hdf,hd->hf", wv, al).contiguous(), torch.einsum("hdf,hd->hf", wv, ar).contiguous()
+    for r0 in range(0, n_own, pp.chunk_rows):
+        r1 = min(n_own, r0 + pp.chunk_rows)
+        _gemm_into(z[r0:r1], h[r0:r1], wz)
+        if Dp > 256:
+            _gemm_into(el[r0:r1], h[r0:r1], vl)
+            _gemm_into(er[r0:r1], h[r0:r1], vr)
+        else:
+            _chk(AL.csl_gat_logits_fwd_f32(_ptr(z[r0]), _ptr(al), _ptr(ar), r1 - r0, H, Dp, _ptr(el[r0]), _ptr(er[r0]),
+                                           st), "csl_gat_logits_fwd_f32")
+    pld = int(L.csl_infer_gat_partial_ld(H, Dp))
+    chunks = pp.chunks()
+    pack = pp.pack(Cz)
+    S_max = max([c[1] - c[0] for c in chunks] + [1])
+    R_max = max([c[11] - c[10] for c in chunks] + [1])
+    send = torch.empty((S_max, pld), dtype=torch.float32, device=dev)
+    recv = torch.empty((R_max, pld), dtype=torch.float32, device=dev)
+    er_in = torch.empty((S_max, H), dtype=torch.float32, device=dev)
+    part = _partial(max([c[7] for c in chunks] + [0]), pld, dev)
+    out = torch.empty((pp.m, n_cls if last else Cz), dtype=torch.float32, device=dev)
+    for c, (s0, s1, i0, i1, h0, h1, p0, npart, o0, o1, r0, r1) in enumerate(chunks):
+        # er of the owned destinations out to the ranks holding their neighbours (the partials' path, reversed)
+        er_out = er.index_select(0, dp["er_src"][r0:r1]) if r1 > r0 else er[:0]
+        _exchange(comm, er_in, s1 - s0, er_out, r1 - r0, pp.own_counts[c], pp.sub_counts[c])
+        _chk(L.csl_infer_gat_part_f32(_ptr(dp["ip"]), _ptr(dp["ix"]), _ptr(dp["items"], 4 * i0), i1 - i0,
+                                      _ptr(dp["hubs"], 4 * h0) if h1 > h0 else C.c_void_p(0), h1 - h0, s0, p0, _ptr(z),
+                                      _ptr(el), _ptr(er_in), H, Dp, float(conv.slope), pack, _ptr(part), _ptr(send), st),
+             "csl_infer_gat_part_f32")
+        _exchange(comm, recv, r1 - r0, send, s1 - s0, pp.sub_counts[c], pp.own_counts[c])
+        dst = out[o0:o1]
+        _chk(L.csl_infer_gat_merge_f32(_ptr(dp["ml"], pp.P * o0), o1 - o0, pp.P, _ptr(recv), H, Dp, _ptr(bz), int(last),
+                                       int(n_cls), _ptr(dst), dst.stride(0), st), "csl_infer_gat_merge_f32")
+    if last:
+        return out, None
+    cmap = (torch.arange(H, device=dev)[:, None] * Dp + torch.arange(D, device=dev)[None, :]).reshape(-1)
+    return out, cmap
+
+
+def _need_bytes_parts(model, n_own, F, plans):
+    """the device bytes full_inference_parts allocates at its peak (float32 tables and per-chunk buffers; the plans'
+    device copies not included)"""
+    f = 4
+    hid, lastp = plans
+    need, width = 0, _r4(F)
+
+    def chunk_max(pp, k):
+        return max([c[k + 1] - c[k] for c in pp.chunks()] + [1])
+    for k, conv in enumerate(model.convs):
+        pp = lastp if k + 1 == len(model.convs) else hid
+        S, R = chunk_max(pp, 0), chunk_max(pp, 10)
+        parts = max([c[7] for c in pp.chunks()] + [1])
+        if isinstance(model, splitgnn.DistSAGEModel):
+            out_w, in_w = conv.fc.weight.shape[0], conv.fc.weight.shape[1] // 2
+            op = _r4(out_w)
+            t = n_own * width + pp.m * op
+            if out_w >= in_w:
+                t += min(pp.chunk_rows, max(pp.m, 1)) * 2 * width + (S + R + parts) * width
+            else:
+                t += n_own * 2 * op + (S + R + parts) * op
+            width = op
+        else:
+            C_ = conv.H * _r4(conv.D)
+            pld = C_ + 2 * conv.H + 4
+            t = n_own * width + n_own * C_ + 2 * n_own * conv.H + pp.m * C_ + (S + R + parts) * pld + S * conv.H
+            width = C_
+        need = max(need, t)
+    return need * f
+
+
+def _nodes_key(nodes):
+    import hashlib
+    if nodes is None:
+        return -1, 0
+    h = int.from_bytes(hashlib.blake2b(nodes.tobytes(), digest_size=8).digest(), "little", signed=True)
+    return int(nodes.shape[0]), h
+
+
+def full_inference_parts(model, indptr, indices, features_own, comm, owner=None, nodes=None, chunk_rows=CHUNK_ROWS,
+                         _check=None):
+    """full_inference on one rank of a split-parallel run: float32 logits [own positions of `nodes`, n_classes] of the
+    nodes of `nodes` this rank owns, in `nodes` order (None: every node; see owns()).  Collective over comm (a
+    splitgnn.DistComm): every rank calls it with the same model, graph, owner table and nodes.
+
+    features_own: float32 [n_own, F], the rows of the rank's own nodes in ascending node order.  owner: int32 [N] owner
+    rank of every node (None: v % P).  Hidden layers are computed for the rank's own nodes, the last one for its own
+    nodes among `nodes`.  Every rank receives at most P partial rows per own destination and chunk; no rank ever holds
+    another rank's feature or hidden rows.  `nodes` is compared across ranks (length and a 64-bit hash: ValueError on
+    every rank if they differ), and the device-memory check is agreed on: if one rank would raise MemoryError, every rank
+    does, before the first exchange.  With one part the result is bitwise that of full_inference."""
+    if not isinstance(model, (splitgnn.DistSAGEModel, splitgnn.DistGATModel)):
+        raise TypeError("full_inference_parts takes a DistSAGEModel or a DistGATModel")
+    if isinstance(model, splitgnn.DistGATModel) and model.convs[-1].H * _r4(model.convs[-1].D) > GAT_LAST_MAX_C:
+        raise ValueError("full_inference_parts: the attention model's last layer has heads x classes (padded to 4) = %d > "
+                         "%d columns" % (model.convs[-1].H * _r4(model.convs[-1].D), GAT_LAST_MAX_C))
+    chunk_rows = int(chunk_rows)
+    if chunk_rows < 1:
+        raise ValueError("chunk_rows must be positive")
+    P, rank = comm.world, comm.rank
+    N = np.asarray(indptr).shape[0] - 1
+    dev = features_own.device if torch.is_tensor(features_own) and features_own.is_cuda else comm.device
+    if nodes is not None:
+        nodes = np.ascontiguousarray(np.asarray(nodes.cpu() if torch.is_tensor(nodes) else nodes).astype(np.int64)
+                                     .reshape(-1))
+    # arguments that could differ between ranks are agreed on before anything else, so that no rank is left waiting
+    err = None
+    try:
+        owner = owner_table(N, P, owner)
+        n_own = int(np.count_nonzero(owner == rank))
+        if features_own.shape[0] != n_own:
+            raise ValueError("features_own must hold the rank's %d own rows, got %d" % (n_own, features_own.shape[0]))
+        if _check is not None:
+            _check(n_own)
+    except ValueError as ex:
+        err = ex
+    ln, hs = _nodes_key(nodes)
+    got = _gather(comm, [ln, hs, int(err is not None)])
+    if any(g[2] for g in got):
+        raise err if err is not None else ValueError("full_inference_parts: invalid arguments on another rank")
+    if any(g[:2] != got[0][:2] for g in got):
+        raise ValueError("full_inference_parts: the ranks were given different nodes (lengths %s)"
+                         % [g[0] for g in got])
+    if nodes is not None and nodes.size and (nodes.min() < 0 or nodes.max() >= N):
+        raise ValueError("nodes outside [0, %d)" % N)
+    gat = isinstance(model, splitgnn.DistGATModel)
+    with torch.no_grad():
+        rg = rank_graph(indptr, indices, owner, P, rank)
+        hid = rg.plan(chunk_rows)
+        lastp = hid if nodes is None else rg.plan(chunk_rows, nodes)
+        F = features_own.shape[1]
+        upload = not (torch.is_tensor(features_own) and features_own.is_cuda and features_own.dtype == torch.float32
+                      and F % 4 == 0 and features_own.stride(1) == 1 and features_own.stride(0) == F)
+        need = _need_bytes_parts(model, n_own, F, (hid, lastp)) + (n_own * _r4(F) * 4 if upload else 0)
+        need += (0 if hid.dev is not None else hid.device_bytes(gat)) + (lastp.device_bytes(gat) if lastp is not hid else 0)
+        free, _ = torch.cuda.mem_get_info(dev)
+        free += torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+        short = [g for g in _gather(comm, [int(need), int(free)]) if g[0] > g[1]]
+        if short:
+            raise MemoryError("full_inference_parts needs %d bytes of device memory on a rank where %d are free"
+                              % (short[0][0], short[0][1]))
+        dh, dl = hid.upload(dev, gat), lastp.upload(dev, gat)
+        if upload:
+            h = torch.zeros((n_own, _r4(F)), dtype=torch.float32, device=dev)
+            if n_own:
+                h[:, :F] = torch.as_tensor(features_own).to(dev, torch.float32)
+        else:
+            h = features_own
+        in_map = torch.arange(F, device=dev)
+        Lc = len(model.convs)
+        for k, conv in enumerate(model.convs):
+            last = k + 1 == Lc
+            pp, dp = (lastp, dl) if last else (hid, dh)
+            if gat:
+                h, in_map = _gat_layer_parts(pp, dp, h, in_map, conv, last, model.n_classes, comm)
+            else:
+                h = _sage_layer_parts(pp, dp, h, conv, not last, comm)
+        if not gat:
+            n_cls = model.convs[-1].fc.weight.shape[0]
+            if h.shape[1] != n_cls:
+                h = h[:, :n_cls].contiguous()
+        return h
+
+
+def owns(N, P, rank, nodes, owner=None):
+    """bool [len(nodes)]: which of `nodes` rank `rank` owns (the rows full_inference_parts returns on that rank)"""
+    nodes = np.asarray(nodes.cpu() if torch.is_tensor(nodes) else nodes).astype(np.int64).reshape(-1)
+    own = (nodes % P) if owner is None else np.asarray(owner)[nodes]
+    return own == rank
+
+
+def evaluate_parts(model, indptr, indices, features_own, comm, nodes, labels_own, owner=None, chunk_rows=CHUNK_ROWS):
+    """evaluate() on one rank of a split-parallel run (collective, see full_inference_parts): {"accuracy", "loss", "n"}
+    of the model on `nodes`, the same dict on every rank.  labels_own: int [n_own], the labels of the rank's own nodes in
+    ascending node order.  Each rank scores its own nodes among `nodes`; the per-rank (correct, float64 loss sum, n) are
+    all-gathered and added in rank order, so the result is reproducible bit for bit."""
+    nodes = np.ascontiguousarray(np.asarray(nodes.cpu() if torch.is_tensor(nodes) else nodes).astype(np.int64).reshape(-1))
+    lab = torch.as_tensor(labels_own)
+
+    def check(n_own):
+        if lab.dim() != 1 or lab.shape[0] != n_own:
+            raise ValueError("labels_own must hold one label per own node of the rank ([%d])" % n_own)
+    logits = full_inference_parts(model, indptr, indices, features_own, comm, owner=owner, nodes=nodes,
+                                  chunk_rows=chunk_rows, _check=check)
+    N = np.asarray(indptr).shape[0] - 1
+    rg = rank_graph(indptr, indices, owner_table(N, comm.world, owner), comm.world, comm.rank)
+    mine = nodes[rg.owner[nodes] == comm.rank] if nodes.size else nodes
+    rows = torch.from_numpy(rg.lrow[mine].astype(np.int64)).to(lab.device)
+    _, correct, loss = eval_head(logits, lab[rows].to(logits.device))
+    got = _gather(comm, [correct, int(np.float64(loss).view(np.int64)), int(mine.shape[0])])
+    tc, tl, tn = 0, 0.0, 0
+    for c, l, n in got:
+        tc, tl, tn = tc + c, tl + float(np.int64(l).view(np.float64)), tn + n
+    return {"accuracy": tc / max(tn, 1), "loss": tl / max(tn, 1), "n": tn}

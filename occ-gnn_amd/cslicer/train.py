@@ -80,6 +80,8 @@ class Trainer(object):
         else:
             own = np.flatnonzero(workload == rank).astype(np.int64)   # ascending: local row = rank among owned
         self.n_own = own.shape[0]
+        # the rank's nodes (ascending) and the owner table (None: v % P), which rank-path evaluation needs
+        self.own, self.owner = own, workload
         take = (lambda a: a(own)) if callable(features) else (lambda a: a[own] if self.P > 1 else a)
         f_own = np.ascontiguousarray(take(features), dtype=np.float32)
         l_own = np.ascontiguousarray((labels(own) if callable(labels) else (labels[own] if self.P > 1 else labels)),
@@ -368,26 +370,40 @@ class Trainer(object):
 
     # -- evaluation: full-neighbour, layer-wise inference of the model as trained (cslicer.infer)
     def _infer_args(self):
-        if self.rank_path:
+        if self.rank_path and getattr(self, "comm", None) is None:
             raise NotImplementedError(
-                "evaluation runs full-neighbour inference, which needs every node's feature row in one process: the "
-                "split-parallel rank path (world > 1) holds only its own rows; evaluate a single-process or "
-                "data-parallel trainer")
+                "evaluation on the rank path runs collectively over the trainer's process group (one process per "
+                "part, each with its own rows); this rank path trainer has none")
         return self.model, self.eng.indptr, self.eng.indices, self.feat
 
     def predict(self, nodes=None, chunk_rows=None):
-        """float32 logits [len(nodes) (or N), n_classes] of the current weights by full-neighbour inference
-        (cslicer.infer.full_inference), enqueued on the training stream after every step already enqueued.  It neither
-        submits to the engine nor draws random numbers nor touches the optimizer state."""
+        """float32 logits of the current weights by full-neighbour inference, enqueued on the training stream after every
+        step already enqueued.  It neither submits to the engine nor draws random numbers nor touches the optimizer
+        state.  Single process / data-parallel replica: [len(nodes) (or N), n_classes] (cslicer.infer.full_inference).
+        Rank path: collective, every rank calls it with the same nodes; the logits of the rank's own nodes among `nodes`
+        in `nodes` order, the rows owns(nodes) marks (cslicer.infer.full_inference_parts)."""
         from . import infer
-        return infer.full_inference(*self._infer_args(), nodes=nodes, chunk_rows=chunk_rows or infer.CHUNK_ROWS)
+        args = self._infer_args()
+        chunk_rows = chunk_rows or infer.CHUNK_ROWS
+        if self.rank_path:
+            return infer.full_inference_parts(*args, self.comm, owner=self.owner, nodes=nodes, chunk_rows=chunk_rows)
+        return infer.full_inference(*args, nodes=nodes, chunk_rows=chunk_rows)
+
+    def owns(self, nodes):
+        """bool mask over `nodes`: the nodes this rank owns, i.e. the rows predict(nodes) returns on the rank path"""
+        from . import infer
+        return infer.owns(self.N, self.P, self.rank, nodes, self.owner)
 
     def evaluate(self, nodes, chunk_rows=None):
         """{"accuracy", "loss", "n"} of the current weights on `nodes` (argmax accuracy, mean cross-entropy against the
-        trainer's labels) by full-neighbour inference; see predict()."""
+        trainer's labels) by full-neighbour inference; see predict().  Rank path: collective, the same dict on every
+        rank (cslicer.infer.evaluate_parts)."""
         from . import infer
-        return infer.evaluate(*self._infer_args(), nodes=nodes, labels=self.labels,
-                              chunk_rows=chunk_rows or infer.CHUNK_ROWS)
+        args = self._infer_args()
+        chunk_rows = chunk_rows or infer.CHUNK_ROWS
+        if self.rank_path:
+            return infer.evaluate_parts(*args, self.comm, nodes, self.labels, owner=self.owner, chunk_rows=chunk_rows)
+        return infer.evaluate(*args, nodes=nodes, labels=self.labels, chunk_rows=chunk_rows)
 
     def close(self):
         from . import infer
@@ -541,7 +557,7 @@ def main(argv=None):
     --eval-split (extra): `none` (default) trains on every node and never evaluates; `file` trains on the L0 directory's
     train_idx.bin and evaluates val_idx.bin; `holdout` trains on a seeded 80 % of the nodes and evaluates the other
     20 %.  With a split the model is evaluated by full-neighbour inference every --eval-every epochs and after the last
-    one (single process only)."""
+    one; with one process per part every rank takes part (each holds only its own rows) and rank 0 prints `Eval Acc`."""
     import os
     a = _parser().parse_args(argv)
     from . import l0
@@ -575,9 +591,6 @@ def main(argv=None):
         n_classes = meta["num_classes"]
         if a.partition == "file":
             workload = np.fromfile(os.path.join(a.graph, "partition_map_opt.bin"), dtype=np.int32)
-    if a.eval_split != "none" and world > 1:
-        raise SystemExit("--eval-split runs full-neighbour inference in one process (every feature row); it is not "
-                         "available with one process per part")
     train_nodes, eval_nodes = _split(a, indptr.shape[0] - 1)
     fan = tuple(int(x) for x in a.fan_out.split(","))[::-1]          # engine order: layer 0 = hop from the seeds
     if len(fan) != a.num_layers:
