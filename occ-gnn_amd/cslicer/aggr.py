@@ -61,6 +61,8 @@ def _lib():
         L.csl_softmax_ce_f32.argtypes = [vp, i64, i64, i32, vp, vp, vp, f32, vp, vp, i64, vp, vp]
         L.csl_softmax_ce_scratch.argtypes = [i64]
         L.csl_softmax_ce_scratch.restype = i64
+        L.csl_softmax_ce_partial_f32.argtypes = [vp, i64, i64, i64, i32, vp, vp, vp, f32, vp, i64, vp, vp, vp]
+        L.csl_reduce_multi_f32.argtypes = [i32, vp, vp, vp, vp, vp]
         L.csl_adam_f32.argtypes = [i32, vp, vp, vp, vp, vp, f32, f32, f32, f32, i64, vp]
         L.csl_sage_cat_bwd_t_f32.argtypes = [vp, vp, vp, vp, i64, vp, i64, i64, i64, vp, i64, vp, vp, i32, vp]
         L.csl_sage_cat_bwd_t_scratch.argtypes = [i64, i32]
@@ -530,6 +532,10 @@ class SageRankStep(object):
         return self._ws[off:off + rows * width].view(rows, width)
 
     def _exchange(self, user, layer, backward, src, dst, width, stream):
+        # The native step enters every exchange on every rank, whatever the rank's own slice holds (a collective that
+        # one rank skipped would hang the group).  A world of one has no peer: nothing to exchange, nothing to wait for.
+        if getattr(self.comm, "world", 0) == 1:
+            return 0
         try:
             s = self._cur[layer]
             send, recv = (s.to_counts, s.from_counts) if backward else (s.from_counts, s.to_counts)
@@ -563,7 +569,8 @@ class SageRankStep(object):
 
     def _wait(self, user, layer, backward, stream):
         try:
-            torch.cuda.current_stream().wait_event(self._done.pop((layer, backward)))
+            if getattr(self.comm, "world", 0) != 1:             # (a world of one started no exchange)
+                torch.cuda.current_stream().wait_event(self._done.pop((layer, backward)))
             return 0
         except Exception as ex:
             self._exc = ex

@@ -1424,7 +1424,7 @@ int csl_spmm_sum_bwd_f32(const int32_t* indptr, const int32_t* indices, const in
                          const float* grad_out, int64_t ldg, int32_t compact, float* grad_x, int64_t ldx, int32_t H,
                          void* stream) {
   if (n_rows == 0) return CSL_OK;
-  if (n_rows < 0 || H < 1 || !indptr || !grad_out || !grad_x) return CSL_E_INVALID;
+  if (n_rows < 0 || H < 1 || !indptr || !grad_out || !grad_x || ldg < H || ldx < H) return CSL_E_INVALID;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(k_spmm_sum_bwd, dim3((unsigned)((n_rows + BLK / 64 - 1) / (BLK / 64))), dim3(BLK), 0, st,
                      indptr, indices, rows, (long long)n_rows,
@@ -1435,7 +1435,7 @@ int csl_spmm_sum_bwd_f32(const int32_t* indptr, const int32_t* indices, const in
 int csl_gather_rows_f32(const float* src, int64_t lds, const int32_t* idx, int64_t n, float* dst, int64_t ldd,
                         int32_t H, void* stream) {
   if (n == 0) return CSL_OK;
-  if (n < 0 || H < 1 || !idx || !dst) return CSL_E_INVALID;
+  if (n < 0 || H < 1 || !idx || !dst || !src || lds < H || ldd < H) return CSL_E_INVALID;
   hipStream_t st = (hipStream_t)stream;
   const int G = group_for(H), v = vec_ok(src, lds, dst, ldd, H);
   DISPATCH_G(G, k_gather_rows, n, src, (long long)lds, idx, (long long)n, dst, (long long)ldd, (int)H, v);

@@ -459,7 +459,11 @@ int csl_sage_rank_fwd_bwd_f32(int32_t n_layers, const int32_t* dims, const csl_s
     const int32_t* map = k == 0 ? feat_rows : nullptr;
     if (k == 0 && o.wpack >= 0) {
       // no boundary rows: the single-GPU layer as one kernel (gather -> fp32 MFMA -> bias + ReLU); the CSR degree IS the
-      // true degree, the owned rows ARE the out rows
+      // true degree, the owned rows ARE the out rows.  "No boundary rows" is a property of THIS part's slice: a peer may
+      // have some in the same minibatch, and the exchange is a collective every rank must enter -- so it is issued here
+      // too, with the empty buffers (whether a collective is entered depends only on L, which all ranks share)
+      XCHG(0, 0, ws + o.send[0], ws + o.recv[0], in);
+      XWAIT(0, 0);
       STEP(csl_sage_fwd_mfma_f32(s.indptr, s.indices, s.self_ids_in, feat_rows, feat, ldf, weights[0], 2 * (int64_t)in,
                                  biases[0], s.n_owned, o.mp[0], in, out, 0, L > 1 ? 1 : 0, ws + o.cat[0], 2 * (int64_t)in,
                                  ws + o.y[0], out, ws + o.wpack, stream));

@@ -2,7 +2,8 @@
 against plain torch fp32 references.  The reference's Python consumer needs DGL (absent here,
 ModuleNotFoundError) and ships no goldens: these results are pinned by analytic torch references
 only ("parity unpinned" by the reference).  Tolerance: 1e-5 (north_star: aggregation outputs
-within 1e-5 fp32)."""
+within 1e-5 fp32).  The float64 pins of the GraphSAGE kernels at their dispatch edges (group sizes, the scalar
+fallback, block resizes, hub segments) are in tests/test_gpu_sage_aggr.py, against tests/sage_ref.py."""
 import numpy as np
 import pytest
 import torch

@@ -20,44 +20,10 @@ pytestmark = pytest.mark.gpu
 
 
 def _float64_reference(trav, feats, labels, weights, biases, n_nodes):
-    """loss and parameter gradients (float64, CPU autograd) of the model on the oracle's traversal"""
-    L = len(trav["nbr_counts"])
-    ws = [w.detach().double().cpu().requires_grad_() for w in weights]
-    bs = [b.detach().double().cpu().requires_grad_() for b in biases]
-    src_nodes = np.asarray(trav["frontier"][L], dtype=np.int64)           # every node the deepest hop reads
-    h = torch.from_numpy(np.asarray(feats)[src_nodes]).double()
-    for k in range(L):
-        l = L - 1 - k
-        fr = np.asarray(trav["frontier"][l], dtype=np.int64)
-        counts = np.asarray(trav["nbr_counts"][l], dtype=np.int64)
-        flat = np.asarray(trav["nbr_flat"][l], dtype=np.int64)
-        lut = np.full(n_nodes, -1, dtype=np.int64)
-        lut[src_nodes] = np.arange(src_nodes.shape[0])
-        starts = np.zeros(fr.shape[0] + 1, dtype=np.int64)
-        np.cumsum(counts, out=starts[1:])
-        assert np.array_equal(flat[starts[:-1]], fr)                       # every list starts with the node itself
-        keep = np.ones(flat.shape[0], dtype=bool)
-        keep[starts[:-1]] = False
-        row = np.repeat(np.arange(fr.shape[0]), counts)
-        keep &= flat != fr[row]                                            # (a sampled self loop is not a neighbour)
-        row, nb = row[keep], flat[keep]
-        assert (lut[nb] >= 0).all() and (lut[fr] >= 0).all()
-        agg = torch.zeros(fr.shape[0], h.shape[1], dtype=torch.float64)
-        agg.index_add_(0, torch.from_numpy(row), h[torch.from_numpy(lut[nb])])
-        deg = torch.from_numpy(np.bincount(row, minlength=fr.shape[0])).double().clamp(min=1)
-        cat = torch.cat([h[torch.from_numpy(lut[fr])], agg / deg.unsqueeze(1)], 1)
-        h = cat @ ws[k].t() + bs[k]
-        if k + 1 < L:
-            h = torch.relu(h)
-        src_nodes = fr
-    seeds = np.asarray(trav["frontier"][0], dtype=np.int64)
-    y = torch.from_numpy(np.asarray(labels)[seeds])
-    loss = torch.nn.functional.cross_entropy(h, y, reduction="sum") / seeds.shape[0]
-    loss.backward()
-    grads = []
-    for w, b in zip(ws, bs):
-        grads += [w.grad, b.grad]
-    return float(loss.detach()), grads
+    """loss and parameter gradients (float64, CPU autograd) of the model on the oracle's traversal: tests/sage_ref.py,
+    which also holds the same model with the backward written out (checked against this one without a GPU)"""
+    import sage_ref
+    return sage_ref.model_on_traversal(trav, feats, labels, weights, biases, n_nodes, autograd=True)
 
 
 @pytest.mark.parametrize("fused_deepest_layer", [True, False])
