@@ -10,7 +10,7 @@ import os
 
 import torch
 
-from . import _abi
+from . import _abi, l0
 
 SYMBOLS = ["csl_spmm_sum_f32", "csl_spmm_sum_bwd_f32", "csl_gather_rows_f32",
            "csl_scatter_add_rows_f32", "csl_div_rows_f32", "csl_gat_fwd_f32", "csl_gat_bwd_f32",
@@ -29,6 +29,13 @@ SYMBOLS = ["csl_spmm_sum_f32", "csl_spmm_sum_bwd_f32", "csl_gather_rows_f32",
            "csl_elu_bwd_colsum_scratch", "csl_elu_bwd_colsum_f32", "csl_gat_in_proj_ok", "csl_gat_in_proj_fpad",
            "csl_gat_in_proj_f32", "csl_gat_in_proj_bwd_scratch", "csl_gat_in_proj_bwd_f32", "csl_gat_in_layer_fwd_scratch",
            "csl_gat_in_layer_fwd_f32", "csl_gat_in_layer_bwd_scratch", "csl_gat_in_layer_bwd_f32"]
+# every symbol include/cslicer_feat16.h declares (checked by tests/test_feat16_cpu.py): the readers of a 16-bit table
+FEAT16_SYMBOLS = ["csl_sage_fwd_mfma_x16", "csl_sage_cat_x16", "csl_spmm_sum_map_x16", "csl_gather_rows_x16",
+                  "csl_sage_fwd_bwd_x16", "csl_sage_rank_fwd_bwd_x16"]
+# element kinds of a 16-bit feature table (CSL_FEAT_F16 / CSL_FEAT_BF16); a float32 table has the fp32 entry points
+FEAT_KINDS = {torch.float16: 1, torch.bfloat16: 2}
+# the names a feature table's element type goes by (cslicer.l0.FEATURE_DTYPES: the one list) -> torch dtypes
+FEATURE_DTYPES = {name: getattr(torch, name) for name in l0.FEATURE_DTYPES}
 _ready = False
 _GAT_TORCH_MM = bool(os.environ.get("CSLICER_GAT_TORCH_MM"))
 
@@ -124,6 +131,14 @@ def _lib():
         L.csl_gat_in_layer_bwd_scratch.restype = i64
         L.csl_gat_in_layer_bwd_f32.argtypes = [vp, vp, vp, vp, vp, i64, i32, vp, vp, vp, i32, i32, f32, i32, i64, i64, i32,
                                                vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.csl_sage_fwd_mfma_x16.argtypes = [vp, vp, vp, vp, vp, i32, i64, vp, i64, vp, i64, i64, i32, i32, i32, i32, vp, i64,
+                                            vp, i64, vp, vp]
+        L.csl_sage_cat_x16.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i64, vp, i64, i64, i64, vp, i64, i32, i32, vp]
+        L.csl_spmm_sum_map_x16.argtypes = [vp, vp, vp, i64, vp, i32, i64, vp, vp, i64, i32, i32, vp]
+        L.csl_gather_rows_x16.argtypes = [vp, i32, i64, vp, i64, vp, i64, i32, vp]
+        L.csl_sage_fwd_bwd_x16.argtypes = [i32, vp, vp, vp, vp, vp, i32, i64, vp, vp, vp, f32, i64, i32, vp, vp, vp, i64, vp]
+        L.csl_sage_rank_fwd_bwd_x16.argtypes = [i32, vp, vp, vp, vp, vp, i32, i64, vp, vp, vp, vp, f32, i64, i32, EXCHANGE_FN,
+                                                EXCHANGE_WAIT_FN, vp, vp, vp, vp, i64, vp]
         _ready = True
     return L
 
@@ -152,6 +167,17 @@ def _f32(x):
     if x.dtype != torch.float32 or not x.is_cuda:
         raise TypeError("expected a float32 CUDA tensor")
     return x if x.stride(-1) == 1 else x.contiguous()
+
+
+def _table(x):
+    """a feature table: float32 (-> None) or 16-bit (-> its element kind), row-contiguous on the device"""
+    if not x.is_cuda or x.dim() != 2 or x.stride(-1) != 1:
+        raise TypeError("expected a CUDA matrix with unit column stride")
+    if x.dtype == torch.float32:
+        return None
+    if x.dtype not in FEAT_KINDS:
+        raise TypeError("a feature table is float32, float16 or bfloat16, not %s" % x.dtype)
+    return FEAT_KINDS[x.dtype]
 
 
 def _i32(x):
@@ -212,8 +238,10 @@ def spmm_sum_bwd(indptr, indices, grad_out, n_src, rows=None, compact=False, out
 def gather_rows(src, idx, out=None):
     """dst[k] = src[idx[k]] (zero row for idx -1): pull_for_remotes / self_gather.
     out: optional destination, [len(idx), H] with unit column stride (rows may be strided: a column
-    block of a wider matrix)."""
-    src = _f32(src)
+    block of a wider matrix).  src may be a 16-bit feature table (float16 / bfloat16): its rows arrive upcast
+    (csl_gather_rows_x16), which is how every path without a 16-bit kernel of its own reads such a table."""
+    kind = _table(src) if src.dtype != torch.float32 else None
+    src = _f32(src) if kind is None else src
     idx = _i32(idx)
     if out is None:
         dst = torch.empty((idx.numel(), src.shape[1]), dtype=torch.float32, device=src.device)
@@ -221,6 +249,10 @@ def gather_rows(src, idx, out=None):
         dst = out
         if dst.shape != (idx.numel(), src.shape[1]) or dst.stride(-1) != 1 or dst.dtype != torch.float32:
             raise ValueError("out must be float32 [len(idx), H] with unit column stride")
+    if kind is not None:
+        _chk(_lib().csl_gather_rows_x16(_p(src), kind, src.stride(0), _p(idx), idx.numel(), _p(dst), dst.stride(0),
+                                        src.shape[1], _stream()), "csl_gather_rows_x16")
+        return dst
     _chk(_lib().csl_gather_rows_f32(_p(src), src.stride(0), _p(idx), idx.numel(), _p(dst), dst.stride(0),
                                     src.shape[1], _stream()), "csl_gather_rows_f32")
     return dst
@@ -259,8 +291,9 @@ def sage_cat(x, self_ids, n, n_pad, indptr=None, indices=None, owned=None, deg=N
              relu_in=False):
     """The operand of Linear(2*in, out) in one pass (csl_sage_cat_f32): [n_pad, 2*H] with
     cat[:, :H] = x[map(self_ids)], cat[:, H:] = mean over the CSR row of x[map(indices)] (indptr given) or
-    agg[owned] / deg (indptr None).  Rows n..n_pad are zero."""
-    x = _f32(x)
+    agg[owned] / deg (indptr None).  Rows n..n_pad are zero.  x may be a 16-bit feature table (csl_sage_cat_x16)."""
+    kind = _table(x) if x.dtype != torch.float32 else None
+    x = _f32(x) if kind is None else x
     H = x.shape[1]
     cat = torch.empty((n_pad, 2 * H), dtype=torch.float32, device=x.device)
     nul = C.c_void_p(0)
@@ -271,17 +304,47 @@ def sage_cat(x, self_ids, n, n_pad, indptr=None, indices=None, owned=None, deg=N
         agg = _f32(agg)
         args = (nul, nul, _p(_i32(self_ids)), _p(_i32(owned)), _p(_i32(deg)),
                 _p(rowmap) if rowmap is not None else nul, _p(x), x.stride(0), _p(agg), agg.stride(0))
+    if kind is not None:
+        # (the table's kind follows its pointer: args = (..., rowmap, x, ldx, agg, lda))
+        _chk(_lib().csl_sage_cat_x16(*args[:7], kind, *args[7:], n, n_pad, _p(cat), cat.stride(0), H, 1 if relu_in else 0,
+                                     _stream()), "csl_sage_cat_x16")
+        return cat
     _chk(_lib().csl_sage_cat_f32(*args, n, n_pad, _p(cat), cat.stride(0), H, 1 if relu_in else 0, _stream()),
          "csl_sage_cat_f32")
     return cat
+
+
+def spmm_sum_map(indptr, indices, x, rows, rowmap=None, compact=False, n_out=None):
+    """Sum-aggregate of the listed CSR rows over a resident table read through `rowmap` (csl_spmm_sum_map_f32, or
+    csl_spmm_sum_map_x16 for a float16 / bfloat16 table): the k-th listed row goes to out[k] (compact: a send buffer)
+    or to out[rows[k]] (out [n_out, H], other rows zero)."""
+    kind = _table(x) if x.dtype != torch.float32 else None
+    x = _f32(x) if kind is None else x
+    rows = _i32(rows)
+    H = x.shape[1]
+    if compact:
+        out = torch.empty((rows.numel(), H), dtype=torch.float32, device=x.device)
+    else:
+        out = torch.zeros((n_out, H), dtype=torch.float32, device=x.device)
+    nul = C.c_void_p(0)
+    head = (_p(_i32(indptr)), _p(_i32(indices)), _p(rows), rows.numel(), _p(x))
+    tail = (x.stride(0), _p(_i32(rowmap)) if rowmap is not None else nul, _p(out), out.stride(0), H, 1 if compact else 0,
+            _stream())
+    if kind is not None:
+        _chk(_lib().csl_spmm_sum_map_x16(*head, kind, *tail), "csl_spmm_sum_map_x16")
+    else:
+        _chk(_lib().csl_spmm_sum_map_f32(*head, *tail), "csl_spmm_sum_map_f32")
+    return out
 
 
 def sage_fwd_mfma(x, self_ids, indptr, indices, weight, bias, n, n_pad, rowmap=None, relu_in=False, relu_out=False,
                   want_cat=False):
     """A GraphSAGE layer's forward as one kernel on the fp32 matrix cores (csl_sage_fwd_mfma_f32):
     y [n_pad, out] = act([x[map(self_ids)] | mean over the CSR row of x[map(indices)]] weight^T + bias); with want_cat
-    also the operand [n_pad, 2 H] (what sage_cat returns).  weight [out, 2 H] (torch's Linear.weight)."""
-    x, weight = _f32(x), _f32(weight)
+    also the operand [n_pad, 2 H] (what sage_cat returns).  weight [out, 2 H] (torch's Linear.weight).  x may be a
+    16-bit feature table (csl_sage_fwd_mfma_x16: the producers load 8 bytes per lane and upcast in registers)."""
+    kind = _table(x) if x.dtype != torch.float32 else None
+    x, weight = (_f32(x) if kind is None else x), _f32(weight)
     H, out = x.shape[1], weight.shape[0]
     L = _lib()
     nw = L.csl_sage_fwd_mfma_scratch(H, out)
@@ -291,12 +354,14 @@ def sage_fwd_mfma(x, self_ids, indptr, indices, weight, bias, n, n_pad, rowmap=N
     y = torch.empty((n_pad, out), dtype=torch.float32, device=x.device)
     cat = torch.empty((n_pad, 2 * H), dtype=torch.float32, device=x.device) if want_cat else None
     nul = C.c_void_p(0)
-    _chk(L.csl_sage_fwd_mfma_f32(_p(_i32(indptr)), _p(_i32(indices)), _p(_i32(self_ids)),
-                                 _p(rowmap) if rowmap is not None else nul, _p(x), x.stride(0), _p(weight),
-                                 weight.stride(0), _p(_f32(bias)) if bias is not None else nul, n, n_pad, H, out,
-                                 1 if relu_in else 0, 1 if relu_out else 0, _p(cat) if want_cat else nul,
-                                 cat.stride(0) if want_cat else 0, _p(y), y.stride(0), _p(wpack), _stream()),
-         "csl_sage_fwd_mfma_f32")
+    head = (_p(_i32(indptr)), _p(_i32(indices)), _p(_i32(self_ids)), _p(rowmap) if rowmap is not None else nul, _p(x))
+    tail = (x.stride(0), _p(weight), weight.stride(0), _p(_f32(bias)) if bias is not None else nul, n, n_pad, H, out,
+            1 if relu_in else 0, 1 if relu_out else 0, _p(cat) if want_cat else nul, cat.stride(0) if want_cat else 0,
+            _p(y), y.stride(0), _p(wpack), _stream())
+    if kind is not None:
+        _chk(L.csl_sage_fwd_mfma_x16(*head, kind, *tail), "csl_sage_fwd_mfma_x16")
+    else:
+        _chk(L.csl_sage_fwd_mfma_f32(*head, *tail), "csl_sage_fwd_mfma_f32")
     return (y, cat) if want_cat else y
 
 
@@ -476,10 +541,15 @@ class SageStep(object):
             raise _abi.CslError(need, "csl_sage_fwd_bwd_workspace: unsupported model or slices")
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty((int(need * 1.25) + 1024,), dtype=torch.float32, device=feat.device)
-        rc = L.csl_sage_fwd_bwd_f32(self.L, self._dims, self._sl, self._w, self._b, feat.data_ptr(), feat.stride(0),
-                                    slices[0].ptr(A.IN_NODES), slices[-1].ptr(A.OUT_NODES), labels.data_ptr(),
-                                    float(scale), self.row_pad, self.n_slabs, self.grads.data_ptr(),
-                                    loss_out.data_ptr(), self._ws.data_ptr(), self._ws.numel(), _stream())
+        # a 16-bit table (float16 / bfloat16) goes to the step's _x16 twin: only its deepest layer's forward differs
+        kind = _table(feat)
+        tail = (feat.stride(0), slices[0].ptr(A.IN_NODES), slices[-1].ptr(A.OUT_NODES), labels.data_ptr(),
+                float(scale), self.row_pad, self.n_slabs, self.grads.data_ptr(),
+                loss_out.data_ptr(), self._ws.data_ptr(), self._ws.numel(), _stream())
+        if kind is not None:
+            rc = L.csl_sage_fwd_bwd_x16(self.L, self._dims, self._sl, self._w, self._b, feat.data_ptr(), kind, *tail)
+        else:
+            rc = L.csl_sage_fwd_bwd_f32(self.L, self._dims, self._sl, self._w, self._b, feat.data_ptr(), *tail)
         if rc < 0:
             raise _abi.CslError(rc, "csl_sage_fwd_bwd_f32: " + L.csl_sage_last_error().decode() + " / " +
                                 L.csl_gemm_last_error().decode())
@@ -600,12 +670,16 @@ class SageRankStep(object):
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty((int(need * 1.25) + 1024,), dtype=torch.float32, device=feat.device)
         self._cur, self._exc = slices, None
-        rc = L.csl_sage_rank_fwd_bwd_f32(self.L, self._dims, self._sl, self._w, self._b, feat.data_ptr(), feat.stride(0),
-                                         _p(feat_rows), _p(seed_ids), _p(label_rows) if label_rows is not None else None,
-                                         labels.data_ptr(), float(scale), self.row_pad, self.n_slabs, self._cb,
-                                         self._cb_wait if self.overlap else EXCHANGE_WAIT_FN(0), None,
-                                         self.grads.data_ptr(), loss_out.data_ptr(), self._ws.data_ptr(),
-                                         self._ws.numel(), _stream())
+        kind = _table(feat)      # (a 16-bit table: the step's _x16 twin, the same exchanges)
+        tail = (feat.stride(0), _p(feat_rows), _p(seed_ids), _p(label_rows) if label_rows is not None else None,
+                labels.data_ptr(), float(scale), self.row_pad, self.n_slabs, self._cb,
+                self._cb_wait if self.overlap else EXCHANGE_WAIT_FN(0), None,
+                self.grads.data_ptr(), loss_out.data_ptr(), self._ws.data_ptr(),
+                self._ws.numel(), _stream())
+        if kind is not None:
+            rc = L.csl_sage_rank_fwd_bwd_x16(self.L, self._dims, self._sl, self._w, self._b, feat.data_ptr(), kind, *tail)
+        else:
+            rc = L.csl_sage_rank_fwd_bwd_f32(self.L, self._dims, self._sl, self._w, self._b, feat.data_ptr(), *tail)
         self._cur = None
         if self._exc is not None:
             raise self._exc

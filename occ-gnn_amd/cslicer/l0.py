@@ -5,10 +5,14 @@ reader cslicer/dataset.cpp:18-113):
 
     <dir>/meta.txt            key=value lines: num_nodes, num_edges, feature_dim,
                               csum_features, csum_labels, csum_offsets,
-                              csum_edges, num_classes
+                              csum_edges, num_classes; optionally
+                              feature_dtype=float32|float16|bfloat16 (no key:
+                              float32, what the reference writes and reads)
     <dir>/indptr.bin          int64[N+1]
     <dir>/indices.bin         int64[E]
-    <dir>/features.bin        float32[N*feature_dim]   (unused by the slicer)
+    <dir>/features.bin        float32[N*feature_dim]   (unused by the slicer);
+                              float16 / bfloat16 (raw 16-bit words) when
+                              meta.txt says so
     <dir>/labels.bin          int32[N]                 (unused by the slicer)
     <dir>/partition_map_opt.bin int32[N]               (loaded, ignored: the
                               reference uses v % 4, cslicer/pyfrontend.cpp:57)
@@ -116,13 +120,57 @@ def synth_preset(name, seed=0):
     return synth_graph(n, d, seed=seed)
 
 
+FEATURE_DTYPES = ("float32", "float16", "bfloat16")
+
+
+def to_bfloat16_words(x):
+    """float32 array -> its bfloat16 values as raw uint16 words, round to nearest even (what
+    torch.as_tensor(x).to(torch.bfloat16) stores); a NaN stays a (quiet) NaN."""
+    b = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
+    r = ((b + np.uint32(0x7FFF) + ((b >> np.uint32(16)) & np.uint32(1))) >> np.uint32(16)).astype(np.uint16)
+    nan = (b & np.uint32(0x7FFFFFFF)) > np.uint32(0x7F800000)
+    if nan.any():
+        r[nan] = ((b[nan] >> np.uint32(16)) | np.uint32(0x0040)).astype(np.uint16)
+    return r
+
+
+def bfloat16_words_to_float32(w):
+    """raw bfloat16 words (uint16) -> float32, exact"""
+    return (np.asarray(w).astype(np.uint32) << np.uint32(16)).view(np.float32)
+
+
+def feature_file_dtype(feature_dtype):
+    """numpy dtype of features.bin's elements: bfloat16 has none, its words are read as uint16"""
+    if feature_dtype not in FEATURE_DTYPES:
+        raise ValueError("feature_dtype must be one of %s, not %r" % (", ".join(FEATURE_DTYPES), feature_dtype))
+    return {"float32": np.float32, "float16": np.float16, "bfloat16": np.uint16}[feature_dtype]
+
+
+def read_features(path, meta=None, mmap=True):
+    """(rows, feature_dtype) of an L0 directory: features.bin as [N, feature_dim] in its stored element type -- float32,
+    float16, or for bfloat16 the raw uint16 words (bfloat16_words_to_float32, or a torch view as torch.bfloat16)."""
+    meta = read_meta(path) if meta is None else meta
+    dt = feature_file_dtype(meta["feature_dtype"])
+    shape = (meta["num_nodes"], meta["feature_dim"])
+    f = os.path.join(path, "features.bin")
+    if mmap:
+        return np.memmap(f, dtype=dt, mode="r", shape=shape), meta["feature_dtype"]
+    return np.fromfile(f, dtype=dt, count=shape[0] * shape[1]).reshape(shape), meta["feature_dtype"]
+
+
 def write_l0(path, indptr, indices, features=None, labels=None, partition=None,
-             feature_dim=None, num_classes=2, train_idx=None, val_idx=None):
+             feature_dim=None, num_classes=2, train_idx=None, val_idx=None, feature_dtype=None):
     """Write an L0 dataset directory readable by the reference's Dataset class.  train_idx / val_idx (both or
     neither): the node split, written as train_idx.bin / val_idx.bin (int64) with their sums csum_train / csum_test
-    in meta.txt, as the reference's converter does (convert_dgl_dataset.py:107-112)."""
+    in meta.txt, as the reference's converter does (convert_dgl_dataset.py:107-112).
+
+    feature_dtype ("float32", "float16" or "bfloat16"; None: float32 and no key, the reference's own format):
+    features.bin is written in that element type -- float32 input rounded to nearest even, bfloat16 as its raw 16-bit
+    words -- and meta.txt records feature_dtype=.  csum_features is the sum of the STORED values, as for float32."""
     if (train_idx is None) != (val_idx is None):
         raise ValueError("write_l0: pass both train_idx and val_idx, or neither")
+    if feature_dtype is not None:
+        feature_file_dtype(feature_dtype)      # (raises for an unknown name)
     os.makedirs(path, exist_ok=True)
     indptr = np.ascontiguousarray(indptr, dtype=np.int64)
     indices = np.ascontiguousarray(indices, dtype=np.int64)
@@ -139,14 +187,25 @@ def write_l0(path, indptr, indices, features=None, labels=None, partition=None,
     partition = np.ascontiguousarray(partition, dtype=np.int32)
     indptr.tofile(os.path.join(path, "indptr.bin"))
     indices.tofile(os.path.join(path, "indices.bin"))
-    features.tofile(os.path.join(path, "features.bin"))
+    if feature_dtype == "float16":
+        with np.errstate(over="ignore"):
+            stored = features.astype(np.float16)              # (numpy rounds to nearest even, as torch does)
+        if np.isinf(stored).any() and not np.isinf(features).any():
+            raise ValueError("write_l0: features beyond float16's range (65504) would be stored as Inf; use bfloat16")
+        fsum = stored.astype(np.float32).sum(dtype=np.float64)
+    elif feature_dtype == "bfloat16":
+        stored = to_bfloat16_words(features)
+        fsum = bfloat16_words_to_float32(stored).sum(dtype=np.float64)
+    else:
+        stored, fsum = features, features.sum(dtype=np.float64)
+    stored.tofile(os.path.join(path, "features.bin"))
     labels.tofile(os.path.join(path, "labels.bin"))
     partition.tofile(os.path.join(path, "partition_map_opt.bin"))
     meta = {
         "num_nodes": n,
         "num_edges": int(indices.shape[0]),
         "feature_dim": int(features.shape[1]),
-        "csum_features": int(features.sum(dtype=np.float64)),
+        "csum_features": int(fsum),
         "csum_labels": int(labels.sum(dtype=np.int64)),
     }
     if train_idx is not None:
@@ -167,6 +226,9 @@ def write_l0(path, indptr, indices, features=None, labels=None, partition=None,
     with open(os.path.join(path, "meta.txt"), "w") as f:
         for k, v in meta.items():
             f.write("%s=%d\n" % (k, v))
+        if feature_dtype is not None:
+            f.write("feature_dtype=%s\n" % feature_dtype)
+    meta["feature_dtype"] = feature_dtype or "float32"
     return meta
 
 
@@ -180,7 +242,9 @@ def read_meta(path):
             if not line:
                 continue
             k, _, v = line.partition("=")
-            meta[k] = int(v)
+            meta[k] = v if k == "feature_dtype" else int(v)
+    meta.setdefault("feature_dtype", "float32")     # (a directory without the key: the reference's float32)
+    feature_file_dtype(meta["feature_dtype"])
     return meta
 
 
@@ -258,6 +322,7 @@ def from_edge_list(num_nodes, src, dst, symmetric=False, rows="in"):
 
 def _main(argv):
     """python -m cslicer.l0 convert <edges.npz|edges.npy> <out_dir> [--symmetric] [--num-nodes N]
+                                 [--feature-dtype float32|float16|bfloat16]
     edges.npz: arrays `src`, `dst` (optionally `features`, `labels`, `partition`, `num_nodes`);
     edges.npy: int array of shape [2, E] or [E, 2]."""
     import argparse
@@ -268,6 +333,8 @@ def _main(argv):
     c.add_argument("out_dir")
     c.add_argument("--symmetric", action="store_true")
     c.add_argument("--num-nodes", type=int, default=None)
+    c.add_argument("--feature-dtype", choices=FEATURE_DTYPES, default=None,
+                   help="element type of features.bin (recorded in meta.txt; default: float32, no key)")
     a = ap.parse_args(argv)
     feats = labels = part = None
     if a.edges.endswith(".npz"):
@@ -285,7 +352,8 @@ def _main(argv):
         n = int(max(src.max(), dst.max())) + 1
     indptr, indices = from_edge_list(n, src, dst, symmetric=a.symmetric)
     classes = int(labels.max()) + 1 if labels is not None else 2
-    meta = write_l0(a.out_dir, indptr, indices, features=feats, labels=labels, partition=part, num_classes=classes)
+    meta = write_l0(a.out_dir, indptr, indices, features=feats, labels=labels, partition=part, num_classes=classes,
+                    feature_dtype=a.feature_dtype)
     print("wrote %s: %s" % (a.out_dir, meta))
 
 

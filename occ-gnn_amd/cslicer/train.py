@@ -30,14 +30,25 @@ class Trainer(object):
 
     def __init__(self, indptr, indices, features, labels, n_classes, rank=0, world=1, fanouts=(15, 10, 5),
                  batch=1024, streams=8, hidden=256, lr=1e-3, device=0, dist=None, seed=0, overlap=False,
-                 model="sage", heads=8, rank_path=None, workload=None, feat_dim=None, rng_seed=5489):
+                 model="sage", heads=8, rank_path=None, workload=None, feat_dim=None, rng_seed=5489,
+                 feature_dtype="float32"):
         """Part `rank` of `world`.  Ownership = the engine's workload table (`workload` int32 [N], the METIS map of
         python/utils/sampler.py:64-134 / partition_map_opt.bin; None = v % world like pyfrontend.cpp:57): the rank
         keeps the feature and label rows of the nodes it owns, in ascending node order.
 
         features / labels: either host arrays over ALL nodes (float32 [N, F], int64 [N]; the rank copies its own
         rows) or callables `f(own_ids) -> rows` so that a rank never holds more than its share (papers100M:
-        57 GB of features over 8 ranks); with a callable `features`, pass `feat_dim`."""
+        57 GB of features over 8 ranks); with a callable `features`, pass `feat_dim`.
+
+        feature_dtype: "float32" (default), "float16" or "bfloat16": the element type of the resident feature table
+        `self.feat`.  The rows (float32 or float16 numpy arrays, torch tensors of any of the three types) are stored as
+        torch.as_tensor(rows).to(dtype), round to nearest even; a 16-bit table is half the HBM, no float32 copy of it
+        stays on the device, and the deepest layer's forward reads it in place and upcasts in registers (exact), so the
+        model is bitwise the one trained on the stored table upcast to float32.  A 16-bit table whose width
+        is no multiple of 4 is stored with zero-padded rows; `self.feat` is then the [n_own, F] view of it."""
+        if feature_dtype not in aggr.FEATURE_DTYPES:
+            raise ValueError("feature_dtype must be one of %s, not %r" % (", ".join(aggr.FEATURE_DTYPES), feature_dtype))
+        fdt = aggr.FEATURE_DTYPES[feature_dtype]
         self.rank, self.world, self.dist = rank, world, dist
         self.P = world
         self.dev = torch.device("cuda", device)
@@ -67,7 +78,9 @@ class Trainer(object):
             # GAT aggregates PROJECTED features: every layer's sources take a gradient -- the deepest layer's too, unless
             # it runs aggregate-then-project on the raw feature rows (aggr.GatInputLayer: no source gradient at all)
             F_in = features.shape[1] if feat_dim is None and not callable(features) else feat_dim
+            # (the input layer's kernels read float32 rows: a 16-bit table takes the project-then-aggregate path)
             self.gat_input = (not splitgnn._NO_GAT_INPUT and not splitgnn._NO_LOCAL_FUSE and F_in is not None
+                              and fdt == torch.float32
                               and aggr.gat_input_ok(heads, F_in, fanouts[-1],
                                                     hidden if len(fanouts) > 1 else (n_classes + 3) // 4 * 4))
             eng_flags = _abi.FLAG_TRANSPOSE | (0 if self.gat_input else _abi.FLAG_TRANSPOSE_ALL)
@@ -83,13 +96,30 @@ class Trainer(object):
         # the rank's nodes (ascending) and the owner table (None: v % P), which rank-path evaluation needs
         self.own, self.owner = own, workload
         take = (lambda a: a(own)) if callable(features) else (lambda a: a[own] if self.P > 1 else a)
-        f_own = np.ascontiguousarray(take(features), dtype=np.float32)
+        f_own = take(features)
+        if not torch.is_tensor(f_own):
+            f_own = np.asarray(f_own)
+            # (host arrays: float32 or float16 as they come, anything else through float32 as before)
+            f_own = torch.from_numpy(np.ascontiguousarray(
+                f_own, dtype=None if f_own.dtype in (np.float32, np.float16) else np.float32))
+        if f_own.dtype not in (torch.float32, torch.float16, torch.bfloat16) or f_own.dim() != 2:
+            raise ValueError("features: a float32, float16 or bfloat16 matrix expected")
+        # converted on the HOST (round to nearest even), so that the device only ever holds the table in its stored type
+        f_own = f_own.to(fdt).contiguous()
         l_own = np.ascontiguousarray((labels(own) if callable(labels) else (labels[own] if self.P > 1 else labels)),
                                      dtype=np.int64)
         if f_own.shape[0] != self.n_own or l_own.shape[0] != self.n_own:
             raise ValueError("features / labels do not cover the rank's %d nodes" % self.n_own)
         F = f_own.shape[1] if feat_dim is None else feat_dim
-        self.feat = torch.from_numpy(f_own).to(self.dev)
+        if fdt != torch.float32 and f_own.shape[1] % 4:
+            # the readers of a 16-bit table load whole quads of a row (8 bytes): a width that is no multiple of 4 is stored
+            # with its rows padded to one (zeros), self.feat being the [n_own, F] view of it
+            wide = torch.zeros((self.n_own, (f_own.shape[1] + 3) // 4 * 4), dtype=fdt)
+            wide[:, :f_own.shape[1]] = f_own
+            self.feat = wide.to(self.dev)[:, :f_own.shape[1]]
+            del wide
+        else:
+            self.feat = f_own.to(self.dev)
         self.labels = torch.from_numpy(l_own).to(self.dev)
         del f_own, l_own
         # global node id -> local row of the owner (-1 elsewhere); a single part holds every node at its own id
@@ -333,7 +363,8 @@ class Trainer(object):
           gemm          flops of the library GEMMs: forward (k >= 1, or every layer when the deepest is not fused),
                         weight gradient (every layer), input gradient (k >= 1), 2 m 2in out each
           fused_forward the deepest layer as one kernel: 2 m 2in out flops; HBM bytes: (m + e) in 4 of gathered
-                        feature-table rows + m out 4 of result + m 2in 4 of operand kept for the weight gradient
+                        feature-table rows (in 2 on a 16-bit table: the table's element size, here and in the two-kernel
+                        form below) + m out 4 of result + m 2in 4 of operand kept for the weight gradient
           aggregation   HBM bytes of the gather kernels, every row counted ONCE (the per-edge re-reads of a layer's
                         sources are served by L2: the whole source matrix is a few tens of MB):
                         forward k >= 1: src in 4 read + m 2in 4 written; backward k >= 1 (by source): m 2in 4 read
@@ -341,6 +372,7 @@ class Trainer(object):
         The returned dict also has the totals `gemm_flops` (fused forward included) and `aggregation_bytes`."""
         fused = self.fused_deepest_layer()
         w = {"gemm": {"flops": 0.0}, "fused_forward": {"flops": 0.0, "bytes": 0.0}, "aggregation": {"bytes": 0.0}}
+        esz = self.feat.element_size()
         for k, (u, conv) in enumerate(zip(self.units, self.model.convs)):
             if not hasattr(conv, "fc"):
                 return None
@@ -354,10 +386,10 @@ class Trainer(object):
                 w["aggregation"]["bytes"] += (src * fin + m * fin2) * 4 + (m * fin2 + 2 * src * fin) * 4
             elif fused:
                 w["fused_forward"]["flops"] += g
-                w["fused_forward"]["bytes"] += (m + e) * fin * 4 + m * fout * 4 + m * fin2 * 4
+                w["fused_forward"]["bytes"] += (m + e) * fin * esz + m * fout * 4 + m * fin2 * 4
             else:
                 w["gemm"]["flops"] += g
-                w["aggregation"]["bytes"] += (m + e) * fin * 4 + m * fin2 * 4
+                w["aggregation"]["bytes"] += (m + e) * fin * esz + m * fin2 * 4
         w["gemm_flops"] = w["gemm"]["flops"] + w["fused_forward"]["flops"]
         w["aggregation_bytes"] = w["aggregation"]["bytes"] + w["fused_forward"]["bytes"]
         return w
@@ -522,6 +554,10 @@ def _parser():
     ap.add_argument("--eval-split", choices=("none", "file", "holdout"), default="none",
                     help="(extra) node split for evaluation: none, the L0 directory's train_idx.bin / val_idx.bin, or a "
                          "seeded 80/20 holdout")
+    ap.add_argument("--feature-dtype", choices=tuple(aggr.FEATURE_DTYPES), default=None,
+                    help="(extra) element type of the feature table resident in HBM (default: float32, or what an L0 "
+                         "directory's meta.txt says); a 16-bit table is half the memory and trains bitwise the model of "
+                         "the same table upcast to float32")
     return ap
 
 
@@ -557,7 +593,13 @@ def main(argv=None):
     --eval-split (extra): `none` (default) trains on every node and never evaluates; `file` trains on the L0 directory's
     train_idx.bin and evaluates val_idx.bin; `holdout` trains on a seeded 80 % of the nodes and evaluates the other
     20 %.  With a split the model is evaluated by full-neighbour inference every --eval-every epochs and after the last
-    one; with one process per part every rank takes part (each holds only its own rows) and rank 0 prints `Eval Acc`."""
+    one; with one process per part every rank takes part (each holds only its own rows) and rank 0 prints `Eval Acc`.
+    --feature-dtype (extra): float32, float16 or bfloat16, the element type of the feature table kept in HBM
+    (`Trainer(feature_dtype=...)`).  Default: float32, or with an L0 directory what its meta.txt records
+    (feature_dtype=, cslicer.l0.write_l0); features.bin is memory-mapped in its stored type and, where the two differ,
+    the rank's rows are converted on load.
+
+        python -m cslicer.train --graph <L0 dir> --feature-dtype bfloat16 --eval-split holdout"""
     import os
     a = _parser().parse_args(argv)
     from . import l0
@@ -572,6 +614,7 @@ def main(argv=None):
         torch.cuda.set_device(local)
         dist.init_process_group(backend=os.environ.get("CSLICER_DIST_BACKEND", "nccl"))
     workload, fdim = None, None
+    fdtype = a.feature_dtype or "float32"
     if a.graph == "synthetic" or a.graph in l0.PRESETS:
         n, d, fdim, n_classes = (200_000, 20.0, 128, 40) if a.graph == "synthetic" else l0.PRESETS[a.graph]
         indptr, indices = l0.synth_graph(n, d, seed=0)
@@ -584,9 +627,13 @@ def main(argv=None):
         indptr, indices, meta = l0.read_l0(a.graph, mmap=False)
         n, fdim = meta["num_nodes"], meta["feature_dim"]
         # memory-mapped: a rank touches only the rows it owns
-        fmap = np.memmap(os.path.join(a.graph, "features.bin"), dtype=np.float32, mode="r", shape=(n, fdim))
+        fmap, stored = l0.read_features(a.graph, meta)          # (in the stored element type)
         lmap = np.memmap(os.path.join(a.graph, "labels.bin"), dtype=np.int32, mode="r", shape=(n,))
-        feats = lambda own: np.asarray(fmap[own])                                            # noqa: E731
+        if stored == "bfloat16":    # (numpy has no bfloat16: the rank's words become a torch.bfloat16 tensor)
+            feats = lambda own: torch.from_numpy(np.asarray(fmap[own]).view(np.int16)).view(torch.bfloat16)   # noqa: E731
+        else:
+            feats = lambda own: np.asarray(fmap[own])                                        # noqa: E731
+        fdtype = a.feature_dtype or stored
         labels = lambda own: np.asarray(lmap[own]).astype(np.int64)                          # noqa: E731
         n_classes = meta["num_classes"]
         if a.partition == "file":
@@ -599,7 +646,9 @@ def main(argv=None):
     hidden = a.num_hidden // a.num_heads if kind == "gat" else a.num_hidden
     tr = Trainer(indptr, indices, feats, labels, n_classes, rank=rank, world=world, fanouts=fan, batch=a.batch_size,
                  streams=8, hidden=max(4, hidden // 4 * 4), lr=a.lr, device=local, dist=dist, model=kind, heads=a.num_heads,
-                 workload=workload, feat_dim=fdim)
+                 workload=workload, feat_dim=fdim, feature_dtype=fdtype)
+    if rank == 0 and fdtype != "float32":
+        print("feature table: %s, %d bytes on this rank" % (fdtype, tr.feat.numel() * tr.feat.element_size()))
     n = indptr.shape[0] - 1
     for epoch in range(a.num_epochs):
         if train_nodes is None:

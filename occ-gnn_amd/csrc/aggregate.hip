@@ -14,8 +14,12 @@
 #include <cstdint>
 #include <cstdlib>
 
+#include <type_traits>
+
 #include "cslicer_aggr.h"
+#include "cslicer_feat16.h"
 #include "cslicer_hip.h"
+#include "feat_elem.h"
 
 namespace {
 
@@ -46,12 +50,23 @@ __device__ __forceinline__ void add4(float4& a, const float4 b) {
   a.w += b.w;
 }
 
-// G lanes per row (power of two, <= 64); quads beyond G*4 columns are looped
-template <int G>
+// a quad of a source row: of a float32 matrix as before (whole quads when vec_ok, else element-wise at the row's tail),
+// of a 16-bit feature table (cslicer_feat16.h: rows of whole quads, 8-byte aligned) one 8-byte load upcast in registers
+template <typename E>
+__device__ __forceinline__ float4 ldq(const E* p, int c, int H, int vec_ok) {
+  if constexpr (std::is_same<E, float>::value) {
+    return vec_ok ? *reinterpret_cast<const float4*>(p + c) : ld4(p, c, H);
+  } else {
+    return feat::Elem<E>::up(feat::Elem<E>::ld(p + c));
+  }
+}
+
+// G lanes per row (power of two, <= 64); quads beyond G*4 columns are looped.  E: the element type of x
+template <int G, typename E = float>
 __global__ __launch_bounds__(BLK) void k_spmm_sum(const int* __restrict__ indptr,
                                                   const int* __restrict__ indices,
                                                   const int* __restrict__ rows, long long n_rows,
-                                                  const float* __restrict__ x, long long ldx, float* __restrict__ out,
+                                                  const E* __restrict__ x, long long ldx, float* __restrict__ out,
                                                   long long ldo, int H, int vec_ok, int compact,
                                                   const int* __restrict__ rowmap) {
   // rowmap: x is a resident table read through it (x row of source s = rowmap[s]): the deepest layer of a rank reads its
@@ -71,7 +86,12 @@ __global__ __launch_bounds__(BLK) void k_spmm_sum(const int* __restrict__ indptr
       long long s0 = indices[e], s1 = indices[e + 1], s2 = indices[e + 2], s3 = indices[e + 3];
       if (rowmap) s0 = rowmap[s0], s1 = rowmap[s1], s2 = rowmap[s2], s3 = rowmap[s3];
       float4 v0, v1, v2, v3;
-      if (vec_ok) {
+      if constexpr (!std::is_same<E, float>::value) {
+        v0 = ldq(x + s0 * ldx, c, H, 1);
+        v1 = ldq(x + s1 * ldx, c, H, 1);
+        v2 = ldq(x + s2 * ldx, c, H, 1);
+        v3 = ldq(x + s3 * ldx, c, H, 1);
+      } else if (vec_ok) {
         v0 = *reinterpret_cast<const float4*>(x + s0 * ldx + c);
         v1 = *reinterpret_cast<const float4*>(x + s1 * ldx + c);
         v2 = *reinterpret_cast<const float4*>(x + s2 * ldx + c);
@@ -91,7 +111,7 @@ __global__ __launch_bounds__(BLK) void k_spmm_sum(const int* __restrict__ indptr
     for (; e < e1; e++) {
       long long s0 = indices[e];
       if (rowmap) s0 = rowmap[s0];
-      add4(acc, vec_ok ? *reinterpret_cast<const float4*>(x + s0 * ldx + c) : ld4(x + s0 * ldx, c, H));
+      add4(acc, ldq(x + s0 * ldx, c, H, vec_ok));
     }
     if (vec_ok) {
       *reinterpret_cast<float4*>(out + orow * ldo + c) = acc;
@@ -121,8 +141,8 @@ __global__ __launch_bounds__(BLK) void k_spmm_sum_bwd(const int* __restrict__ in
   }
 }
 
-template <int G>
-__global__ __launch_bounds__(BLK) void k_gather_rows(const float* __restrict__ src, long long lds,
+template <int G, typename E = float>
+__global__ __launch_bounds__(BLK) void k_gather_rows(const E* __restrict__ src, long long lds,
                                                      const int* __restrict__ idx, long long n,
                                                      float* __restrict__ dst, long long ldd, int H, int vec_ok) {
   constexpr int RPB = BLK / G;
@@ -132,7 +152,7 @@ __global__ __launch_bounds__(BLK) void k_gather_rows(const float* __restrict__ s
   const long long s = idx[k];
   for (int c = lane * 4; c < H; c += G * 4) {
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (s >= 0) v = vec_ok ? *reinterpret_cast<const float4*>(src + s * lds + c) : ld4(src + s * lds, c, H);
+    if (s >= 0) v = ldq(src + s * lds, c, H, vec_ok);
     if (vec_ok) {
       *reinterpret_cast<float4*>(dst + k * ldd + c) = v;
     } else {
@@ -543,11 +563,11 @@ __global__ __launch_bounds__(BLK) void k_gat_logits_bwd_dst(const float* __restr
 // map(i) = rowmap ? rowmap[i] : i  (the deepest layer reads the resident feature table through the slice's
 // in_nodes, so the gathered input matrix is never materialised); act = ReLU when relu_in (the previous
 // layer's pre-activation output is consumed directly: no separate activation pass).  Rows [n, n_pad) are zeroed.
-template <int G>
+template <int G, typename E = float>
 __global__ __launch_bounds__(BLK) void k_sage_cat(const int* __restrict__ indptr, const int* __restrict__ indices,
                                                   const int* __restrict__ self_ids, const int* __restrict__ owned,
                                                   const int* __restrict__ deg, const int* __restrict__ rowmap,
-                                                  const float* __restrict__ x, long long ldx,
+                                                  const E* __restrict__ x, long long ldx,
                                                   const float* __restrict__ agg, long long lda, long long n,
                                                   long long n_pad, float* __restrict__ cat, long long ldc, int H,
                                                   int relu_in) {
@@ -573,7 +593,7 @@ __global__ __launch_bounds__(BLK) void k_sage_cat(const int* __restrict__ indptr
   for (int c = lane * 4; c < H; c += G * 4) {
     float4 sv = make_float4(0.f, 0.f, 0.f, 0.f);
     if (srow >= 0) {
-      sv = *reinterpret_cast<const float4*>(x + srow * ldx + c);
+      sv = ldq(x + srow * ldx, c, H, 1);
       sv.x = fmaxf(sv.x, lo), sv.y = fmaxf(sv.y, lo), sv.z = fmaxf(sv.z, lo), sv.w = fmaxf(sv.w, lo);
     }
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -582,10 +602,10 @@ __global__ __launch_bounds__(BLK) void k_sage_cat(const int* __restrict__ indptr
       for (; e + 4 <= e1; e += 4) {  // four source rows in flight per lane, fixed summation order
         long long s0 = indices[e], s1 = indices[e + 1], s2 = indices[e + 2], s3 = indices[e + 3];
         if (rowmap) s0 = rowmap[s0], s1 = rowmap[s1], s2 = rowmap[s2], s3 = rowmap[s3];
-        float4 v0 = *reinterpret_cast<const float4*>(x + s0 * ldx + c);
-        float4 v1 = *reinterpret_cast<const float4*>(x + s1 * ldx + c);
-        float4 v2 = *reinterpret_cast<const float4*>(x + s2 * ldx + c);
-        float4 v3 = *reinterpret_cast<const float4*>(x + s3 * ldx + c);
+        float4 v0 = ldq(x + s0 * ldx, c, H, 1);
+        float4 v1 = ldq(x + s1 * ldx, c, H, 1);
+        float4 v2 = ldq(x + s2 * ldx, c, H, 1);
+        float4 v3 = ldq(x + s3 * ldx, c, H, 1);
         acc.x += fmaxf(v0.x, lo), acc.y += fmaxf(v0.y, lo), acc.z += fmaxf(v0.z, lo), acc.w += fmaxf(v0.w, lo);
         acc.x += fmaxf(v1.x, lo), acc.y += fmaxf(v1.y, lo), acc.z += fmaxf(v1.z, lo), acc.w += fmaxf(v1.w, lo);
         acc.x += fmaxf(v2.x, lo), acc.y += fmaxf(v2.y, lo), acc.z += fmaxf(v2.z, lo), acc.w += fmaxf(v2.w, lo);
@@ -594,7 +614,7 @@ __global__ __launch_bounds__(BLK) void k_sage_cat(const int* __restrict__ indptr
       for (; e < e1; e++) {
         long long s0 = indices[e];
         if (rowmap) s0 = rowmap[s0];
-        const float4 v0 = *reinterpret_cast<const float4*>(x + s0 * ldx + c);
+        const float4 v0 = ldq(x + s0 * ldx, c, H, 1);
         acc.x += fmaxf(v0.x, lo), acc.y += fmaxf(v0.y, lo), acc.z += fmaxf(v0.z, lo), acc.w += fmaxf(v0.w, lo);
       }
     } else {
@@ -1276,6 +1296,26 @@ int vec_ok(const void* a, long long lda, const void* b, long long ldb, int H) {
     default: hipLaunchKernelGGL(KERNEL<64>, dim3((unsigned)(((grid_rows) + BLK / 64 - 1) / (BLK / 64))), dim3(BLK), 0, st, __VA_ARGS__); break; \
   }
 
+// the same with a 16-bit table: KERNEL<G, E> for E = feat::f16 or feat::bf16 (`kind` checked by the caller)
+#define DISPATCH_G_E(G, E, KERNEL, grid_rows, ...)                                                                        \
+  switch (G) {                                                                                                            \
+    case 1: hipLaunchKernelGGL((KERNEL<1, E>), dim3((unsigned)(((grid_rows) + BLK - 1) / BLK)), dim3(BLK), 0, st, __VA_ARGS__); break; \
+    case 2: hipLaunchKernelGGL((KERNEL<2, E>), dim3((unsigned)(((grid_rows) + BLK / 2 - 1) / (BLK / 2))), dim3(BLK), 0, st, __VA_ARGS__); break; \
+    case 4: hipLaunchKernelGGL((KERNEL<4, E>), dim3((unsigned)(((grid_rows) + BLK / 4 - 1) / (BLK / 4))), dim3(BLK), 0, st, __VA_ARGS__); break; \
+    case 8: hipLaunchKernelGGL((KERNEL<8, E>), dim3((unsigned)(((grid_rows) + BLK / 8 - 1) / (BLK / 8))), dim3(BLK), 0, st, __VA_ARGS__); break; \
+    case 16: hipLaunchKernelGGL((KERNEL<16, E>), dim3((unsigned)(((grid_rows) + BLK / 16 - 1) / (BLK / 16))), dim3(BLK), 0, st, __VA_ARGS__); break; \
+    case 32: hipLaunchKernelGGL((KERNEL<32, E>), dim3((unsigned)(((grid_rows) + BLK / 32 - 1) / (BLK / 32))), dim3(BLK), 0, st, __VA_ARGS__); break; \
+    default: hipLaunchKernelGGL((KERNEL<64, E>), dim3((unsigned)(((grid_rows) + BLK / 64 - 1) / (BLK / 64))), dim3(BLK), 0, st, __VA_ARGS__); break; \
+  }
+#define DISPATCH_G_KIND(G, kind, KERNEL, grid_rows, XPTR, ...)                                          \
+  if ((kind) == CSL_FEAT_F16) {                                                                        \
+    const feat::f16* XPTR##_e = static_cast<const feat::f16*>(XPTR);                                   \
+    DISPATCH_G_E(G, feat::f16, KERNEL, grid_rows, __VA_ARGS__)                                         \
+  } else {                                                                                             \
+    const feat::bf16* XPTR##_e = static_cast<const feat::bf16*>(XPTR);                                 \
+    DISPATCH_G_E(G, feat::bf16, KERNEL, grid_rows, __VA_ARGS__)                                        \
+  }
+
 int done() { return hipGetLastError() == hipSuccess ? CSL_OK : CSL_E_HIP; }
 
 }  // namespace
@@ -1297,6 +1337,20 @@ static int spmm_sum_impl(const int32_t* indptr, const int32_t* indices, const in
 int csl_spmm_sum_map_f32(const int32_t* indptr, const int32_t* indices, const int32_t* rows, int64_t n_rows, const float* x,
                          int64_t ldx, const int32_t* rowmap, float* out, int64_t ldo, int32_t H, int32_t compact, void* stream) {
   return spmm_sum_impl(indptr, indices, rows, n_rows, x, ldx, out, ldo, H, compact ? 1 : 0, stream, rowmap);
+}
+
+int csl_spmm_sum_map_x16(const int32_t* indptr, const int32_t* indices, const int32_t* rows, int64_t n_rows, const void* x,
+                         int32_t kind, int64_t ldx, const int32_t* rowmap, float* out, int64_t ldo, int32_t H,
+                         int32_t compact, void* stream) {
+  if (!feat::table_ok(x, kind, ldx) || H < 1 || ldx < H) return CSL_E_INVALID;
+  if (n_rows == 0) return CSL_OK;
+  if (n_rows < 0 || !indptr || !out || ldo < H || (compact && !rows)) return CSL_E_INVALID;
+  hipStream_t st = (hipStream_t)stream;
+  // (the destination decides whether whole quads are stored; the table's quads are always whole)
+  const int G = group_for(H), v = vec_ok(out, ldo, out, ldo, H), cp = compact ? 1 : 0;
+  DISPATCH_G_KIND(G, kind, k_spmm_sum, n_rows, x, indptr, indices, rows, (long long)n_rows, x_e, (long long)ldx, out,
+                  (long long)ldo, (int)H, v, cp, rowmap);
+  return done();
 }
 
 int csl_spmm_sum_f32(const int32_t* indptr, const int32_t* indices, const int32_t* rows, int64_t n_rows,
@@ -1442,6 +1496,17 @@ int csl_gather_rows_f32(const float* src, int64_t lds, const int32_t* idx, int64
   return done();
 }
 
+int csl_gather_rows_x16(const void* src, int32_t kind, int64_t lds, const int32_t* idx, int64_t n, float* dst, int64_t ldd,
+                        int32_t H, void* stream) {
+  if (!feat::table_ok(src, kind, lds) || H < 1 || lds < H) return CSL_E_INVALID;
+  if (n == 0) return CSL_OK;
+  if (n < 0 || !idx || !dst || ldd < H) return CSL_E_INVALID;
+  hipStream_t st = (hipStream_t)stream;
+  const int G = group_for(H), v = vec_ok(dst, ldd, dst, ldd, H);
+  DISPATCH_G_KIND(G, kind, k_gather_rows, n, src, src_e, (long long)lds, idx, (long long)n, dst, (long long)ldd, (int)H, v);
+  return done();
+}
+
 int csl_scatter_add_rows_f32(float* dst, int64_t ldd, const int32_t* idx, int64_t n, const float* src, int64_t lds,
                              int32_t H, void* stream) {
   if (n == 0) return CSL_OK;
@@ -1516,6 +1581,25 @@ int csl_sage_cat_f32(const int32_t* indptr, const int32_t* indices, const int32_
   const int G = group_for(H);
   DISPATCH_G(G, k_sage_cat, n_pad, indptr, indices, self_ids, owned, deg, rowmap, x, (long long)ldx, agg, (long long)lda,
              (long long)n, (long long)n_pad, cat, (long long)ldc, (int)H, (int)relu_in);
+  return done();
+}
+
+int csl_sage_cat_x16(const int32_t* indptr, const int32_t* indices, const int32_t* self_ids, const int32_t* owned,
+                     const int32_t* deg, const int32_t* rowmap, const void* x, int32_t kind, int64_t ldx, const float* agg,
+                     int64_t lda, int64_t n, int64_t n_pad, float* cat, int64_t ldc, int32_t H, int32_t relu_in,
+                     void* stream) {
+  if (!feat::table_ok(x, kind, ldx) || ldx < H) return CSL_E_INVALID;
+  if (n_pad == 0) return CSL_OK;
+  if (n < 0 || n_pad < n || H < 4 || H % 4 != 0 || !cat || ldc < 2 * (int64_t)H || ldc % 4 != 0 || !aligned16(cat))
+    return CSL_E_INVALID;
+  if (n > 0) {
+    if (!self_ids) return CSL_E_INVALID;
+    if (!indptr && (!owned || !deg || !agg || lda < H || lda % 4 != 0 || !aligned16(agg))) return CSL_E_INVALID;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int G = group_for(H);
+  DISPATCH_G_KIND(G, kind, k_sage_cat, n_pad, x, indptr, indices, self_ids, owned, deg, rowmap, x_e, (long long)ldx, agg,
+                  (long long)lda, (long long)n, (long long)n_pad, cat, (long long)ldc, (int)H, (int)relu_in);
   return done();
 }
 

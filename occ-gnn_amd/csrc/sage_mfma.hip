@@ -41,7 +41,9 @@
 #include <cstdlib>
 
 #include "cslicer_aggr.h"
+#include "cslicer_feat16.h"
 #include "cslicer_hip.h"
+#include "feat_elem.h"
 
 namespace {
 
@@ -72,12 +74,8 @@ static_assert(3 * EC >= EMAX, "the staged row covers every slot a fast-path pass
 typedef unsigned long long StagedT;          // (64-bit: an address, the row of zeros where there is nothing to fetch)
 // (an address that went through LDS as an integer is loaded from as GLOBAL memory, said explicitly: a generic pointer
 // would make it a flat load, which counts in both wait counters and completes out of order)
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef const f32x4 __attribute__((address_space(1)))* GlobalF4;
-__device__ __forceinline__ float4 ldg4(StagedT addr) {
-  const f32x4 v = *reinterpret_cast<GlobalF4>((uintptr_t)addr);
-  return make_float4(v.x, v.y, v.z, v.w);
-}
+// (feat::Elem<E>::ldg: four elements of the table's type E -- 16 bytes of float32, 8 of float16 / bfloat16)
+using feat::Elem;
 constexpr int NSL = EMAX * BM / PT;         // edge slots of a row per producer thread in the index pipeline (2)
 
 struct FwdArgs {
@@ -85,8 +83,8 @@ struct FwdArgs {
   const int* indices;
   const int* self_ids;
   const int* rowmap;
-  const float* x;
-  long long ldx;
+  const void* x;      // the feature table: float32, or 16-bit elements (the kernel's element type E)
+  long long ldx;      // (in elements)
   const float4* wp;   // packed W: [K2/8][NTp][64 lanes] float4
   const float* zero;  // a row of zeros behind it (as wide as the widest accepted layer): what a lane with nothing to fetch loads
   const float* bias;
@@ -132,10 +130,13 @@ __device__ __forceinline__ void acc4(float4& a, const float4 b) { a.x += b.x, a.
 // ---- producers.  Tile ids of this workgroup: b, b + G, b + 2 G, ... (S of them).  Step t finishes tile t's feature
 // rows (stage F), resolves tile t+2's rows through the row map (R), reads tile t+3's indices (I) and tile t+4's row
 // pointers (P), and stores the result tile t-2 the consumers left in LDS.
+template <typename E>
 struct ProdState {
   int p_e0, p_deg, p_sid;         // stage P -> I: CSR range and self id of this thread's row
   int i_raw[NSL], i_sid, i_deg;   // stage I -> R: this thread's edge slots (raw indices), self id, degree
-  float4 r[2][2 * (EC + 1)];      // stage F in flight (fast path): two chunks of [two rows x (self + EC edges)] quads
+  // stage F in flight (fast path): two chunks of [two rows x (self + EC edges)] quads, AS LOADED: a 16-bit quad is
+  // upcast where it is consumed (an upcast at the issue would wait for the load there, a whole step early)
+  typename Elem<E>::Raw r[2][2 * (EC + 1)];
 };
 
 // the index pipeline: thread j is row pr of the tile, edge slots ps and ps + 8.  Its loads are issued unconditionally,
@@ -145,7 +146,8 @@ struct PipeLoads {
   int m_nbr[NSL], m_self, m_raw[NSL], m_e0, m_e1, m_sid;
   bool okP;
 };
-__device__ __forceinline__ void pipe_issue(const FwdArgs& a, int t, int S, int b, int G, int j, const ProdState& st,
+template <typename E>
+__device__ __forceinline__ void pipe_issue(const FwdArgs& a, int t, int S, int b, int G, int j, const ProdState<E>& st,
                                            PipeLoads& pl) {
   const int pr = j >> 3, ps = j & 7;
 #pragma unroll
@@ -163,21 +165,23 @@ __device__ __forceinline__ void pipe_issue(const FwdArgs& a, int t, int S, int b
 // (row, slot): each of the 32 lanes that later fetch a row adds its column and loads -- one vector instruction per load
 // instead of a 64-bit multiply-add and a select in every lane (the fp32 MFMA and the vector ALU share the SIMD's fp32
 // lanes on this chip: every vector instruction a producer issues is taken from the consumer beside it).
-__device__ __forceinline__ void pipe_finish(const FwdArgs& a, int t, int S, int j, StagedT* Ibuf, ProdState& st,
+template <typename E>
+__device__ __forceinline__ void pipe_finish(const FwdArgs& a, int t, int S, int j, StagedT* Ibuf, ProdState<E>& st,
                                             const PipeLoads& pl) {
   const int pr = j >> 3, ps = j & 7;
   if (t + 2 >= 0 && t + 2 < S) {
     StagedT* Iw = Ibuf + ((t + 6) % 3) * BM * IDXW + pr * IDXW;   // tile t+2's (tile T lives in slot (T + 4) % 3)
     const StagedT zero = (StagedT)(uintptr_t)a.zero;
+    const E* x = static_cast<const E*>(a.x);
 #pragma unroll
     for (int k = 0; k < NSL; k++) {
       const long long row = a.rowmap ? pl.m_nbr[k] : st.i_raw[k];
-      Iw[2 + ps + 8 * k] = st.i_raw[k] >= 0 ? (StagedT)(uintptr_t)(a.x + row * a.ldx) : zero;
+      Iw[2 + ps + 8 * k] = st.i_raw[k] >= 0 ? (StagedT)(uintptr_t)(x + row * a.ldx) : zero;
     }
     if (ps == 0) {
       const long long row = a.rowmap ? pl.m_self : st.i_sid;
       Iw[0] = (StagedT)(unsigned)st.i_deg;
-      Iw[1] = st.i_sid >= 0 ? (StagedT)(uintptr_t)(a.x + row * a.ldx) : zero;
+      Iw[1] = st.i_sid >= 0 ? (StagedT)(uintptr_t)(x + row * a.ldx) : zero;
     }
   }
 #pragma unroll
@@ -192,31 +196,32 @@ __device__ __forceinline__ void pipe_finish(const FwdArgs& a, int t, int S, int 
 // or of the next one, so two chunks of loads are in flight at every moment, barriers included.  No loop with a memory
 // operation in it between the issue and the use of a load: the compiler then waits with counted vmcnt instead of
 // draining the queue.
-template <int EP>
-__device__ __forceinline__ void chunk_issue(const StagedT* I_tile, int g, unsigned cb, int k, float4 (&r)[2 * (EC + 1)]) {
+template <int EP, typename E>
+__device__ __forceinline__ void chunk_issue(const StagedT* I_tile, int g, unsigned cb, int k,
+                                            typename Elem<E>::Raw (&r)[2 * (EC + 1)]) {
   // every load is issued: a slot with nothing to fetch (no self row, a shorter row) holds the address of a row of zeros.
   // No branch around a load (a join the compiler's wait insertion does not count across), no select afterwards.
   const int P = k / EP, p = k % EP;
 #pragma unroll
   for (int w = 0; w < 2; w++) {
     const StagedT* I = I_tile + (g + 16 * P + 8 * w) * IDXW;
-    float4* rr = r + w * (EC + 1);
-    if (p == 0) rr[0] = ldg4(I[1] + cb);
+    typename Elem<E>::Raw* rr = r + w * (EC + 1);
+    if (p == 0) rr[0] = Elem<E>::ldg(I[1] + cb);
 #pragma unroll
-    for (int e = 0; e < EC; e++) rr[1 + e] = ldg4(I[2 + EC * p + e] + cb);
+    for (int e = 0; e < EC; e++) rr[1 + e] = Elem<E>::ldg(I[2 + EC * p + e] + cb);
   }
 }
 
-template <int EP, bool RELU>
+template <int EP, bool RELU, typename E>
 __device__ __forceinline__ void producer_step_fast(const FwdArgs& a, int t, int S, int b, int G, int j, float* Abuf,
-                                                   StagedT* Ibuf, ProdState& st) {
+                                                   StagedT* Ibuf, ProdState<E>& st) {
   const int H = a.H, lda = a.lda;
   const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
   PipeLoads pl;
   pipe_issue(a, t, S, b, G, j, st, pl);
   const bool doF = t >= 0 && t < S, doN = t + 1 >= 0 && t + 1 < S;
   const int g = j >> 5, gl = j & 31, c = gl * 4;
-  const unsigned cb = c < H ? (unsigned)c * 4u : 0u;    // (lanes beyond the row's width fetch its first quad again: same line)
+  const unsigned cb = c < H ? (unsigned)c * Elem<E>::SIZE : 0u;    // (lanes beyond the row's width fetch its first quad again: same line)
   const StagedT* Ib = Ibuf + ((t + 4) % 3) * BM * IDXW;    // tile t's staged rows (initial values before tile 0's are there)
   const StagedT* In = doN ? Ibuf + ((t + 5) % 3) * BM * IDXW : Ib;    // tile t+1's (the last step loads the last tile again)
   float* A = Abuf + (t & 1) * BM * lda;
@@ -225,18 +230,18 @@ __device__ __forceinline__ void producer_step_fast(const FwdArgs& a, int t, int 
 #pragma unroll
   for (int k = 0; k < 2 * EP; k++) {
     const int P = k / EP, p = k % EP;
-    float4(&r)[2 * (EC + 1)] = st.r[k % 2];
+    typename Elem<E>::Raw(&r)[2 * (EC + 1)] = st.r[k % 2];
 #pragma unroll
     for (int w = 0; w < 2; w++) {
       const int rl = g + 16 * P + 8 * w;
-      const float4* rr = r + w * (EC + 1);
+      const typename Elem<E>::Raw* rr = r + w * (EC + 1);
       if (p == 0) {
         m[w] = z4;
-        const float4 s4 = RELU ? relu4(rr[0], 0.f) : rr[0];
+        const float4 s4 = RELU ? relu4(Elem<E>::up(rr[0]), 0.f) : Elem<E>::up(rr[0]);
         if (doF && c < H) *reinterpret_cast<float4*>(A + rl * lda + c) = s4;
       }
 #pragma unroll
-      for (int e = 0; e < EC; e++) acc4(m[w], RELU ? relu4(rr[1 + e], 0.f) : rr[1 + e]);
+      for (int e = 0; e < EC; e++) acc4(m[w], RELU ? relu4(Elem<E>::up(rr[1 + e]), 0.f) : Elem<E>::up(rr[1 + e]));
       if (p == EP - 1) {
         const int deg = (int)Ib[rl * IDXW];
         const float inv = 1.0f / (float)(deg > 1 ? deg : 1);
@@ -246,15 +251,16 @@ __device__ __forceinline__ void producer_step_fast(const FwdArgs& a, int t, int 
       }
     }
     // the set takes the chunk after the next: of this tile, or of the next one
-    if (k + 2 < 2 * EP) chunk_issue<EP>(Ib, g, cb, k + 2, r);
-    else chunk_issue<EP>(In, g, cb, k + 2 - 2 * EP, r);
+    if (k + 2 < 2 * EP) chunk_issue<EP, E>(Ib, g, cb, k + 2, r);
+    else chunk_issue<EP, E>(In, g, cb, k + 2 - 2 * EP, r);
   }
   pipe_finish(a, t, S, j, Ibuf, st, pl);
 }
 
 // ---- the generic path (rows of any length, any width): stage F of tile t is issued and waited for inside step t
+template <typename E>
 __device__ __forceinline__ void producer_step_slow(const FwdArgs& a, int t, int S, int b, int G, int j, float* Abuf,
-                                                   StagedT* Ibuf, ProdState& st) {
+                                                   StagedT* Ibuf, ProdState<E>& st) {
   const int H = a.H, lda = a.lda;
   const float lo = a.relu_in ? 0.f : -__builtin_inff();
   const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -273,7 +279,7 @@ __device__ __forceinline__ void producer_step_slow(const FwdArgs& a, int t, int 
         const int deg = (int)I[0];
         float4 s4 = z4, m = z4;
         if (!(a.dbg & 1)) {
-          s4 = relu4(ldg4(I[1] + 4u * (unsigned)c), lo);   // (the zero row stays zero)
+          s4 = relu4(Elem<E>::up(Elem<E>::ldg(I[1] + Elem<E>::SIZE * (unsigned)c)), lo);   // (the zero row stays zero)
           for (int e = 0; e < deg; e++) {
             StagedT src;
             if (e < EMAX) {
@@ -281,9 +287,9 @@ __device__ __forceinline__ void producer_step_slow(const FwdArgs& a, int t, int 
             } else {
               long long s = a.indices[(long long)a.indptr[row0 + rl] + e];
               if (a.rowmap) s = a.rowmap[s];
-              src = (StagedT)(uintptr_t)(a.x + s * a.ldx);
+              src = (StagedT)(uintptr_t)(static_cast<const E*>(a.x) + s * a.ldx);
             }
-            acc4(m, relu4(ldg4(src + 4u * (unsigned)c), lo));
+            acc4(m, relu4(Elem<E>::up(Elem<E>::ldg(src + Elem<E>::SIZE * (unsigned)c)), lo));
           }
         }
         const float inv = 1.0f / (float)(deg > 1 ? deg : 1);
@@ -296,14 +302,14 @@ __device__ __forceinline__ void producer_step_slow(const FwdArgs& a, int t, int 
   pipe_finish(a, t, S, j, Ibuf, st, pl);
 }
 
-template <int MODE, bool RELU>   // 1, 2, 3: fast path with that many edge passes; 0: generic
+template <int MODE, bool RELU, typename E>   // 1, 2, 3: fast path with that many edge passes; 0: generic
 __device__ __forceinline__ void producer_loop(const FwdArgs& a, int S, int b, int G, int j, float* Abuf, StagedT* Ibuf,
-                                              ProdState& st) {
+                                              ProdState<E>& st) {
   // (no global store anywhere in a producer, diagnostics included: with stores and loads both pending in the queue the
   // compiler stops counting and waits with vmcnt(0), which would drain the next tile's loads at every use of this one's)
   for (int t = -4; t <= S + 1; t++) {
     if (MODE == 0) producer_step_slow(a, t, S, b, G, j, Abuf, Ibuf, st);
-    else producer_step_fast<(MODE > 0 ? MODE : 1), RELU>(a, t, S, b, G, j, Abuf, Ibuf, st);
+    else producer_step_fast<(MODE > 0 ? MODE : 1), RELU, E>(a, t, S, b, G, j, Abuf, Ibuf, st);
     __syncthreads();
   }
 }
@@ -472,8 +478,10 @@ __device__ __forceinline__ void store_operand(const FwdArgs& a, int t, int tile,
   }
 }
 
-// KS k-groups of W stationary in the consumers' registers, the next KL in LDS; STREAM: the layer has more, streamed from L2
-template <int KS, int KL, bool STREAM>
+// KS k-groups of W stationary in the consumers' registers, the next KL in LDS; STREAM: the layer has more, streamed from L2.
+// E: the element type of the feature table (float, feat::f16, feat::bf16): only the producers' feature loads, their
+// address stride and the upcast where a quad is consumed depend on it
+template <int KS, int KL, bool STREAM, typename E>
 __global__ __launch_bounds__(TBP) void k_sage_fwd_mfma(const FwdArgs a) {
   extern __shared__ float4 smem4[];
   float* Abuf = reinterpret_cast<float*>(smem4);               // [2][BM][lda]
@@ -502,23 +510,23 @@ __global__ __launch_bounds__(TBP) void k_sage_fwd_mfma(const FwdArgs a) {
     const int j = tid - 64 * NCONS;
     const int md = s_maxdeg;
     if (a.dbg & 2048) __builtin_amdgcn_s_setprio(3);
-    ProdState st;
+    ProdState<E> st;
     st.p_e0 = 0, st.p_deg = 0, st.p_sid = -1, st.i_sid = -1, st.i_deg = 0;
 #pragma unroll
     for (int k = 0; k < NSL; k++) st.i_raw[k] = -1;
 #pragma unroll
     for (int k = 0; k < 2; k++)
 #pragma unroll
-      for (int e = 0; e < 2 * (EC + 1); e++) st.r[k][e] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (a.H > 128 || md > 3 * EC || md > EMAX || (a.dbg & 4096)) producer_loop<0, false>(a, S, b, G, j, Abuf, Ibuf, st);
+      for (int e = 0; e < 2 * (EC + 1); e++) st.r[k][e] = Elem<E>::zero();
+    if (a.H > 128 || md > 3 * EC || md > EMAX || (a.dbg & 4096)) producer_loop<0, false, E>(a, S, b, G, j, Abuf, Ibuf, st);
     else if (a.relu_in) {
-      if (md <= EC) producer_loop<1, true>(a, S, b, G, j, Abuf, Ibuf, st);
-      else if (md <= 2 * EC) producer_loop<2, true>(a, S, b, G, j, Abuf, Ibuf, st);
-      else producer_loop<3, true>(a, S, b, G, j, Abuf, Ibuf, st);
+      if (md <= EC) producer_loop<1, true, E>(a, S, b, G, j, Abuf, Ibuf, st);
+      else if (md <= 2 * EC) producer_loop<2, true, E>(a, S, b, G, j, Abuf, Ibuf, st);
+      else producer_loop<3, true, E>(a, S, b, G, j, Abuf, Ibuf, st);
     } else {
-      if (md <= EC) producer_loop<1, false>(a, S, b, G, j, Abuf, Ibuf, st);
-      else if (md <= 2 * EC) producer_loop<2, false>(a, S, b, G, j, Abuf, Ibuf, st);
-      else producer_loop<3, false>(a, S, b, G, j, Abuf, Ibuf, st);
+      if (md <= EC) producer_loop<1, false, E>(a, S, b, G, j, Abuf, Ibuf, st);
+      else if (md <= 2 * EC) producer_loop<2, false, E>(a, S, b, G, j, Abuf, Ibuf, st);
+      else producer_loop<3, false, E>(a, S, b, G, j, Abuf, Ibuf, st);
     }
   } else {
     if (!(a.dbg & 1024)) __builtin_amdgcn_s_setprio(2);
@@ -571,45 +579,27 @@ inline void split_for(int KQ, int& KS, int& KL) {
   KL = (KQ == 24 || KQ == 25) ? 6 : 0;
 }
 
-template <int KS, int KL, bool STREAM>
+template <int KS, int KL, bool STREAM, typename E>
 int launch(const FwdArgs& a, unsigned grid, size_t lds, hipStream_t st) {
   static size_t attr_lds = 48 * 1024;   // (more dynamic LDS than the default limit must be asked for, once per size)
   if (lds > attr_lds) {
-    if (hipFuncSetAttribute((const void*)k_sage_fwd_mfma<KS, KL, STREAM>, hipFuncAttributeMaxDynamicSharedMemorySize,
+    if (hipFuncSetAttribute((const void*)k_sage_fwd_mfma<KS, KL, STREAM, E>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)lds) != hipSuccess)
       return CSL_E_HIP;
     attr_lds = lds;
   }
-  hipLaunchKernelGGL((k_sage_fwd_mfma<KS, KL, STREAM>), dim3(grid), dim3(TBP), lds, st, a);
+  hipLaunchKernelGGL((k_sage_fwd_mfma<KS, KL, STREAM, E>), dim3(grid), dim3(TBP), lds, st, a);
   return hipGetLastError() == hipSuccess ? CSL_OK : CSL_E_HIP;
 }
 
-}  // namespace
-
-extern "C" {
-
-int64_t csl_sage_fwd_mfma_scratch(int32_t H, int32_t out) {
-  int KS, KL;
-  split_for(2 * H / 8, KS, KL);
-  if (H < 4 || H % 4 != 0 || out < 1 || out > 256 || lds_for(H, out, KL) > 160 * 1024 - 64) return CSL_E_INVALID;
-  return (int64_t)(2 * H / 8) * ntp_for(out) * 64 * 4 + 4 * ZROW4;   // packed W + a zero row
-}
-
-int csl_sage_fwd_mfma_f32(const int32_t* indptr, const int32_t* indices, const int32_t* self_ids, const int32_t* rowmap,
-                          const float* x, int64_t ldx, const float* W, int64_t ldw, const float* bias, int64_t n,
-                          int64_t n_pad, int32_t H, int32_t out, int32_t relu_in, int32_t relu_out, float* cat,
-                          int64_t ldc, float* y, int64_t ldy, float* wpack, void* stream) {
-  if (n_pad == 0) return CSL_OK;
-  if (n < 0 || n_pad < n || H < 4 || H % 4 != 0 || out < 1 || out > 256 || !W || ldw < 2 * (int64_t)H || ldw % 4 != 0 ||
-      !y || ldy < out || !wpack || ((uintptr_t)W & 15) || ((uintptr_t)wpack & 15))
-    return CSL_E_INVALID;
-  if (n > 0 && (!indptr || !self_ids || !x || ldx < H || ldx % 4 != 0 || ((uintptr_t)x & 15))) return CSL_E_INVALID;
-  if (cat && (ldc < 2 * (int64_t)H || ldc % 4 != 0 || ((uintptr_t)cat & 15))) return CSL_E_INVALID;
+// the layer behind csl_sage_fwd_mfma_f32 (E = float) and csl_sage_fwd_mfma_x16: arguments checked by the caller
+template <typename E>
+int fwd_mfma(const int32_t* indptr, const int32_t* indices, const int32_t* self_ids, const int32_t* rowmap, const void* x,
+             int64_t ldx, const float* W, int64_t ldw, const float* bias, int64_t n, int64_t n_pad, int32_t H, int32_t out,
+             int32_t relu_in, int32_t relu_out, float* cat, int64_t ldc, float* y, int64_t ldy, float* wpack, void* stream) {
   int KS, KL;
   split_for(2 * H / 8, KS, KL);
   const size_t lds = lds_for(H, out, KL);
-  if (lds > 160 * 1024 - 64) return CSL_E_INVALID;
-  if ((n_pad + BM - 1) / BM > 0x7fffffffLL / BM) return CSL_E_INVALID;
   int dbg = 0;
   {
     const char* e = getenv("CSLICER_MFMA_DBG");
@@ -645,11 +635,63 @@ int csl_sage_fwd_mfma_f32(const int32_t* indptr, const int32_t* indices, const i
   }
   a.dbg = dbg;
   const unsigned grid = (unsigned)(a.n_tiles < n_cu ? a.n_tiles : n_cu);
-  if (KQ == 25) return launch<19, 6, false>(a, grid, lds, st);
-  if (KQ == 24) return launch<18, 6, false>(a, grid, lds, st);
-  if (KQ == 16) return launch<16, 0, false>(a, grid, lds, st);
-  if (KQ > 16) return launch<16, 0, true>(a, grid, lds, st);
-  return launch<0, 0, true>(a, grid, lds, st);
+  if (KQ == 25) return launch<19, 6, false, E>(a, grid, lds, st);
+  if (KQ == 24) return launch<18, 6, false, E>(a, grid, lds, st);
+  if (KQ == 16) return launch<16, 0, false, E>(a, grid, lds, st);
+  if (KQ > 16) return launch<16, 0, true, E>(a, grid, lds, st);
+  return launch<0, 0, true, E>(a, grid, lds, st);
+}
+
+// what csl_sage_fwd_mfma_f32 and its 16-bit twin refuse alike (everything but the table itself); no HIP call
+inline bool fwd_mfma_shape_ok(int64_t n, int64_t n_pad, int32_t H, int32_t out, const float* W, int64_t ldw, const float* y,
+                              int64_t ldy, const float* wpack, const float* cat, int64_t ldc) {
+  if (n < 0 || n_pad < n || H < 4 || H % 4 != 0 || out < 1 || out > 256 || !W || ldw < 2 * (int64_t)H || ldw % 4 != 0 ||
+      !y || ldy < out || !wpack || ((uintptr_t)W & 15) || ((uintptr_t)wpack & 15))
+    return false;
+  if (cat && (ldc < 2 * (int64_t)H || ldc % 4 != 0 || ((uintptr_t)cat & 15))) return false;
+  int KS, KL;
+  split_for(2 * H / 8, KS, KL);
+  if (lds_for(H, out, KL) > 160 * 1024 - 64) return false;
+  if ((n_pad + BM - 1) / BM > 0x7fffffffLL / BM) return false;
+  return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t csl_sage_fwd_mfma_scratch(int32_t H, int32_t out) {
+  int KS, KL;
+  split_for(2 * H / 8, KS, KL);
+  if (H < 4 || H % 4 != 0 || out < 1 || out > 256 || lds_for(H, out, KL) > 160 * 1024 - 64) return CSL_E_INVALID;
+  return (int64_t)(2 * H / 8) * ntp_for(out) * 64 * 4 + 4 * ZROW4;   // packed W + a zero row
+}
+
+int csl_sage_fwd_mfma_f32(const int32_t* indptr, const int32_t* indices, const int32_t* self_ids, const int32_t* rowmap,
+                          const float* x, int64_t ldx, const float* W, int64_t ldw, const float* bias, int64_t n,
+                          int64_t n_pad, int32_t H, int32_t out, int32_t relu_in, int32_t relu_out, float* cat,
+                          int64_t ldc, float* y, int64_t ldy, float* wpack, void* stream) {
+  if (n_pad == 0) return CSL_OK;
+  if (!fwd_mfma_shape_ok(n, n_pad, H, out, W, ldw, y, ldy, wpack, cat, ldc)) return CSL_E_INVALID;
+  if (n > 0 && (!indptr || !self_ids || !x || ldx < H || ldx % 4 != 0 || ((uintptr_t)x & 15))) return CSL_E_INVALID;
+  return fwd_mfma<float>(indptr, indices, self_ids, rowmap, x, ldx, W, ldw, bias, n, n_pad, H, out, relu_in, relu_out, cat,
+                         ldc, y, ldy, wpack, stream);
+}
+
+int csl_sage_fwd_mfma_x16(const int32_t* indptr, const int32_t* indices, const int32_t* self_ids, const int32_t* rowmap,
+                          const void* x, int32_t kind, int64_t ldx, const float* W, int64_t ldw, const float* bias,
+                          int64_t n, int64_t n_pad, int32_t H, int32_t out, int32_t relu_in, int32_t relu_out, float* cat,
+                          int64_t ldc, float* y, int64_t ldy, float* wpack, void* stream) {
+  // (the table is checked first, and whatever n is: a lane's 8-byte load needs an 8-byte aligned base and rows of whole quads)
+  if (!feat::table_ok(x, kind, ldx) || ldx < H) return CSL_E_INVALID;
+  if (n_pad == 0) return CSL_OK;
+  if (!fwd_mfma_shape_ok(n, n_pad, H, out, W, ldw, y, ldy, wpack, cat, ldc)) return CSL_E_INVALID;
+  if (n > 0 && (!indptr || !self_ids)) return CSL_E_INVALID;
+  if (kind == CSL_FEAT_F16)
+    return fwd_mfma<feat::f16>(indptr, indices, self_ids, rowmap, x, ldx, W, ldw, bias, n, n_pad, H, out, relu_in, relu_out,
+                               cat, ldc, y, ldy, wpack, stream);
+  return fwd_mfma<feat::bf16>(indptr, indices, self_ids, rowmap, x, ldx, W, ldw, bias, n, n_pad, H, out, relu_in, relu_out,
+                              cat, ldc, y, ldy, wpack, stream);
 }
 
 }  // extern "C"

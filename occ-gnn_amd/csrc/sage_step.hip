@@ -26,7 +26,9 @@
 #include <vector>
 
 #include "cslicer_aggr.h"
+#include "cslicer_feat16.h"
 #include "cslicer_hip.h"
+#include "feat_elem.h"
 
 namespace {
 
@@ -164,6 +166,38 @@ struct SpanGuard {   // records e0 now and e1 when it goes out of scope
     }                                                                        \
   } while (0)
 
+// ---- the resident feature table: float32 (kind 0: csl_sage_fwd_bwd_f32, csl_sage_rank_fwd_bwd_f32) or 16-bit elements
+// (CSL_FEAT_F16 / CSL_FEAT_BF16: the _x16 twins, cslicer_feat16.h).  Only the deepest layer's forward reads it; each of
+// its three readers has both forms, and everything downstream of them is fp32 either way.
+inline int feat_fwd_mfma(int32_t kind, const int32_t* indptr, const int32_t* indices, const int32_t* self_ids,
+                         const int32_t* rowmap, const void* x, int64_t ldx, const float* W, int64_t ldw, const float* bias,
+                         int64_t n, int64_t n_pad, int32_t H, int32_t out, int32_t relu_in, int32_t relu_out, float* cat,
+                         int64_t ldc, float* y, int64_t ldy, float* wpack, void* stream) {
+  if (kind == 0)
+    return csl_sage_fwd_mfma_f32(indptr, indices, self_ids, rowmap, static_cast<const float*>(x), ldx, W, ldw, bias, n, n_pad,
+                                 H, out, relu_in, relu_out, cat, ldc, y, ldy, wpack, stream);
+  return csl_sage_fwd_mfma_x16(indptr, indices, self_ids, rowmap, x, kind, ldx, W, ldw, bias, n, n_pad, H, out, relu_in,
+                               relu_out, cat, ldc, y, ldy, wpack, stream);
+}
+inline int feat_sage_cat(int32_t kind, const int32_t* indptr, const int32_t* indices, const int32_t* self_ids,
+                         const int32_t* owned, const int32_t* deg, const int32_t* rowmap, const void* x, int64_t ldx,
+                         const float* agg, int64_t lda, int64_t n, int64_t n_pad, float* cat, int64_t ldc, int32_t H,
+                         int32_t relu_in, void* stream) {
+  if (kind == 0)
+    return csl_sage_cat_f32(indptr, indices, self_ids, owned, deg, rowmap, static_cast<const float*>(x), ldx, agg, lda, n,
+                            n_pad, cat, ldc, H, relu_in, stream);
+  return csl_sage_cat_x16(indptr, indices, self_ids, owned, deg, rowmap, x, kind, ldx, agg, lda, n, n_pad, cat, ldc, H,
+                          relu_in, stream);
+}
+inline int feat_spmm_sum_map(int32_t kind, const int32_t* indptr, const int32_t* indices, const int32_t* rows,
+                             int64_t n_rows, const void* x, int64_t ldx, const int32_t* rowmap, float* out, int64_t ldo,
+                             int32_t H, int32_t compact, void* stream) {
+  if (kind == 0)
+    return csl_spmm_sum_map_f32(indptr, indices, rows, n_rows, static_cast<const float*>(x), ldx, rowmap, out, ldo, H,
+                                compact, stream);
+  return csl_spmm_sum_map_x16(indptr, indices, rows, n_rows, x, kind, ldx, rowmap, out, ldo, H, compact, stream);
+}
+
 }  // namespace
 
 extern "C" {
@@ -198,10 +232,11 @@ int64_t csl_sage_fwd_bwd_workspace(int32_t n_layers, const int32_t* dims, const 
   return o.total;
 }
 
-int csl_sage_fwd_bwd_f32(int32_t n_layers, const int32_t* dims, const csl_sage_slice* sl, const float* const* weights,
-                         const float* const* biases, const float* feat, int64_t ldf, const int32_t* feat_rows,
-                         const int32_t* seed_ids, const int64_t* labels, float scale, int64_t row_pad, int32_t n_slabs,
-                         float* grads, float* loss, float* workspace, int64_t workspace_floats, void* stream) {
+// the step behind csl_sage_fwd_bwd_f32 (kind 0) and csl_sage_fwd_bwd_x16
+static int sage_fwd_bwd(int32_t n_layers, const int32_t* dims, const csl_sage_slice* sl, const float* const* weights,
+                        const float* const* biases, const void* feat, int32_t kind, int64_t ldf, const int32_t* feat_rows,
+                        const int32_t* seed_ids, const int64_t* labels, float scale, int64_t row_pad, int32_t n_slabs,
+                        float* grads, float* loss, float* workspace, int64_t workspace_floats, void* stream) {
   int k = -1;
   s_err[0] = 0;
   Layout o;
@@ -229,16 +264,17 @@ int csl_sage_fwd_bwd_f32(int32_t n_layers, const int32_t* dims, const csl_sage_s
   for (k = 0; k < L; k++) {
     const int32_t in = dims[k], out = dims[k + 1];
     const int64_t m = sl[k].n_out, mp = o.mp[k];
-    const float* x = k == 0 ? feat : ws + o.y[k - 1];
+    const void* x = k == 0 ? feat : ws + o.y[k - 1];
+    const int32_t xk = k == 0 ? kind : 0;   // (only the feature table may be 16-bit)
     if (k == 0 && o.wpack >= 0) {
       // gather [self | mean] into LDS, multiply on the fp32 matrix cores, bias + ReLU on the way out; the operand is
       // also written (the weight gradient reads it), but never read back by the forward
-      TSTEP(CSL_STEP_FUSED_FWD, csl_sage_fwd_mfma_f32(sl[0].indptr, sl[0].indices, sl[0].self_ids_in, feat_rows, feat, ldf, weights[0],
+      TSTEP(CSL_STEP_FUSED_FWD, feat_fwd_mfma(kind, sl[0].indptr, sl[0].indices, sl[0].self_ids_in, feat_rows, feat, ldf, weights[0],
                                  2 * (int64_t)in, biases[0], m, mp, in, out, 0, L > 1 ? 1 : 0, ws + o.cat[0],
                                  2 * (int64_t)in, ws + o.y[0], out, ws + o.wpack, stream));
       continue;
     }
-    TSTEP(CSL_STEP_AGGREGATION, csl_sage_cat_f32(sl[k].indptr, sl[k].indices, sl[k].self_ids_in, nullptr, nullptr, k == 0 ? feat_rows : nullptr, x,
+    TSTEP(CSL_STEP_AGGREGATION, feat_sage_cat(xk, sl[k].indptr, sl[k].indices, sl[k].self_ids_in, nullptr, nullptr, k == 0 ? feat_rows : nullptr, x,
                           k == 0 ? ldf : (int64_t)in, nullptr, 0, m, mp, ws + o.cat[k], 2 * (int64_t)in, in, 0, stream));
     TSTEP(CSL_STEP_GEMM, csl_gemm_f32(0, 1, mp, out, 2 * (int64_t)in, ws + o.cat[k], 2 * (int64_t)in, 0, weights[k], 2 * (int64_t)in, 0,
                       ws + o.y[k], out, 0, 1, biases[k], k + 1 < L ? 1 : 0, stream));
@@ -313,6 +349,27 @@ int csl_sage_fwd_bwd_f32(int32_t n_layers, const int32_t* dims, const csl_sage_s
   k = -1;
   TSTEP(CSL_STEP_OTHER, csl_reduce_multi_f32(nr, r_src, r_nblk, r_h, r_dst, stream));
   return CSL_OK;
+}
+
+int csl_sage_fwd_bwd_f32(int32_t n_layers, const int32_t* dims, const csl_sage_slice* sl, const float* const* weights,
+                         const float* const* biases, const float* feat, int64_t ldf, const int32_t* feat_rows,
+                         const int32_t* seed_ids, const int64_t* labels, float scale, int64_t row_pad, int32_t n_slabs,
+                         float* grads, float* loss, float* workspace, int64_t workspace_floats, void* stream) {
+  return sage_fwd_bwd(n_layers, dims, sl, weights, biases, feat, 0, ldf, feat_rows, seed_ids, labels, scale, row_pad, n_slabs,
+                      grads, loss, workspace, workspace_floats, stream);
+}
+
+int csl_sage_fwd_bwd_x16(int32_t n_layers, const int32_t* dims, const csl_sage_slice* sl, const float* const* weights,
+                         const float* const* biases, const void* feat, int32_t kind, int64_t ldf, const int32_t* feat_rows,
+                         const int32_t* seed_ids, const int64_t* labels, float scale, int64_t row_pad, int32_t n_slabs,
+                         float* grads, float* loss, float* workspace, int64_t workspace_floats, void* stream) {
+  if (!feat::table_ok(feat, kind, ldf)) {
+    snprintf(s_err, sizeof(s_err), "16-bit feature table: kind %d (1 float16, 2 bfloat16), 8-byte aligned base, row stride a "
+             "multiple of 4 elements expected", (int)kind);
+    return CSL_E_INVALID;
+  }
+  return sage_fwd_bwd(n_layers, dims, sl, weights, biases, feat, kind, ldf, feat_rows, seed_ids, labels, scale, row_pad,
+                      n_slabs, grads, loss, workspace, workspace_floats, stream);
 }
 
 }  // extern "C"
@@ -398,12 +455,13 @@ int64_t csl_sage_rank_workspace(int32_t n_layers, const int32_t* dims, const csl
   return o.total;
 }
 
-int csl_sage_rank_fwd_bwd_f32(int32_t n_layers, const int32_t* dims, const csl_sage_rank_slice* sl,
-                              const float* const* weights, const float* const* biases, const float* feat, int64_t ldf,
-                              const int32_t* feat_rows, const int32_t* seed_ids, const int32_t* label_rows,
-                              const int64_t* labels, float scale, int64_t row_pad, int32_t n_slabs,
-                              csl_exchange_fn exchange, csl_exchange_wait_fn wait, void* user, float* grads, float* loss,
-                              float* workspace, int64_t workspace_floats, void* stream) {
+// the rank step behind csl_sage_rank_fwd_bwd_f32 (kind 0) and csl_sage_rank_fwd_bwd_x16
+static int sage_rank_fwd_bwd(int32_t n_layers, const int32_t* dims, const csl_sage_rank_slice* sl,
+                             const float* const* weights, const float* const* biases, const void* feat, int32_t kind,
+                             int64_t ldf, const int32_t* feat_rows, const int32_t* seed_ids, const int32_t* label_rows,
+                             const int64_t* labels, float scale, int64_t row_pad, int32_t n_slabs,
+                             csl_exchange_fn exchange, csl_exchange_wait_fn wait, void* user, float* grads, float* loss,
+                             float* workspace, int64_t workspace_floats, void* stream) {
   int k = -1;
   s_err[0] = 0;
   RankLayout o;
@@ -454,7 +512,8 @@ int csl_sage_rank_fwd_bwd_f32(int32_t n_layers, const int32_t* dims, const csl_s
     const int32_t in = dims[k], out = dims[k + 1];
     const csl_sage_rank_slice& s = sl[k];
     // the deepest layer reads the resident feature rows through feat_rows (no gathered input matrix)
-    const float* x = k == 0 ? feat : ws + o.y[k - 1];
+    const void* x = k == 0 ? feat : ws + o.y[k - 1];
+    const int32_t xk = k == 0 ? kind : 0;   // (only the feature table may be 16-bit)
     const int64_t ldx = k == 0 ? ldf : (int64_t)in;
     const int32_t* map = k == 0 ? feat_rows : nullptr;
     if (k == 0 && o.wpack >= 0) {
@@ -464,18 +523,18 @@ int csl_sage_rank_fwd_bwd_f32(int32_t n_layers, const int32_t* dims, const csl_s
       // too, with the empty buffers (whether a collective is entered depends only on L, which all ranks share)
       XCHG(0, 0, ws + o.send[0], ws + o.recv[0], in);
       XWAIT(0, 0);
-      STEP(csl_sage_fwd_mfma_f32(s.indptr, s.indices, s.self_ids_in, feat_rows, feat, ldf, weights[0], 2 * (int64_t)in,
+      STEP(feat_fwd_mfma(kind, s.indptr, s.indices, s.self_ids_in, feat_rows, feat, ldf, weights[0], 2 * (int64_t)in,
                                  biases[0], s.n_owned, o.mp[0], in, out, 0, L > 1 ? 1 : 0, ws + o.cat[0], 2 * (int64_t)in,
                                  ws + o.y[0], out, ws + o.wpack, stream));
       continue;
     }
     // partial sums of the rows peers own, straight into the send buffer; then the rows this part owns
-    STEP(csl_spmm_sum_map_f32(s.indptr, s.indices, s.from_all, s.n_from, x, ldx, map, ws + o.send[k], in, in, 1, stream));
+    STEP(feat_spmm_sum_map(xk, s.indptr, s.indices, s.from_all, s.n_from, x, ldx, map, ws + o.send[k], in, in, 1, stream));
     XCHG(k, 0, ws + o.send[k], ws + o.recv[k], in);
-    STEP(csl_spmm_sum_map_f32(s.indptr, s.indices, s.owned_out_nodes, s.n_owned, x, ldx, map, ws + o.agg[k], in, in, 0, stream));
+    STEP(feat_spmm_sum_map(xk, s.indptr, s.indices, s.owned_out_nodes, s.n_owned, x, ldx, map, ws + o.agg[k], in, in, 0, stream));
     XWAIT(k, 0);
     STEP(csl_scatter_add_rows_atomic_f32(ws + o.agg[k], in, s.to_all, s.n_to, ws + o.recv[k], in, in, stream));
-    STEP(csl_sage_cat_f32(nullptr, nullptr, s.self_ids_in, s.owned_out_nodes, s.owned_degree, map, x, ldx, ws + o.agg[k],
+    STEP(feat_sage_cat(xk, nullptr, nullptr, s.self_ids_in, s.owned_out_nodes, s.owned_degree, map, x, ldx, ws + o.agg[k],
                           in, s.n_owned, o.mp[k], ws + o.cat[k], 2 * (int64_t)in, in, 0, stream));
     STEP(csl_gemm_f32(0, 1, o.mp[k], out, 2 * (int64_t)in, ws + o.cat[k], 2 * (int64_t)in, 0, weights[k], 2 * (int64_t)in, 0,
                       ws + o.y[k], out, 0, 1, biases[k], k + 1 < L ? 1 : 0, stream));
@@ -565,6 +624,31 @@ int csl_sage_rank_fwd_bwd_f32(int32_t n_layers, const int32_t* dims, const csl_s
 #undef XCHG
 #undef XWAIT
   return CSL_OK;
+}
+
+int csl_sage_rank_fwd_bwd_f32(int32_t n_layers, const int32_t* dims, const csl_sage_rank_slice* sl,
+                              const float* const* weights, const float* const* biases, const float* feat, int64_t ldf,
+                              const int32_t* feat_rows, const int32_t* seed_ids, const int32_t* label_rows,
+                              const int64_t* labels, float scale, int64_t row_pad, int32_t n_slabs,
+                              csl_exchange_fn exchange, csl_exchange_wait_fn wait, void* user, float* grads, float* loss,
+                              float* workspace, int64_t workspace_floats, void* stream) {
+  return sage_rank_fwd_bwd(n_layers, dims, sl, weights, biases, feat, 0, ldf, feat_rows, seed_ids, label_rows, labels, scale,
+                           row_pad, n_slabs, exchange, wait, user, grads, loss, workspace, workspace_floats, stream);
+}
+
+int csl_sage_rank_fwd_bwd_x16(int32_t n_layers, const int32_t* dims, const csl_sage_rank_slice* sl,
+                              const float* const* weights, const float* const* biases, const void* feat, int32_t kind,
+                              int64_t ldf, const int32_t* feat_rows, const int32_t* seed_ids, const int32_t* label_rows,
+                              const int64_t* labels, float scale, int64_t row_pad, int32_t n_slabs,
+                              csl_exchange_fn exchange, csl_exchange_wait_fn wait, void* user, float* grads, float* loss,
+                              float* workspace, int64_t workspace_floats, void* stream) {
+  if (!feat::table_ok(feat, kind, ldf)) {
+    snprintf(s_err, sizeof(s_err), "16-bit feature table: kind %d (1 float16, 2 bfloat16), 8-byte aligned base, row stride a "
+             "multiple of 4 elements expected", (int)kind);
+    return CSL_E_INVALID;
+  }
+  return sage_rank_fwd_bwd(n_layers, dims, sl, weights, biases, feat, kind, ldf, feat_rows, seed_ids, label_rows, labels,
+                           scale, row_pad, n_slabs, exchange, wait, user, grads, loss, workspace, workspace_floats, stream);
 }
 
 }  // extern "C"
