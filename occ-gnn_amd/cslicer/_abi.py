@@ -5,12 +5,14 @@ loaded this module raises -- there is no CPU fallback.
 """
 import ctypes as C
 import os
+import re
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # CSLICER_LIB: alternative build of the same library (tuning sweeps); default is the in-tree build
 LIB_PATH = os.environ.get("CSLICER_LIB") or os.path.join(os.path.dirname(HERE), "lib", "libcslicer_hip.so")
+INCLUDE_DIR = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include")   # where csrc/Makefile finds the headers
 
 MAX_PARTS = 8
 MAX_LAYERS = 4
@@ -96,6 +98,48 @@ class CslError(RuntimeError):
         self.code = code
 
 
+# the callbacks of the rank step (csl_exchange_fn, csl_exchange_wait_fn of cslicer_aggr.h)
+EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p)
+EXCHANGE_WAIT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p)
+# the headers whose prototypes are taken from their text (cslicer_hip.h keeps its typed pointers, written out in load())
+HEADERS = ("cslicer_aggr.h", "cslicer_feat16.h", "cslicer_infer.h", "cslicer_infer_parts.h")
+BOUND = {}     # header -> the names bind_header bound from it, in header order (filled by load())
+_SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "float": C.c_float}
+_PROTOTYPE = re.compile(r"^((?:const\s+)?\w+\s*\*?)\s*(csl_\w+)\s*\(([^()]*)\)\s*;", re.M)
+
+
+def bind_header(L, header, types=None):
+    """Set argtypes and restype of every `<ret> csl_name(<params>);` that include/<header> (or the path `header`)
+    declares on the library L; returns the names in header order.  Pointers are c_void_p (const char*: c_char_p), the
+    scalars those of _SCALARS, a name in `types` the ctypes type given there; any other type is a ValueError, a
+    function the library does not export an AttributeError."""
+    path = os.path.join(INCLUDE_DIR, header)
+    if not os.path.exists(path):
+        raise ImportError("%s not found: the C ABI is bound from the headers beside the package" % path)
+    src = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
+    src = re.sub(r"//[^\n]*|^[ \t]*#[^\n]*", "", src, flags=re.M)
+
+    def ctype(decl, fn, is_param):
+        decl = decl.strip()
+        if "*" in decl:
+            return C.c_char_p if re.match(r"const\s+char\s*\*\s*\w*$", decl) else C.c_void_p
+        words = decl.split()
+        name = " ".join(words[:-1] if is_param and len(words) > 1 else words)
+        for table in (types or {}, _SCALARS):
+            if name in table:
+                return table[name]
+        raise ValueError("%s: %s: no ctypes type for `%s`" % (header, fn, name))
+
+    names = []
+    for ret, fn, params in _PROTOTYPE.findall(src):
+        restype = ctype(ret, fn, False)
+        argtypes = [] if params.strip() == "void" else [ctype(p, fn, True) for p in params.split(",")]
+        f = getattr(L, fn)
+        f.restype, f.argtypes = restype, argtypes
+        names.append(fn)
+    return names
+
+
 _lib = None
 
 
@@ -143,6 +187,8 @@ def load():
     L.csl_device_bytes.restype = C.c_int64
     if L.csl_abi_version() != ABI_VERSION:
         raise ImportError("libcslicer_hip.so ABI version mismatch")
+    for h in HEADERS:
+        BOUND[h] = bind_header(L, h, {"csl_exchange_fn": EXCHANGE_FN, "csl_exchange_wait_fn": EXCHANGE_WAIT_FN})
     _lib = L
     return L
 

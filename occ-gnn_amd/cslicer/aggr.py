@@ -12,135 +12,17 @@ import torch
 
 from . import _abi, l0
 
-SYMBOLS = ["csl_spmm_sum_f32", "csl_spmm_sum_bwd_f32", "csl_gather_rows_f32",
-           "csl_scatter_add_rows_f32", "csl_div_rows_f32", "csl_gat_fwd_f32", "csl_gat_bwd_f32",
-           "csl_sage_cat_f32", "csl_sage_cat_bwd_f32", "csl_relu_bwd_colsum_f32", "csl_softmax_ce_f32",
-           "csl_relu_bwd_colsum_scratch", "csl_softmax_ce_scratch", "csl_adam_f32",
-           "csl_scatter_add_rows_atomic_f32", "csl_gat_logits_fwd_f32", "csl_gat_logits_bwd_f32",
-           "csl_gat_logits_bwd_scratch", "csl_spmm_sum_compact_f32", "csl_sage_cat_rows_bwd_f32",
-           "csl_sage_cat_bwd_t_f32", "csl_sage_cat_bwd_t_scratch", "csl_gemm_f32", "csl_gemm_last_error",
-           "csl_sum_slabs_f32", "csl_sage_fwd_bwd_f32", "csl_sage_fwd_bwd_workspace", "csl_sage_last_error",
-           "csl_gemm_save_plans", "csl_gemm_load_plans", "csl_softmax_ce_partial_f32", "csl_reduce_multi_f32",
-           "csl_sage_rank_fwd_bwd_f32", "csl_sage_rank_workspace", "csl_gat_logits_bwd_acc_f32", "csl_gat_finish_fwd_f32", "csl_gat_finish_bwd_f32", "csl_gat_finish_bwd_scratch",
-           "csl_gat_bwd_t_f32", "csl_sage_fwd_mfma_f32", "csl_sage_fwd_mfma_scratch", "csl_sage_step_timing",
-           "csl_sage_step_timing_read", "csl_sage_cat_bwd_t_hub_f32", "csl_sage_cat_bwd_t_hub_scratch",
-           "csl_gat_bwd_t_fused_f32", "csl_gat_bwd_t_fused_scratch", "csl_sage_rank_g2_f32", "csl_scatter_rows_f32", "csl_spmm_sum_map_f32",
-           "csl_gat_in_max_degree", "csl_gat_in_fwd_f32", "csl_gat_in_bwd_scratch", "csl_gat_in_bwd_f32", "csl_bias_elu_f32",
-           "csl_elu_bwd_colsum_scratch", "csl_elu_bwd_colsum_f32", "csl_gat_in_proj_ok", "csl_gat_in_proj_fpad",
-           "csl_gat_in_proj_f32", "csl_gat_in_proj_bwd_scratch", "csl_gat_in_proj_bwd_f32", "csl_gat_in_layer_fwd_scratch",
-           "csl_gat_in_layer_fwd_f32", "csl_gat_in_layer_bwd_scratch", "csl_gat_in_layer_bwd_f32"]
-# every symbol include/cslicer_feat16.h declares (checked by tests/test_feat16_cpu.py): the readers of a 16-bit table
-FEAT16_SYMBOLS = ["csl_sage_fwd_mfma_x16", "csl_sage_cat_x16", "csl_spmm_sum_map_x16", "csl_gather_rows_x16",
-                  "csl_sage_fwd_bwd_x16", "csl_sage_rank_fwd_bwd_x16"]
+# every entry point include/cslicer_aggr.h and include/cslicer_feat16.h (the readers of a 16-bit table) declare: their
+# prototypes are bound from the headers' text when the library is loaded (_abi.bind_header)
+_abi.load()
+SYMBOLS, FEAT16_SYMBOLS = _abi.BOUND["cslicer_aggr.h"], _abi.BOUND["cslicer_feat16.h"]
+EXCHANGE_FN, EXCHANGE_WAIT_FN = _abi.EXCHANGE_FN, _abi.EXCHANGE_WAIT_FN
 # element kinds of a 16-bit feature table (CSL_FEAT_F16 / CSL_FEAT_BF16); a float32 table has the fp32 entry points
 FEAT_KINDS = {torch.float16: 1, torch.bfloat16: 2}
 # the names a feature table's element type goes by (cslicer.l0.FEATURE_DTYPES: the one list) -> torch dtypes
 FEATURE_DTYPES = {name: getattr(torch, name) for name in l0.FEATURE_DTYPES}
-_ready = False
 _GAT_TORCH_MM = bool(os.environ.get("CSLICER_GAT_TORCH_MM"))
-
-
-def _lib():
-    global _ready
-    L = _abi.load()
-    if not _ready:
-        vp, i64, i32 = C.c_void_p, C.c_int64, C.c_int32
-        L.csl_spmm_sum_f32.argtypes = [vp, vp, vp, i64, vp, i64, vp, i64, i32, vp]
-        L.csl_spmm_sum_bwd_f32.argtypes = [vp, vp, vp, i64, vp, i64, i32, vp, i64, i32, vp]
-        L.csl_spmm_sum_compact_f32.argtypes = [vp, vp, vp, i64, vp, i64, vp, i64, i32, vp]
-        L.csl_sage_cat_rows_bwd_f32.argtypes = [vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, i32, vp]
-        L.csl_gather_rows_f32.argtypes = [vp, i64, vp, i64, vp, i64, i32, vp]
-        L.csl_scatter_add_rows_f32.argtypes = [vp, i64, vp, i64, vp, i64, i32, vp]
-        L.csl_div_rows_f32.argtypes = [vp, i64, vp, i64, i32, vp]
-        L.csl_scatter_add_rows_atomic_f32.argtypes = [vp, i64, vp, i64, vp, i64, i32, vp]
-        L.csl_gat_logits_fwd_f32.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp, vp]
-        L.csl_gat_logits_bwd_f32.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, vp]
-        L.csl_gat_logits_bwd_scratch.argtypes = [i64, i32, i32]
-        L.csl_gat_logits_bwd_scratch.restype = i64
-        f32 = C.c_float
-        L.csl_gat_fwd_f32.argtypes = [vp, vp, i64, vp, vp, vp, i32, i32, f32, vp, vp, vp, vp]
-        L.csl_gat_bwd_f32.argtypes = [vp, vp, i64, vp, vp, vp, i32, i32, f32, vp, vp, vp, vp, vp, vp, vp]
-        L.csl_sage_cat_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, i64, i64, vp, i64, i32, i32, vp]
-        L.csl_sage_cat_bwd_f32.argtypes = [vp, vp, vp, i64, vp, i64, vp, i64, i64, i32, vp]
-        L.csl_relu_bwd_colsum_f32.argtypes = [vp, i64, vp, i64, i64, i64, vp, i64, vp, vp, i32, vp]
-        L.csl_relu_bwd_colsum_scratch.argtypes = [i64, i32]
-        L.csl_relu_bwd_colsum_scratch.restype = i64
-        L.csl_softmax_ce_f32.argtypes = [vp, i64, i64, i32, vp, vp, vp, f32, vp, vp, i64, vp, vp]
-        L.csl_softmax_ce_scratch.argtypes = [i64]
-        L.csl_softmax_ce_scratch.restype = i64
-        L.csl_softmax_ce_partial_f32.argtypes = [vp, i64, i64, i64, i32, vp, vp, vp, f32, vp, i64, vp, vp, vp]
-        L.csl_reduce_multi_f32.argtypes = [i32, vp, vp, vp, vp, vp]
-        L.csl_adam_f32.argtypes = [i32, vp, vp, vp, vp, vp, f32, f32, f32, f32, i64, vp]
-        L.csl_sage_cat_bwd_t_f32.argtypes = [vp, vp, vp, vp, i64, vp, i64, i64, i64, vp, i64, vp, vp, i32, vp]
-        L.csl_sage_cat_bwd_t_scratch.argtypes = [i64, i32]
-        L.csl_sage_cat_bwd_t_scratch.restype = i64
-        L.csl_sage_cat_bwd_t_hub_f32.argtypes = [vp, vp, i64, vp, vp, i64, vp, i64, i64, i64, vp, i64, vp, vp, i32, vp]
-        L.csl_sage_cat_bwd_t_hub_scratch.argtypes = [i64, i32]
-        L.csl_sage_cat_bwd_t_hub_scratch.restype = i64
-        L.csl_gemm_f32.argtypes = [i32, i32, i64, i64, i64, vp, i64, i64, vp, i64, i64, vp, i64, i64, i32, vp, i32, vp]
-        L.csl_gemm_last_error.restype = C.c_char_p
-        L.csl_sum_slabs_f32.argtypes = [vp, i64, i32, vp, vp]
-        L.csl_sage_fwd_bwd_workspace.argtypes = [i32, vp, vp, i64, i32]
-        L.csl_sage_fwd_bwd_workspace.restype = i64
-        L.csl_sage_fwd_bwd_f32.argtypes = [i32, vp, vp, vp, vp, vp, i64, vp, vp, vp, f32, i64, i32, vp, vp, vp, i64, vp]
-        L.csl_sage_last_error.restype = C.c_char_p
-        L.csl_gemm_save_plans.argtypes = [C.c_char_p]
-        L.csl_sage_rank_workspace.argtypes = [i32, vp, vp, i64, i32]
-        L.csl_sage_rank_workspace.restype = i64
-        L.csl_sage_rank_fwd_bwd_f32.argtypes = [i32, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, f32, i64, i32, EXCHANGE_FN,
-                                                EXCHANGE_WAIT_FN, vp, vp, vp, vp, i64, vp]
-        L.csl_gat_logits_bwd_acc_f32.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, vp, i32, vp, vp, vp, vp]
-        L.csl_gat_bwd_t_f32.argtypes = [vp, vp, i64, i64, vp, vp, vp, i32, i32, f32, vp, vp, vp, vp, vp, vp, vp]
-        L.csl_gat_bwd_t_fused_f32.argtypes = [vp, vp, i64, i64, vp, vp, vp, i32, i32, f32, vp, vp, vp, vp, vp, vp, i64, vp, vp,
-                                              vp, vp, vp, vp]
-        L.csl_sage_rank_g2_f32.argtypes = [vp, vp, i64, vp, i64, vp, i64, i32, vp]
-        L.csl_scatter_rows_f32.argtypes = [vp, i64, vp, i64, vp, i64, i32, vp]
-        L.csl_spmm_sum_map_f32.argtypes = [vp, vp, vp, i64, vp, i64, vp, vp, i64, i32, i32, vp]
-        L.csl_gat_bwd_t_fused_scratch.argtypes = [i64, i64, i32, i32]
-        L.csl_gat_bwd_t_fused_scratch.restype = i64
-        L.csl_gat_finish_fwd_f32.argtypes = [vp, vp, vp, i64, i32, i32, i32, vp, vp]
-        L.csl_gat_finish_bwd_f32.argtypes = [vp, i64, vp, vp, vp, i64, i32, i32, i32, vp, vp, vp, vp, vp]
-        L.csl_gat_finish_bwd_scratch.argtypes = [i64, i32, i32]
-        L.csl_gat_finish_bwd_scratch.restype = i64
-        L.csl_gemm_load_plans.argtypes = [C.c_char_p]
-        L.csl_sage_step_timing.argtypes = [i32]
-        L.csl_sage_step_timing_read.argtypes = [vp, vp]
-        L.csl_sage_fwd_mfma_scratch.argtypes = [i32, i32]
-        L.csl_sage_fwd_mfma_scratch.restype = i64
-        L.csl_sage_fwd_mfma_f32.argtypes = [vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, i64, i32, i32, i32, i32, vp, i64,
-                                            vp, i64, vp, vp]
-        L.csl_gat_in_fwd_f32.argtypes = [vp, vp, vp, vp, vp, i64, i32, vp, vp, i32, f32, i64, i64, i32, vp, vp, vp]
-        L.csl_gat_in_bwd_scratch.argtypes = [i64, i32, i32]
-        L.csl_gat_in_bwd_scratch.restype = i64
-        L.csl_gat_in_bwd_f32.argtypes = [vp, vp, vp, vp, vp, i64, i32, vp, vp, i64, i64, i32, f32, i64, i64, i32, vp, vp, vp, vp]
-        L.csl_bias_elu_f32.argtypes = [vp, i64, vp, i64, i32, i32, vp]
-        L.csl_elu_bwd_colsum_scratch.argtypes = [i64, i32]
-        L.csl_elu_bwd_colsum_scratch.restype = i64
-        L.csl_elu_bwd_colsum_f32.argtypes = [vp, i64, vp, i64, i64, i32, i32, vp, i64, vp, vp, vp]
-        L.csl_gat_in_proj_ok.argtypes = [i32, i32, i32]
-        L.csl_gat_in_proj_fpad.argtypes = [i32]
-        L.csl_gat_in_proj_f32.argtypes = [vp, vp, vp, i64, i32, i32, i32, i32, vp, i64, vp]
-        L.csl_gat_in_proj_bwd_scratch.argtypes = [i32, i32, i32]
-        L.csl_gat_in_proj_bwd_scratch.restype = i64
-        L.csl_gat_in_proj_bwd_f32.argtypes = [vp, i64, vp, vp, i64, i32, i32, i32, vp, vp, vp, vp]
-        L.csl_gat_in_layer_fwd_scratch.argtypes = [i32, i32]
-        L.csl_gat_in_layer_fwd_scratch.restype = i64
-        L.csl_gat_in_layer_fwd_f32.argtypes = [vp, vp, vp, vp, vp, i64, i32, vp, vp, vp, vp, i32, i32, f32, i32, i64, i64, i32,
-                                               vp, vp, vp, i64, vp, vp]
-        L.csl_gat_in_layer_bwd_scratch.argtypes = [i64, i32, i32, i32]
-        L.csl_gat_in_layer_bwd_scratch.restype = i64
-        L.csl_gat_in_layer_bwd_f32.argtypes = [vp, vp, vp, vp, vp, i64, i32, vp, vp, vp, i32, i32, f32, i32, i64, i64, i32,
-                                               vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]
-        L.csl_sage_fwd_mfma_x16.argtypes = [vp, vp, vp, vp, vp, i32, i64, vp, i64, vp, i64, i64, i32, i32, i32, i32, vp, i64,
-                                            vp, i64, vp, vp]
-        L.csl_sage_cat_x16.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i64, vp, i64, i64, i64, vp, i64, i32, i32, vp]
-        L.csl_spmm_sum_map_x16.argtypes = [vp, vp, vp, i64, vp, i32, i64, vp, vp, i64, i32, i32, vp]
-        L.csl_gather_rows_x16.argtypes = [vp, i32, i64, vp, i64, vp, i64, i32, vp]
-        L.csl_sage_fwd_bwd_x16.argtypes = [i32, vp, vp, vp, vp, vp, i32, i64, vp, vp, vp, f32, i64, i32, vp, vp, vp, i64, vp]
-        L.csl_sage_rank_fwd_bwd_x16.argtypes = [i32, vp, vp, vp, vp, vp, i32, i64, vp, vp, vp, vp, f32, i64, i32, EXCHANGE_FN,
-                                                EXCHANGE_WAIT_FN, vp, vp, vp, vp, i64, vp]
-        _ready = True
-    return L
+_lib = _abi.load      # (every prototype is bound there; the tests and profiles/ reach the library by this name)
 
 
 def _p(t):
@@ -178,6 +60,20 @@ def _table(x):
     if x.dtype not in FEAT_KINDS:
         raise TypeError("a feature table is float32, float16 or bfloat16, not %s" % x.dtype)
     return FEAT_KINDS[x.dtype]
+
+
+def _twins(stem):
+    """(csl_<stem>_f32, csl_<stem>_x16): a reader of a feature table and its twin for a 16-bit table"""
+    L = _lib()
+    return getattr(L, "csl_%s_f32" % stem), getattr(L, "csl_%s_x16" % stem)
+
+
+def _table_call(twins, kind, upto_table, rest, chk=_chk):
+    """Call a reader of a feature table (_twins) whose arguments are (*upto_table, *rest), the table's pointer the last
+    of upto_table: the fp32 entry point for kind None, else the _x16 twin, which takes `kind` directly after that
+    pointer (cslicer_feat16.h).  The return code goes to chk with the name of what was called."""
+    fn = twins[kind is not None]
+    chk(fn(*upto_table, *rest) if kind is None else fn(*upto_table, kind, *rest), fn.__name__)
 
 
 def _i32(x):
@@ -249,12 +145,8 @@ def gather_rows(src, idx, out=None):
         dst = out
         if dst.shape != (idx.numel(), src.shape[1]) or dst.stride(-1) != 1 or dst.dtype != torch.float32:
             raise ValueError("out must be float32 [len(idx), H] with unit column stride")
-    if kind is not None:
-        _chk(_lib().csl_gather_rows_x16(_p(src), kind, src.stride(0), _p(idx), idx.numel(), _p(dst), dst.stride(0),
-                                        src.shape[1], _stream()), "csl_gather_rows_x16")
-        return dst
-    _chk(_lib().csl_gather_rows_f32(_p(src), src.stride(0), _p(idx), idx.numel(), _p(dst), dst.stride(0),
-                                    src.shape[1], _stream()), "csl_gather_rows_f32")
+    _table_call(_twins("gather_rows"), kind, (_p(src),),
+                (src.stride(0), _p(idx), idx.numel(), _p(dst), dst.stride(0), src.shape[1], _stream()))
     return dst
 
 
@@ -298,19 +190,14 @@ def sage_cat(x, self_ids, n, n_pad, indptr=None, indices=None, owned=None, deg=N
     cat = torch.empty((n_pad, 2 * H), dtype=torch.float32, device=x.device)
     nul = C.c_void_p(0)
     if indptr is not None:
-        args = (_p(_i32(indptr)), _p(_i32(indices)), _p(_i32(self_ids)), nul, _p(deg) if deg is not None else nul,
-                _p(rowmap) if rowmap is not None else nul, _p(x), x.stride(0), nul, 0)
+        head = (_p(_i32(indptr)), _p(_i32(indices)), _p(_i32(self_ids)), nul, _p(deg) if deg is not None else nul)
+        merged = (nul, 0)
     else:
         agg = _f32(agg)
-        args = (nul, nul, _p(_i32(self_ids)), _p(_i32(owned)), _p(_i32(deg)),
-                _p(rowmap) if rowmap is not None else nul, _p(x), x.stride(0), _p(agg), agg.stride(0))
-    if kind is not None:
-        # (the table's kind follows its pointer: args = (..., rowmap, x, ldx, agg, lda))
-        _chk(_lib().csl_sage_cat_x16(*args[:7], kind, *args[7:], n, n_pad, _p(cat), cat.stride(0), H, 1 if relu_in else 0,
-                                     _stream()), "csl_sage_cat_x16")
-        return cat
-    _chk(_lib().csl_sage_cat_f32(*args, n, n_pad, _p(cat), cat.stride(0), H, 1 if relu_in else 0, _stream()),
-         "csl_sage_cat_f32")
+        head = (nul, nul, _p(_i32(self_ids)), _p(_i32(owned)), _p(_i32(deg)))
+        merged = (_p(agg), agg.stride(0))
+    _table_call(_twins("sage_cat"), kind, (*head, _p(rowmap) if rowmap is not None else nul, _p(x)),
+                (x.stride(0), *merged, n, n_pad, _p(cat), cat.stride(0), H, 1 if relu_in else 0, _stream()))
     return cat
 
 
@@ -330,10 +217,7 @@ def spmm_sum_map(indptr, indices, x, rows, rowmap=None, compact=False, n_out=Non
     head = (_p(_i32(indptr)), _p(_i32(indices)), _p(rows), rows.numel(), _p(x))
     tail = (x.stride(0), _p(_i32(rowmap)) if rowmap is not None else nul, _p(out), out.stride(0), H, 1 if compact else 0,
             _stream())
-    if kind is not None:
-        _chk(_lib().csl_spmm_sum_map_x16(*head, kind, *tail), "csl_spmm_sum_map_x16")
-    else:
-        _chk(_lib().csl_spmm_sum_map_f32(*head, *tail), "csl_spmm_sum_map_f32")
+    _table_call(_twins("spmm_sum_map"), kind, head, tail)
     return out
 
 
@@ -358,10 +242,7 @@ def sage_fwd_mfma(x, self_ids, indptr, indices, weight, bias, n, n_pad, rowmap=N
     tail = (x.stride(0), _p(weight), weight.stride(0), _p(_f32(bias)) if bias is not None else nul, n, n_pad, H, out,
             1 if relu_in else 0, 1 if relu_out else 0, _p(cat) if want_cat else nul, cat.stride(0) if want_cat else 0,
             _p(y), y.stride(0), _p(wpack), _stream())
-    if kind is not None:
-        _chk(L.csl_sage_fwd_mfma_x16(*head, kind, *tail), "csl_sage_fwd_mfma_x16")
-    else:
-        _chk(L.csl_sage_fwd_mfma_f32(*head, *tail), "csl_sage_fwd_mfma_f32")
+    _table_call(_twins("sage_fwd_mfma"), kind, head, tail)
     return (y, cat) if want_cat else y
 
 
@@ -497,11 +378,10 @@ def step_timing_read():
     return {g: (float(ms[i]), int(n[i])) for i, g in enumerate(STEP_GROUPS)}
 
 
-class SageStep(object):
-    """Forward + cross-entropy + backward of a DistSAGEModel on one part as ONE native call per minibatch
-    (csl_sage_fwd_bwd_f32): the gradients of W_0, b_0, W_1, ... land back to back in `self.grads` (what
-    aggr.Adam.step(flat_grads=...) takes), the loss in the slot the caller names.  The parameters are used in place
-    (their storage must not move: an optimizer that updates in place, as aggr.Adam does)."""
+class _SageNative(object):
+    """What the two native GraphSAGE steps share: the model's layers as pointer tables, the flat gradient buffer, the
+    workspace and the error report.  A step names its entry points (_stem: csl_<stem>_f32 and its _x16 twin;
+    _workspace) and its slice record (_slice); they are looked up here, once, not per minibatch."""
 
     def __init__(self, model, row_pad, n_slabs):
         ws, bs = [c.fc.weight for c in model.convs], [c.fc.bias for c in model.convs]
@@ -515,12 +395,35 @@ class SageStep(object):
         self._dims = (C.c_int32 * (self.L + 1))(*self.dims)
         self._w = (C.c_void_p * self.L)(*[w.data_ptr() for w in ws])
         self._b = (C.c_void_p * self.L)(*[b.data_ptr() for b in bs])
-        self._sl = (SageSlice * self.L)()
+        self._sl = (self._slice * self.L)()
         self.row_pad, self.n_slabs = int(row_pad), int(n_slabs)
         n_grad = sum(w.numel() + b.numel() for w, b in zip(ws, bs))
         self.grads = torch.empty((n_grad,), dtype=torch.float32, device=ws[0].device)
         self._ws = None
+        self._twins, self._need = _twins(self._stem), getattr(_lib(), self._workspace)
         gemm_load_plans()
+
+    def _grow(self, device):
+        """self._ws: at least the floats the slices in self._sl need"""
+        need = self._need(self.L, self._dims, self._sl, self.row_pad, self.n_slabs)
+        if need < 0:
+            raise _abi.CslError(need, self._workspace + ": unsupported model or slices")
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty((int(need * 1.25) + 1024,), dtype=torch.float32, device=device)
+
+    def _chk(self, rc, what):
+        if rc < 0:
+            L = _lib()
+            raise _abi.CslError(rc, what + ": " + L.csl_sage_last_error().decode() + " / " +
+                                L.csl_gemm_last_error().decode())
+
+
+class SageStep(_SageNative):
+    """Forward + cross-entropy + backward of a DistSAGEModel on one part as ONE native call per minibatch
+    (csl_sage_fwd_bwd_f32): the gradients of W_0, b_0, W_1, ... land back to back in `self.grads` (what
+    aggr.Adam.step(flat_grads=...) takes), the loss in the slot the caller names.  The parameters are used in place
+    (their storage must not move: an optimizer that updates in place, as aggr.Adam does)."""
+    _stem, _workspace, _slice = "sage_fwd_bwd", "csl_sage_fwd_bwd_workspace", SageSlice
 
     def __call__(self, slices, feat, labels, scale, loss_out):
         """slices: the part's `splitgnn.Slice`s in MODEL order (deepest hop first), from an engine with
@@ -535,24 +438,12 @@ class SageStep(object):
             c.t_indptr, c.t_indices = (s.ptr(A.T_INDPTR), s.ptr(A.T_INDICES)) if k else (None, None)
             c.n_out, c.n_in, c.t_max_len = s.n_out, s.n_in, s.t_max_len
             c.t_entries = s.count(A.T_INDICES) if k else 0
-        L = _lib()
-        need = L.csl_sage_fwd_bwd_workspace(self.L, self._dims, self._sl, self.row_pad, self.n_slabs)
-        if need < 0:
-            raise _abi.CslError(need, "csl_sage_fwd_bwd_workspace: unsupported model or slices")
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty((int(need * 1.25) + 1024,), dtype=torch.float32, device=feat.device)
+        self._grow(feat.device)
         # a 16-bit table (float16 / bfloat16) goes to the step's _x16 twin: only its deepest layer's forward differs
-        kind = _table(feat)
-        tail = (feat.stride(0), slices[0].ptr(A.IN_NODES), slices[-1].ptr(A.OUT_NODES), labels.data_ptr(),
-                float(scale), self.row_pad, self.n_slabs, self.grads.data_ptr(),
-                loss_out.data_ptr(), self._ws.data_ptr(), self._ws.numel(), _stream())
-        if kind is not None:
-            rc = L.csl_sage_fwd_bwd_x16(self.L, self._dims, self._sl, self._w, self._b, feat.data_ptr(), kind, *tail)
-        else:
-            rc = L.csl_sage_fwd_bwd_f32(self.L, self._dims, self._sl, self._w, self._b, feat.data_ptr(), *tail)
-        if rc < 0:
-            raise _abi.CslError(rc, "csl_sage_fwd_bwd_f32: " + L.csl_sage_last_error().decode() + " / " +
-                                L.csl_gemm_last_error().decode())
+        _table_call(self._twins, _table(feat), (self.L, self._dims, self._sl, self._w, self._b, feat.data_ptr()),
+                    (feat.stride(0), slices[0].ptr(A.IN_NODES), slices[-1].ptr(A.OUT_NODES), labels.data_ptr(),
+                     float(scale), self.row_pad, self.n_slabs, self.grads.data_ptr(), loss_out.data_ptr(),
+                     self._ws.data_ptr(), self._ws.numel(), _stream()), self._chk)
 
 
 class SageRankSlice(C.Structure):
@@ -564,38 +455,24 @@ class SageRankSlice(C.Structure):
                 ("t_max_len", C.c_int64), ("t_entries", C.c_int64)]
 
 
-EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p)
-EXCHANGE_WAIT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p)
-
-
-class SageRankStep(object):
+class SageRankStep(_SageNative):
     """One rank's forward + loss + backward of the SPLIT-parallel GraphSAGE step as one native call
     (csl_sage_rank_fwd_bwd_f32); the 2 L - 1 boundary exchanges come back as callbacks and go through `comm`
     (splitgnn.DistComm: all_to_all_single over RCCL, gloo in the tests).  Gradients of this rank's share land in
     `self.grads` (W_0, b_0, ...) for the caller's all-reduce and aggr.Adam.step(flat_grads=...)."""
+    _stem, _workspace, _slice = "sage_rank_fwd_bwd", "csl_sage_rank_workspace", SageRankSlice
 
     def __init__(self, model, row_pad, n_slabs, comm, overlap=False):
-        ws, bs = [c.fc.weight for c in model.convs], [c.fc.bias for c in model.convs]
-        self.L = len(ws)
-        self.dims = [ws[0].shape[1] // 2] + [w.shape[0] for w in ws]
-        self._params = ws + bs
+        _SageNative.__init__(self, model, row_pad, n_slabs)
+        self.comm = comm
         # overlap: every exchange runs on the communicator's side stream while the rows that stay on this GPU are
         # aggregated (dist_sageconv.py:57-64); same numbers, different schedule
         self.overlap = bool(overlap)
         self._done = {}
         self._cb_wait = EXCHANGE_WAIT_FN(self._wait)
-        self._dims = (C.c_int32 * (self.L + 1))(*self.dims)
-        self._w = (C.c_void_p * self.L)(*[w.data_ptr() for w in ws])
-        self._b = (C.c_void_p * self.L)(*[b.data_ptr() for b in bs])
-        self._sl = (SageRankSlice * self.L)()
-        self.row_pad, self.n_slabs, self.comm = int(row_pad), int(n_slabs), comm
-        n_grad = sum(w.numel() + b.numel() for w, b in zip(ws, bs))
-        self.grads = torch.empty((n_grad,), dtype=torch.float32, device=ws[0].device)
-        self._ws = None
         self._cur = None
         self._exc = None
         self._cb = EXCHANGE_FN(self._exchange)     # (kept alive: the native call holds only the raw pointer)
-        gemm_load_plans()
 
     def _view(self, ptr, rows, width):
         off = (int(ptr or 0) - self._ws.data_ptr()) // 4 if rows else 0
@@ -663,29 +540,20 @@ class SageRankStep(object):
                 c.t_max_len, c.t_entries = s.t_max_len, s.count(A.T_INDICES)
             else:
                 c.t_indptr, c.t_indices, c.t_max_len, c.t_entries = None, None, 0, 0
-        L = _lib()
-        need = L.csl_sage_rank_workspace(self.L, self._dims, self._sl, self.row_pad, self.n_slabs)
-        if need < 0:
-            raise _abi.CslError(need, "csl_sage_rank_workspace: unsupported model or slices")
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty((int(need * 1.25) + 1024,), dtype=torch.float32, device=feat.device)
+        self._grow(feat.device)
         self._cur, self._exc = slices, None
-        kind = _table(feat)      # (a 16-bit table: the step's _x16 twin, the same exchanges)
-        tail = (feat.stride(0), _p(feat_rows), _p(seed_ids), _p(label_rows) if label_rows is not None else None,
-                labels.data_ptr(), float(scale), self.row_pad, self.n_slabs, self._cb,
-                self._cb_wait if self.overlap else EXCHANGE_WAIT_FN(0), None,
-                self.grads.data_ptr(), loss_out.data_ptr(), self._ws.data_ptr(),
-                self._ws.numel(), _stream())
-        if kind is not None:
-            rc = L.csl_sage_rank_fwd_bwd_x16(self.L, self._dims, self._sl, self._w, self._b, feat.data_ptr(), kind, *tail)
-        else:
-            rc = L.csl_sage_rank_fwd_bwd_f32(self.L, self._dims, self._sl, self._w, self._b, feat.data_ptr(), *tail)
+        # (a 16-bit table: the step's _x16 twin, the same exchanges)
+        _table_call(self._twins, _table(feat), (self.L, self._dims, self._sl, self._w, self._b, feat.data_ptr()),
+                    (feat.stride(0), _p(feat_rows), _p(seed_ids), _p(label_rows) if label_rows is not None else None,
+                     labels.data_ptr(), float(scale), self.row_pad, self.n_slabs, self._cb,
+                     self._cb_wait if self.overlap else EXCHANGE_WAIT_FN(0), None, self.grads.data_ptr(),
+                     loss_out.data_ptr(), self._ws.data_ptr(), self._ws.numel(), _stream()), self._chk)
+
+    def _chk(self, rc, what):
         self._cur = None
-        if self._exc is not None:
+        if self._exc is not None:      # what a callback raised goes before the return code it caused
             raise self._exc
-        if rc < 0:
-            raise _abi.CslError(rc, "csl_sage_rank_fwd_bwd_f32: " + L.csl_sage_last_error().decode() + " / " +
-                                L.csl_gemm_last_error().decode())
+        _SageNative._chk(self, rc, what)
 
 
 class SoftmaxCE(torch.autograd.Function):

@@ -26,37 +26,16 @@ import torch
 
 from . import _abi, aggr, splitgnn
 
-# every symbol include/cslicer_infer.h declares (checked by tests/test_infer_cpu.py)
-SYMBOLS = ["csl_infer_seg", "csl_infer_sage_f32", "csl_infer_gat_partial_ld", "csl_infer_gat_f32", "csl_infer_eval_f32"]
-# every symbol include/cslicer_infer_parts.h declares (checked by tests/test_infer_parts_cpu.py)
-PARTS_SYMBOLS = ["csl_infer_sage_part_f32", "csl_infer_sage_merge_f32", "csl_infer_gat_part_f32", "csl_infer_gat_merge_f32"]
+# every entry point include/cslicer_infer.h and include/cslicer_infer_parts.h declare (bound from the headers' text when
+# the library is loaded: _abi.bind_header)
+_abi.load()
+SYMBOLS, PARTS_SYMBOLS = _abi.BOUND["cslicer_infer.h"], _abi.BOUND["cslicer_infer_parts.h"]
 SEG = 512                 # CSL_INFER_SEG
 CHUNK_ROWS = 1 << 16      # output rows per kernel call / GEMM (bounds the operand and partial scratch)
 GAT_LAST_MAX_C = 4096     # heads x padded classes of an attention model's last layer (csl_infer_gat_f32, last != 0)
-_ready = False
-
-
-def _lib():
-    global _ready
-    L = _abi.load()
-    if not _ready:
-        vp, i64, i32, f32 = C.c_void_p, C.c_int64, C.c_int32, C.c_float
-        L.csl_infer_seg.restype = i32
-        L.csl_infer_sage_f32.argtypes = [vp, vp, vp, i64, vp, i64, i64, i64, vp, i64, i32, i32, vp, i32, vp, vp, i64, vp]
-        L.csl_infer_gat_partial_ld.argtypes = [i32, i32]
-        L.csl_infer_gat_partial_ld.restype = i64
-        L.csl_infer_gat_f32.argtypes = [vp, vp, vp, i64, vp, i64, i64, i64, vp, vp, vp, i32, i32, f32, vp, i32, i32, vp, vp,
-                                        i64, vp]
-        L.csl_infer_eval_f32.argtypes = [vp, i64, i64, i32, vp, vp, vp, vp, vp, vp]
-        L.csl_infer_sage_part_f32.argtypes = [vp, vp, vp, i64, vp, i64, i64, i64, vp, i64, i32, i32, vp, vp, vp]
-        L.csl_infer_sage_merge_f32.argtypes = [vp, vp, i64, i32, vp, vp, i64, i32, i32, vp, i32, vp, i64, vp]
-        L.csl_infer_gat_part_f32.argtypes = [vp, vp, vp, i64, vp, i64, i64, i64, vp, vp, vp, i32, i32, f32, i32, vp, vp,
-                                             vp]
-        L.csl_infer_gat_merge_f32.argtypes = [vp, i64, i32, vp, i32, i32, vp, i32, i32, vp, i64, vp]
-        if L.csl_infer_seg() != SEG:
-            raise ImportError("libcslicer_hip.so: CSL_INFER_SEG differs from cslicer.infer.SEG")
-        _ready = True
-    return L
+_lib = _abi.load      # (every prototype is bound there; the tests and profiles/ reach the library by this name)
+if _lib().csl_infer_seg() != SEG:
+    raise ImportError("libcslicer_hip.so: CSL_INFER_SEG differs from cslicer.infer.SEG")
 
 
 def _ptr(t, off=0):

@@ -34,9 +34,71 @@ def test_aggregation_symbols_exported():
     L = _abi.load()
     src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "cslicer_aggr.h")).read(), flags=re.S)
     names = sorted(set(re.findall(r"\b(csl_[a-z_0-9]+)\s*\(", src)))
+    assert len(names) == 66      # (the list is what the binder found in the header: an empty header would agree too)
     assert names == sorted(aggr.SYMBOLS)
     for n in names:
         assert hasattr(L, n)
+
+
+def test_prototypes_are_the_headers():
+    """_abi.load() takes argtypes / restype of four headers' entry points from the headers' text.  The literals below
+    are copies of the hand-typed tables that derivation replaced, so they do not depend on its parser."""
+    from cslicer import aggr, infer
+    L = _abi.load()
+    vp, cp, i64, i32, f32, i = C.c_void_p, C.c_char_p, C.c_int64, C.c_int32, C.c_float, C.c_int
+    xf, wf = _abi.EXCHANGE_FN, _abi.EXCHANGE_WAIT_FN
+    assert (aggr.EXCHANGE_FN, aggr.EXCHANGE_WAIT_FN) == (xf, wf)
+    want = {
+        "csl_spmm_sum_f32": ([vp, vp, vp, i64, vp, i64, vp, i64, i32, vp], i),
+        "csl_gat_fwd_f32": ([vp, vp, i64, vp, vp, vp, i32, i32, f32, vp, vp, vp, vp], i),
+        "csl_adam_f32": ([i32, vp, vp, vp, vp, vp, f32, f32, f32, f32, i64, vp], i),
+        "csl_gemm_save_plans": ([cp], i),
+        "csl_gemm_last_error": ([], cp),
+        "csl_relu_bwd_colsum_scratch": ([i64, i32], i64),
+        "csl_gat_in_proj_ok": ([i32, i32, i32], i32),
+        "csl_sage_step_timing_read": ([vp, vp], i),
+        "csl_sage_rank_fwd_bwd_x16": ([i32, vp, vp, vp, vp, vp, i32, i64, vp, vp, vp, vp, f32, i64, i32, xf, wf, vp, vp, vp,
+                                       vp, i64, vp], i),
+        "csl_gat_in_layer_bwd_f32": ([vp, vp, vp, vp, vp, i64, i32, vp, vp, vp, i32, i32, f32, i32, i64, i64, i32,
+                                      vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp], i),
+        "csl_infer_gat_f32": ([vp, vp, vp, i64, vp, i64, i64, i64, vp, vp, vp, i32, i32, f32, vp, i32, i32, vp, vp, i64,
+                               vp], i),
+        "csl_infer_seg": ([], i32),
+        "csl_infer_gat_merge_f32": ([vp, i64, i32, vp, i32, i32, vp, i32, i32, vp, i64, vp], i),
+    }
+    assert len(want["csl_gat_in_layer_bwd_f32"][0]) == 31
+    for name, (argtypes, restype) in want.items():
+        fn = getattr(L, name)
+        assert list(fn.argtypes) == argtypes, name
+        assert fn.restype is restype, name
+    names = aggr.SYMBOLS + aggr.FEAT16_SYMBOLS + infer.SYMBOLS + infer.PARTS_SYMBOLS
+    assert len(names) == len(set(names)) == 81
+    for name in names:
+        fn = getattr(L, name)
+        assert fn.argtypes is not None, name
+        assert all(t in (vp, cp, i, i32, i64, f32, xf, wf) for t in fn.argtypes), name
+        assert fn.restype in (i, i32, i64, cp), name
+
+
+def test_binder_refuses_what_it_does_not_know(tmp_path):
+    L = _abi.load()
+
+    def header(text):
+        path = tmp_path / "h.h"
+        path.write_text("/* a header */\n#include <stddef.h>\n" + text + "\n")
+        return str(path)
+    with pytest.raises(ValueError, match="size_t"):
+        _abi.bind_header(L, header("int csl_x(size_t n);"))
+    with pytest.raises(ValueError, match="csl_exchange_fn"):       # a name only `types` can give a type
+        _abi.bind_header(L, header("int csl_x(csl_exchange_fn exchange);"))
+    with pytest.raises(AttributeError, match="csl_not_in_the_library"):
+        _abi.bind_header(L, header("int csl_not_in_the_library(int32_t n);"))
+    with pytest.raises(ImportError, match="no_such_header.h"):
+        _abi.bind_header(L, "no_such_header.h")
+    # what it does know, from such a file: a declared function of the library, bound as declared
+    assert _abi.bind_header(L, header("typedef int (*csl_cb)(void* user);\n// int csl_y(void);\n"
+                                      "int64_t csl_softmax_ce_scratch(int64_t n);")) == ["csl_softmax_ce_scratch"]
+    assert L.csl_softmax_ce_scratch.argtypes == [C.c_int64] and L.csl_softmax_ce_scratch.restype is C.c_int64
 
 
 def test_abi_version_and_struct_layout():

@@ -15,6 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_header_matches_binding_and_library():
     src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "cslicer_infer.h")).read(), flags=re.S)
     names = sorted(set(re.findall(r"\b(csl_[a-z_0-9]+)\s*\(", src)))
+    assert len(names) == 5
     assert names == sorted(infer.SYMBOLS)
     L = infer._lib()
     for n in names:

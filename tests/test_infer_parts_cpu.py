@@ -20,6 +20,7 @@ S = infer.SEG
 def test_header_matches_binding_and_library():
     src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "cslicer_infer_parts.h")).read(), flags=re.S)
     names = sorted(set(re.findall(r"\b(csl_[a-z_0-9]+)\s*\(", src)))
+    assert len(names) == 4
     assert names == sorted(infer.PARTS_SYMBOLS)
     L = infer._lib()
     for n in names:
