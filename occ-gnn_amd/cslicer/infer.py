@@ -18,6 +18,12 @@ current stream, after whatever is already enqueued there.
 
 Widths that are not multiples of 4 (the kernels move float4 columns) are padded: the feature table on upload, every
 later table by zero weight rows / columns, so that padding columns hold exact zeros.
+
+A float16 / bfloat16 feature table (include/cslicer_infer16.h) is read IN PLACE by the first layer, the only one that
+reads it: the GraphSAGE aggregate-first kernels load its rows and upcast them in registers (the _x16 twins), and where
+the library GEMM reads the table (GraphSAGE project-first, the attention model's projections) each chunk of rows is
+upcast into one reusable float32 buffer first.  Both upcasts are exact and everything behind them is the float32 code, so
+the logits are bitwise those of the same call on the table upcast to float32 -- without ever holding that copy.
 """
 import ctypes as C
 
@@ -30,6 +36,7 @@ from . import _abi, aggr, splitgnn
 # the library is loaded: _abi.bind_header)
 _abi.load()
 SYMBOLS, PARTS_SYMBOLS = _abi.BOUND["cslicer_infer.h"], _abi.BOUND["cslicer_infer_parts.h"]
+FEAT16_SYMBOLS = _abi.BOUND["cslicer_infer16.h"]    # the readers of a 16-bit feature table
 SEG = 512                 # CSL_INFER_SEG
 CHUNK_ROWS = 1 << 16      # output rows per kernel call / GEMM (bounds the operand and partial scratch)
 GAT_LAST_MAX_C = 4096     # heads x padded classes of an attention model's last layer (csl_infer_gat_f32, last != 0)
@@ -50,6 +57,11 @@ def _chk(rc, what):
 
 def _r4(x):
     return (int(x) + 3) // 4 * 4
+
+
+def _kind(t):
+    """None for a float32 table, the element kind (CSL_FEAT_F16 / CSL_FEAT_BF16) of a 16-bit one"""
+    return None if t.dtype == torch.float32 else aggr.FEAT_KINDS[t.dtype]
 
 
 # ------------------------------------------------------------------ graph and work list (host)
@@ -221,11 +233,31 @@ def _gemm_into(out, a, w, bias=None, relu=False):
         raise _abi.CslError(rc, "csl_gemm_f32: " + L.csl_gemm_last_error().decode())
 
 
+class _RowChunks(object):
+    """The rows [r0, r1) of a layer's input table as a float32 GEMM operand, r1 - r0 <= chunk_rows: a float32 table's
+    rows in place; a 16-bit table's upcast (csl_upcast_rows_x16) into ONE reusable buffer [min(chunk_rows, rows), width]
+    -- the float32 path's chunk boundaries, shapes and row stride, so the GEMM computes the same bits."""
+
+    def __init__(self, h, chunk_rows):
+        self.h, self.kind, self.buf = h, _kind(h), None
+        if self.kind is not None:
+            self.buf = torch.empty((min(chunk_rows, max(h.shape[0], 1)), h.shape[1]), dtype=torch.float32, device=h.device)
+
+    def __call__(self, r0, r1):
+        h = self.h
+        if self.kind is None:
+            return h[r0:r1]
+        _chk(_lib().csl_upcast_rows_x16(_ptr(h, r0 * h.stride(0)), self.kind, h.stride(0), r1 - r0, _ptr(self.buf),
+                                        self.buf.stride(0), h.shape[1], aggr._stream()), "csl_upcast_rows_x16")
+        return self.buf[:r1 - r0]
+
+
 def _project_rows(h, w, out, chunk_rows, bias=None):
     """out[r] = h[r] . w^T (+ bias) for every row, chunk by chunk (shapes that repeat; no GEMM over 10^7 rows)"""
+    rows = _RowChunks(h, chunk_rows)
     for r0 in range(0, h.shape[0], chunk_rows):
         r1 = min(h.shape[0], r0 + chunk_rows)
-        _gemm_into(out[r0:r1], h[r0:r1], w, bias)
+        _gemm_into(out[r0:r1], rows(r0, r1), w, bias)
 
 
 def _partial(n_rows, width, device):
@@ -234,16 +266,17 @@ def _partial(n_rows, width, device):
 
 def sage_rows(g, dplan, x, ldx, W, proj, bias, relu, out, chunk_rows, scratch=None):
     """csl_infer_sage_f32 over every chunk of the plan; out row k of the plan is out[k] (proj) -- for the aggregate-first
-    form `out` is a callable (k0, k1) -> the chunk's operand buffer, and `scratch` is called after each chunk"""
-    L = _lib()
+    form `out` is a callable (k0, k1) -> the chunk's operand buffer, and `scratch` is called after each chunk.  x may be
+    a 16-bit feature table (aggregate-first only): csl_infer_sage_x16 reads it in place."""
+    twins, kind = aggr._twins("infer_sage"), _kind(x)
     st = aggr._stream()
     for (k0, k1, i0, i1, h0, h1, p0, npart) in dplan.chunks(chunk_rows):
         part = _partial(npart, W, x.device) if npart else None
         dst = out(k0, k1) if callable(out) else out[k0:k1]
-        _chk(L.csl_infer_sage_f32(_ptr(g.indptr), _ptr(g.indices), _ptr(dplan.items, 4 * i0), i1 - i0,
-                                  _ptr(dplan.hubs, 4 * h0) if h1 > h0 else C.c_void_p(0), h1 - h0, k0, p0, _ptr(x), ldx, W,
-                                  int(proj), _ptr(bias), int(relu), _ptr(part), _ptr(dst), dst.stride(0), st),
-             "csl_infer_sage_f32")
+        aggr._table_call(twins, kind,
+                         (_ptr(g.indptr), _ptr(g.indices), _ptr(dplan.items, 4 * i0), i1 - i0,
+                          _ptr(dplan.hubs, 4 * h0) if h1 > h0 else C.c_void_p(0), h1 - h0, k0, p0, _ptr(x)),
+                         (ldx, W, int(proj), _ptr(bias), int(relu), _ptr(part), _ptr(dst), dst.stride(0), st), _chk)
         if scratch is not None:
             scratch(k0, k1, dst)
 
@@ -263,8 +296,9 @@ def gat_rows(g, dplan, z, el, er, H, D, slope, bias, last, n_cls, out, chunk_row
 
 
 def _sage_layer(g, dplan, h, conv, relu, chunk_rows):
-    """One DistSageConv over the rows of `dplan`; h: [N, hp] table (hp % 4 == 0, padding columns zero).  Aggregate
-    first when out >= in, project first otherwise.  Returns the [rows, round4(out)] table (padding columns zero)."""
+    """One DistSageConv over the rows of `dplan`; h: [N, hp] table (hp % 4 == 0, padding columns zero; float32, or the
+    first layer's feature table in its stored 16-bit type, row stride h.stride(0)).  Aggregate first when out >= in,
+    project first otherwise.  Returns the [rows, round4(out)] float32 table (padding columns zero)."""
     dev = h.device
     W, b = conv.fc.weight.detach().float(), conv.fc.bias.detach().float()
     out_w, in_w = W.shape[0], W.shape[1] // 2
@@ -276,7 +310,7 @@ def _sage_layer(g, dplan, h, conv, relu, chunk_rows):
         wc[:, :in_w], wc[:, hp:hp + in_w] = W[:, :in_w], W[:, in_w:]
         y = torch.zeros((n_rows, op), dtype=torch.float32, device=dev)
         cat = torch.empty((min(chunk_rows, max(n_rows, 1)), 2 * hp), dtype=torch.float32, device=dev)
-        sage_rows(g, dplan, h, hp, hp, False, None, False, lambda k0, k1: cat[:k1 - k0], chunk_rows,
+        sage_rows(g, dplan, h, h.stride(0), hp, False, None, False, lambda k0, k1: cat[:k1 - k0], chunk_rows,
                   scratch=lambda k0, k1, c: _gemm_into(y[k0:k1, :out_w], c, wc, b, relu))
         return y
     # (b) P = h . [W_self; W_neigh]^T once for every node, then act(P[v, :out] + mean P[u, out:] + b) in one pass
@@ -292,7 +326,8 @@ def _sage_layer(g, dplan, h, conv, relu, chunk_rows):
 
 
 def _gat_layer(g, dplan, h, in_map, conv, last, n_cls, chunk_rows):
-    """One DistGATConv over the rows of `dplan`; h: [N, hp] table whose logical column c sits at in_map[c].  Returns
+    """One DistGATConv over the rows of `dplan`; h: [N, hp] table whose logical column c sits at in_map[c] (float32, or
+    the first layer's feature table in its stored 16-bit type: its rows reach the GEMMs through _RowChunks).  Returns
     (table, its column map): hidden layers [N, H * round4(D)], the last [rows, n_cls]."""
     dev = h.device
     H, D = conv.H, conv.D
@@ -316,15 +351,18 @@ def _gat_layer(g, dplan, h, in_map, conv, last, n_cls, chunk_rows):
         # likewise, two [N, H] GEMMs on the layer's input (the same logits, summed in another order)
         wv = wz.view(H, Dp, hp)
         vl, vr = torch.einsum("hdf,hd->hf", wv, al).contiguous(), torch.einsum("hdf,hd->hf", wv, ar).contiguous()
+    rows = _RowChunks(h, chunk_rows)
     for r0 in range(0, g.N, chunk_rows):
         r1 = min(g.N, r0 + chunk_rows)
-        _gemm_into(z[r0:r1], h[r0:r1], wz)
+        hc = rows(r0, r1)
+        _gemm_into(z[r0:r1], hc, wz)
         if Dp > 256:
-            _gemm_into(el[r0:r1], h[r0:r1], vl)
-            _gemm_into(er[r0:r1], h[r0:r1], vr)
+            _gemm_into(el[r0:r1], hc, vl)
+            _gemm_into(er[r0:r1], hc, vr)
         else:
             _chk(AL.csl_gat_logits_fwd_f32(_ptr(z[r0]), _ptr(al), _ptr(ar), r1 - r0, H, Dp, _ptr(el[r0]), _ptr(er[r0]),
                                            aggr._stream()), "csl_gat_logits_fwd_f32")
+    rows = hc = None      # (the upcast buffer of a 16-bit table goes back before the layer's outputs are allocated)
     n_rows = dplan.plan["n"]
     if last:
         out = torch.empty((n_rows, n_cls), dtype=torch.float32, device=dev)
@@ -338,29 +376,79 @@ def _gat_layer(g, dplan, h, in_map, conv, last, n_cls, chunk_rows):
 
 # ------------------------------------------------------------------ public interface
 
-def _need_bytes(model, N, n_out, F, chunk_rows, max_parts):
-    """the device bytes full_inference allocates at its peak (float32 tables; the graph and plan not included)"""
-    f = 4
+def _feat16_dtype(features):
+    """torch.float16 / torch.bfloat16 if `features` holds 16-bit elements (a tensor of either type, a float16 host
+    array), else None: everything else takes the float32 path"""
+    if torch.is_tensor(features):
+        return features.dtype if features.dtype in aggr.FEAT_KINDS else None
+    return torch.float16 if getattr(features, "dtype", None) == np.float16 else None
+
+
+def _feat16_in_place(t, zero_padded):
+    """The [rows, round4(F)] view of the 16-bit device table t [rows, F] that the first layer can read in place, or None
+    (a copy is needed): unit column stride, a row stride that is a multiple of 4 and at least round4(F), an 8-byte aligned
+    base, and either F % 4 == 0 or the caller's word (zero_padded) that the columns F .. round4(F) of every row are
+    stored and hold zeros.  An empty table is never read in place (the kernels refuse a null table)."""
+    if not torch.is_tensor(t) or not t.is_cuda or t.dim() != 2 or t.shape[0] == 0:
+        return None
+    F, w = t.shape[1], _r4(t.shape[1])
+    if t.stride(1) != 1 or t.stride(0) % 4 or t.stride(0) < w or t.data_ptr() % 8:
+        return None
+    if w == F:
+        return t
+    if not zero_padded or (t.storage_offset() + (t.shape[0] - 1) * t.stride(0) + w) * 2 > t.untyped_storage().nbytes():
+        return None
+    return t.as_strided((t.shape[0], w), (t.stride(0), 1))
+
+
+def _table16(features, rows, view, dtype, dev):
+    """the first layer's table of a 16-bit input: the in-place view, else a zero-padded 16-bit device copy
+    [rows, round4(F)] (2 bytes per element, never a float32 copy); without rows an empty float32 table"""
+    if view is not None:
+        return view
+    F = features.shape[1]
+    if rows == 0:
+        return torch.zeros((0, _r4(F)), dtype=torch.float32, device=dev)
+    h = torch.zeros((rows, _r4(F)), dtype=dtype, device=dev)
+    h[:, :F].copy_(torch.as_tensor(features))
+    return h
+
+
+def _input_bytes(k, rows, width, chunk_rows, gemm_form, feat_size, feat_copy):
+    """the bytes layer k's input table contributes: rows width 4 for a float32 table (every layer after the first, and
+    a float32 feature table); for a 16-bit feature table (k == 0, feat_size == 2) rows width 2 only if a device copy of
+    it is made (feat_copy), plus, where the library GEMM reads it (gemm_form), the one upcast buffer
+    min(chunk_rows, rows) width 4"""
+    if k > 0 or feat_size == 4:
+        return rows * width * 4
+    return (rows * width * 2 if feat_copy else 0) + (min(chunk_rows, rows) * width * 4 if gemm_form else 0)
+
+
+def _need_bytes(model, N, n_out, F, chunk_rows, max_parts, feat_size=4, feat_copy=False):
+    """the device bytes full_inference allocates at its peak (the graph and plan not included): per layer its input
+    table (_input_bytes), its float32 output table and its scratch; feat_size: bytes per element of the feature table"""
     need, width = 0, _r4(F)
     if isinstance(model, splitgnn.DistSAGEModel):
         for k, conv in enumerate(model.convs):
             out_w, in_w = conv.fc.weight.shape[0], conv.fc.weight.shape[1] // 2
             rows = n_out if k + 1 == len(model.convs) else N
             op = _r4(out_w)
-            t = N * width + rows * op
+            t = rows * op
             if out_w >= in_w:
                 t += min(chunk_rows, rows) * 2 * width + max_parts * width
             else:
                 t += N * 2 * op + max_parts * op
+            t = 4 * t + _input_bytes(k, N, width, chunk_rows, out_w < in_w, feat_size, feat_copy)
             need, width = max(need, t), op
     else:
         for k, conv in enumerate(model.convs):
             last = k + 1 == len(model.convs)
             C_ = conv.H * _r4(conv.D)
-            t = N * width + N * C_ + 2 * N * conv.H + (n_out * model.n_classes if last else N * C_)
+            t = N * C_ + 2 * N * conv.H + (n_out * model.n_classes if last else N * C_)
             t += max_parts * (C_ + 2 * conv.H + 4)
+            t = 4 * t + _input_bytes(k, N, width, chunk_rows, True, feat_size, feat_copy)
             need, width = max(need, t), C_
-    return need * f
+    return need
 
 
 def _check_memory(need, device):
@@ -370,11 +458,17 @@ def _check_memory(need, device):
         raise MemoryError("full_inference needs %d bytes of device memory, %d are free" % (need, free))
 
 
-def full_inference(model, indptr, indices, features, nodes=None, chunk_rows=CHUNK_ROWS):
+def full_inference(model, indptr, indices, features, nodes=None, chunk_rows=CHUNK_ROWS, _zero_padded=False):
     """float32 logits [len(nodes) (or N), n_classes] on the device of `features` of a DistSAGEModel or DistGATModel
     applied with every neighbour (module docstring).  Hidden layers are computed for all N nodes, the last one only for
     `nodes` (int array of node ids; None: all).  features: float32 [N, F] (a device tensor is used in place when F % 4 == 0;
-    anything else is uploaded / padded).  Runs under torch.no_grad() and changes no parameter.  Every width is supported
+    anything else is uploaded / padded), or float16 / bfloat16 [N, F]: a device tensor with unit column stride, a row
+    stride that is a multiple of 4 and at least round4(F), an 8-byte aligned base and F % 4 == 0 is read in place by the
+    first layer (module docstring); any other 16-bit input (a host array, another width, another alignment) becomes a
+    zero-padded 16-bit device copy [N, round4(F)], never a float32 one.  The logits are bitwise those of the call on
+    the table upcast to float32.  (_zero_padded: the caller's word that the rows of a device table with F % 4 != 0 are
+    stored padded to round4(F) with zeros -- the trainer's own storage -- so that it too is read in place.)
+    Runs under torch.no_grad() and changes no parameter.  Every width is supported
     except an attention model whose last layer has more than GAT_LAST_MAX_C = 4096 heads x padded-class columns
     (ValueError).  Before allocating, the device bytes it needs (tables, scratch and, on first use of a graph, the
     graph's CSR and work list) are checked against the free memory: MemoryError with both counts."""
@@ -402,14 +496,18 @@ def full_inference(model, indptr, indices, features, nodes=None, chunk_rows=CHUN
         dlast = g.plan(nodes)
         n_out = dlast.plan["n"]
         max_parts = max([c[7] for c in g.all_rows.chunks(chunk_rows)] + [c[7] for c in dlast.chunks(chunk_rows)] + [0])
-        need = _need_bytes(model, N, n_out, F, chunk_rows, max_parts)
+        dt16 = _feat16_dtype(features)
+        view = _feat16_in_place(features, _zero_padded) if dt16 is not None else None
+        need = _need_bytes(model, N, n_out, F, chunk_rows, max_parts, 4 if dt16 is None else 2, view is None)
         need += (0 if g.uploaded() else g.device_bytes()) + (dlast.nbytes() if nodes is not None else 0)
-        upload = not (torch.is_tensor(features) and features.is_cuda and features.dtype == torch.float32
-                      and F % 4 == 0 and features.stride(1) == 1 and features.stride(0) == F)
+        upload = dt16 is None and not (torch.is_tensor(features) and features.is_cuda and features.dtype == torch.float32
+                                       and F % 4 == 0 and features.stride(1) == 1 and features.stride(0) == F)
         _check_memory(need + (N * _r4(F) * 4 if upload else 0), dev)
         g.upload()
         dlast.upload()
-        if upload:
+        if dt16 is not None:
+            h = _table16(features, N, view, dt16, dev)
+        elif upload:
             h = torch.zeros((N, _r4(F)), dtype=torch.float32, device=dev)
             h[:, :F] = torch.as_tensor(features).to(dev, torch.float32)
         else:
@@ -445,14 +543,15 @@ def eval_head(logits, labels):
     return pred[:n], int(correct.item()), float(loss_sum.item())
 
 
-def evaluate(model, indptr, indices, features, nodes, labels, chunk_rows=CHUNK_ROWS):
+def evaluate(model, indptr, indices, features, nodes, labels, chunk_rows=CHUNK_ROWS, _zero_padded=False):
     """{"accuracy", "loss", "n"} of the model on `nodes` by full-neighbour inference: argmax accuracy and mean
     cross-entropy.  labels: int [N], the label of every node of the graph (those of `nodes` are used)."""
     nodes = np.asarray(nodes.cpu() if torch.is_tensor(nodes) else nodes).astype(np.int64).reshape(-1)
     lab = torch.as_tensor(labels)
     if lab.dim() != 1 or lab.shape[0] != features.shape[0]:
         raise ValueError("labels must hold one label per node of the graph ([%d])" % features.shape[0])
-    logits = full_inference(model, indptr, indices, features, nodes=nodes, chunk_rows=chunk_rows)
+    logits = full_inference(model, indptr, indices, features, nodes=nodes, chunk_rows=chunk_rows,
+                            _zero_padded=_zero_padded)
     lab = lab[torch.from_numpy(nodes).to(lab.device)]
     _, correct, loss = eval_head(logits, lab.to(logits.device))
     n = int(nodes.shape[0])
@@ -652,8 +751,12 @@ def _exchange(comm, recv, R, send, S, send_counts, recv_counts):
 
 
 def _sage_layer_parts(pp, dp, h, conv, relu, comm):
-    """One DistSageConv over the rank's destinations of `pp`; h: [n_own, hp] own rows.  Returns [m, round4(out)]."""
+    """One DistSageConv over the rank's destinations of `pp`; h: [n_own, hp] own rows (float32, or the first layer's
+    feature rows in their stored 16-bit type: the aggregate-first kernels read them in place, the projection through
+    _RowChunks).  Returns [m, round4(out)]."""
     L = _lib()
+    kind = _kind(h)
+    part_twins, merge_twins = aggr._twins("infer_sage_part"), aggr._twins("infer_sage_merge")
     st = aggr._stream()
     dev = h.device
     W, b = conv.fc.weight.detach().float(), conv.fc.bias.detach().float()
@@ -666,7 +769,7 @@ def _sage_layer_parts(pp, dp, h, conv, relu, comm):
         wc[:, :in_w], wc[:, hp:hp + in_w] = W[:, :in_w], W[:, in_w:]
         y = torch.zeros((pp.m, op), dtype=torch.float32, device=dev)
         cat = torch.empty((min(pp.chunk_rows, max(pp.m, 1)), 2 * hp), dtype=torch.float32, device=dev)
-        Y, ldy, Wy = h, hp, hp
+        Y, ldy, Wy = h, h.stride(0), hp
     else:
         wp = torch.zeros((2 * op, hp), dtype=torch.float32, device=dev)
         wp[:out_w, :in_w], wp[op:op + out_w, :in_w] = W[:, :in_w], W[:, in_w:]
@@ -683,14 +786,16 @@ def _sage_layer_parts(pp, dp, h, conv, relu, comm):
     recv = torch.empty((R_max, Wy), dtype=torch.float32, device=dev)
     part = _partial(max([c[7] for c in chunks] + [0]), Wy, dev)
     for c, (s0, s1, i0, i1, h0, h1, p0, npart, o0, o1, r0, r1) in enumerate(chunks):
-        _chk(L.csl_infer_sage_part_f32(_ptr(dp["ip"]), _ptr(dp["ix"]), _ptr(dp["items"], 4 * i0), i1 - i0,
-                                       _ptr(dp["hubs"], 4 * h0) if h1 > h0 else C.c_void_p(0), h1 - h0, s0, p0,
-                                       _ptr(Y, 0 if agg_first else op), ldy, Wy, pack, _ptr(part), _ptr(send), st),
-             "csl_infer_sage_part_f32")
+        # (Y is the layer's input table itself in the aggregate-first form, else the float32 projection)
+        aggr._table_call(part_twins, kind if agg_first else None,
+                         (_ptr(dp["ip"]), _ptr(dp["ix"]), _ptr(dp["items"], 4 * i0), i1 - i0,
+                          _ptr(dp["hubs"], 4 * h0) if h1 > h0 else C.c_void_p(0), h1 - h0, s0, p0,
+                          _ptr(Y, 0 if agg_first else op)), (ldy, Wy, pack, _ptr(part), _ptr(send), st), _chk)
         _exchange(comm, recv, r1 - r0, send, s1 - s0, pp.sub_counts[c], pp.own_counts[c])
         if agg_first:
-            _chk(L.csl_infer_sage_merge_f32(_ptr(dp["dst"], 2 * o0), _ptr(dp["ml"], pp.P * o0), o1 - o0, pp.P, _ptr(recv),
-                                            _ptr(h), hp, hp, 0, None, 0, _ptr(cat), 2 * hp, st), "csl_infer_sage_merge_f32")
+            aggr._table_call(merge_twins, kind,
+                             (_ptr(dp["dst"], 2 * o0), _ptr(dp["ml"], pp.P * o0), o1 - o0, pp.P, _ptr(recv), _ptr(h)),
+                             (h.stride(0), hp, 0, None, 0, _ptr(cat), 2 * hp, st), _chk)
             _gemm_into(y[o0:o1, :out_w], cat[:o1 - o0], wc, b, relu)
         else:
             _chk(L.csl_infer_sage_merge_f32(_ptr(dp["dst"], 2 * o0), _ptr(dp["ml"], pp.P * o0), o1 - o0, pp.P, _ptr(recv),
@@ -701,7 +806,8 @@ def _sage_layer_parts(pp, dp, h, conv, relu, comm):
 
 def _gat_layer_parts(pp, dp, h, in_map, conv, last, n_cls, comm):
     """One DistGATConv over the rank's destinations of `pp`; h: [n_own, hp] own rows whose logical column c sits at
-    in_map[c].  Returns (table, column map) as _gat_layer."""
+    in_map[c] (float32, or the first layer's feature rows in their stored 16-bit type).  Returns (table, column map) as
+    _gat_layer."""
     L, AL = _lib(), aggr._lib()
     st = aggr._stream()
     dev = h.device
@@ -724,15 +830,18 @@ def _gat_layer_parts(pp, dp, h, in_map, conv, last, n_cls, comm):
     if Dp > 256:
         wv = wz.view(H, Dp, hp)
         vl, vr = torch.einsum("hdf,hd->hf", wv, al).contiguous(), torch.einsum("hdf,hd->hf", wv, ar).contiguous()
+    rows = _RowChunks(h, pp.chunk_rows)
     for r0 in range(0, n_own, pp.chunk_rows):
         r1 = min(n_own, r0 + pp.chunk_rows)
-        _gemm_into(z[r0:r1], h[r0:r1], wz)
+        hc = rows(r0, r1)
+        _gemm_into(z[r0:r1], hc, wz)
         if Dp > 256:
-            _gemm_into(el[r0:r1], h[r0:r1], vl)
-            _gemm_into(er[r0:r1], h[r0:r1], vr)
+            _gemm_into(el[r0:r1], hc, vl)
+            _gemm_into(er[r0:r1], hc, vr)
         else:
             _chk(AL.csl_gat_logits_fwd_f32(_ptr(z[r0]), _ptr(al), _ptr(ar), r1 - r0, H, Dp, _ptr(el[r0]), _ptr(er[r0]),
                                            st), "csl_gat_logits_fwd_f32")
+    rows = hc = None      # (the upcast buffer of a 16-bit table goes back before the exchange buffers are allocated)
     pld = int(L.csl_infer_gat_partial_ld(H, Dp))
     chunks = pp.chunks()
     pack = pp.pack(Cz)
@@ -761,10 +870,9 @@ def _gat_layer_parts(pp, dp, h, in_map, conv, last, n_cls, comm):
     return out, cmap
 
 
-def _need_bytes_parts(model, n_own, F, plans):
-    """the device bytes full_inference_parts allocates at its peak (float32 tables and per-chunk buffers; the plans'
-    device copies not included)"""
-    f = 4
+def _need_bytes_parts(model, n_own, F, plans, feat_size=4, feat_copy=False):
+    """the device bytes full_inference_parts allocates at its peak (tables and per-chunk buffers; the plans' device
+    copies not included): as _need_bytes, over the rank's n_own rows"""
     hid, lastp = plans
     need, width = 0, _r4(F)
 
@@ -777,19 +885,20 @@ def _need_bytes_parts(model, n_own, F, plans):
         if isinstance(model, splitgnn.DistSAGEModel):
             out_w, in_w = conv.fc.weight.shape[0], conv.fc.weight.shape[1] // 2
             op = _r4(out_w)
-            t = n_own * width + pp.m * op
+            t = pp.m * op
             if out_w >= in_w:
                 t += min(pp.chunk_rows, max(pp.m, 1)) * 2 * width + (S + R + parts) * width
             else:
                 t += n_own * 2 * op + (S + R + parts) * op
-            width = op
+            gemm_form, out_width = out_w < in_w, op
         else:
             C_ = conv.H * _r4(conv.D)
             pld = C_ + 2 * conv.H + 4
-            t = n_own * width + n_own * C_ + 2 * n_own * conv.H + pp.m * C_ + (S + R + parts) * pld + S * conv.H
-            width = C_
-        need = max(need, t)
-    return need * f
+            t = n_own * C_ + 2 * n_own * conv.H + pp.m * C_ + (S + R + parts) * pld + S * conv.H
+            gemm_form, out_width = True, C_
+        t = 4 * t + _input_bytes(k, n_own, width, pp.chunk_rows, gemm_form, feat_size, feat_copy)
+        need, width = max(need, t), out_width
+    return need
 
 
 def _nodes_key(nodes):
@@ -801,12 +910,13 @@ def _nodes_key(nodes):
 
 
 def full_inference_parts(model, indptr, indices, features_own, comm, owner=None, nodes=None, chunk_rows=CHUNK_ROWS,
-                         _check=None):
+                         _check=None, _zero_padded=False):
     """full_inference on one rank of a split-parallel run: float32 logits [own positions of `nodes`, n_classes] of the
     nodes of `nodes` this rank owns, in `nodes` order (None: every node; see owns()).  Collective over comm (a
     splitgnn.DistComm): every rank calls it with the same model, graph, owner table and nodes.
 
-    features_own: float32 [n_own, F], the rows of the rank's own nodes in ascending node order.  owner: int32 [N] owner
+    features_own: float32, float16 or bfloat16 [n_own, F], the rows of the rank's own nodes in ascending node order (a
+    16-bit device table is read in place or copied in its own type as full_inference says; _zero_padded likewise).  owner: int32 [N] owner
     rank of every node (None: v % P).  Hidden layers are computed for the rank's own nodes, the last one for its own
     nodes among `nodes`.  Every rank receives at most P partial rows per own destination and chunk; no rank ever holds
     another rank's feature or hidden rows.  `nodes` is compared across ranks (length and a 64-bit hash: ValueError on
@@ -852,9 +962,13 @@ def full_inference_parts(model, indptr, indices, features_own, comm, owner=None,
         hid = rg.plan(chunk_rows)
         lastp = hid if nodes is None else rg.plan(chunk_rows, nodes)
         F = features_own.shape[1]
-        upload = not (torch.is_tensor(features_own) and features_own.is_cuda and features_own.dtype == torch.float32
-                      and F % 4 == 0 and features_own.stride(1) == 1 and features_own.stride(0) == F)
-        need = _need_bytes_parts(model, n_own, F, (hid, lastp)) + (n_own * _r4(F) * 4 if upload else 0)
+        dt16 = _feat16_dtype(features_own)
+        view = _feat16_in_place(features_own, _zero_padded) if dt16 is not None else None
+        upload = dt16 is None and not (torch.is_tensor(features_own) and features_own.is_cuda
+                                       and features_own.dtype == torch.float32 and F % 4 == 0
+                                       and features_own.stride(1) == 1 and features_own.stride(0) == F)
+        need = _need_bytes_parts(model, n_own, F, (hid, lastp), 4 if dt16 is None else 2, view is None)
+        need += n_own * _r4(F) * 4 if upload else 0
         need += (0 if hid.dev is not None else hid.device_bytes(gat)) + (lastp.device_bytes(gat) if lastp is not hid else 0)
         free, _ = torch.cuda.mem_get_info(dev)
         free += torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
@@ -863,7 +977,9 @@ def full_inference_parts(model, indptr, indices, features_own, comm, owner=None,
             raise MemoryError("full_inference_parts needs %d bytes of device memory on a rank where %d are free"
                               % (short[0][0], short[0][1]))
         dh, dl = hid.upload(dev, gat), lastp.upload(dev, gat)
-        if upload:
+        if dt16 is not None:
+            h = _table16(features_own, n_own, view, dt16, dev)
+        elif upload:
             h = torch.zeros((n_own, _r4(F)), dtype=torch.float32, device=dev)
             if n_own:
                 h[:, :F] = torch.as_tensor(features_own).to(dev, torch.float32)
@@ -892,7 +1008,8 @@ def owns(N, P, rank, nodes, owner=None):
     return own == rank
 
 
-def evaluate_parts(model, indptr, indices, features_own, comm, nodes, labels_own, owner=None, chunk_rows=CHUNK_ROWS):
+def evaluate_parts(model, indptr, indices, features_own, comm, nodes, labels_own, owner=None, chunk_rows=CHUNK_ROWS,
+                   _zero_padded=False):
     """evaluate() on one rank of a split-parallel run (collective, see full_inference_parts): {"accuracy", "loss", "n"}
     of the model on `nodes`, the same dict on every rank.  labels_own: int [n_own], the labels of the rank's own nodes in
     ascending node order.  Each rank scores its own nodes among `nodes`; the per-rank (correct, float64 loss sum, n) are
@@ -904,7 +1021,7 @@ def evaluate_parts(model, indptr, indices, features_own, comm, nodes, labels_own
         if lab.dim() != 1 or lab.shape[0] != n_own:
             raise ValueError("labels_own must hold one label per own node of the rank ([%d])" % n_own)
     logits = full_inference_parts(model, indptr, indices, features_own, comm, owner=owner, nodes=nodes,
-                                  chunk_rows=chunk_rows, _check=check)
+                                  chunk_rows=chunk_rows, _check=check, _zero_padded=_zero_padded)
     N = np.asarray(indptr).shape[0] - 1
     rg = rank_graph(indptr, indices, owner_table(N, comm.world, owner), comm.world, comm.rank)
     mine = nodes[rg.owner[nodes] == comm.rank] if nodes.size else nodes

@@ -43,8 +43,9 @@ class Trainer(object):
         feature_dtype: "float32" (default), "float16" or "bfloat16": the element type of the resident feature table
         `self.feat`.  The rows (float32 or float16 numpy arrays, torch tensors of any of the three types) are stored as
         torch.as_tensor(rows).to(dtype), round to nearest even; a 16-bit table is half the HBM, no float32 copy of it
-        stays on the device, and the deepest layer's forward reads it in place and upcasts in registers (exact), so the
-        model is bitwise the one trained on the stored table upcast to float32.  A 16-bit table whose width
+        is ever made on the device, and the deepest layer's forward -- and the first layer of evaluate() / predict() --
+        reads it in place and upcasts in registers (exact), so the model is bitwise the one trained on the stored table
+        upcast to float32.  A 16-bit table whose width
         is no multiple of 4 is stored with zero-padded rows; `self.feat` is then the [n_own, F] view of it."""
         if feature_dtype not in aggr.FEATURE_DTYPES:
             raise ValueError("feature_dtype must be one of %s, not %r" % (", ".join(aggr.FEATURE_DTYPES), feature_dtype))
@@ -111,7 +112,9 @@ class Trainer(object):
         if f_own.shape[0] != self.n_own or l_own.shape[0] != self.n_own:
             raise ValueError("features / labels do not cover the rank's %d nodes" % self.n_own)
         F = f_own.shape[1] if feat_dim is None else feat_dim
-        if fdt != torch.float32 and f_own.shape[1] % 4:
+        # whether self.feat is a view of rows stored zero-padded to a multiple of 4 (what lets inference read it in place)
+        self._feat_padded = bool(fdt != torch.float32 and f_own.shape[1] % 4)
+        if self._feat_padded:
             # the readers of a 16-bit table load whole quads of a row (8 bytes): a width that is no multiple of 4 is stored
             # with its rows padded to one (zeros), self.feat being the [n_own, F] view of it
             wide = torch.zeros((self.n_own, (f_own.shape[1] + 3) // 4 * 4), dtype=fdt)
@@ -408,6 +411,10 @@ class Trainer(object):
                 "part, each with its own rows); this rank path trainer has none")
         return self.model, self.eng.indptr, self.eng.indices, self.feat
 
+    def _infer_kw(self, nodes, chunk_rows):
+        from . import infer
+        return {"nodes": nodes, "chunk_rows": chunk_rows or infer.CHUNK_ROWS, "_zero_padded": self._feat_padded}
+
     def predict(self, nodes=None, chunk_rows=None):
         """float32 logits of the current weights by full-neighbour inference, enqueued on the training stream after every
         step already enqueued.  It neither submits to the engine nor draws random numbers nor touches the optimizer
@@ -415,11 +422,10 @@ class Trainer(object):
         Rank path: collective, every rank calls it with the same nodes; the logits of the rank's own nodes among `nodes`
         in `nodes` order, the rows owns(nodes) marks (cslicer.infer.full_inference_parts)."""
         from . import infer
-        args = self._infer_args()
-        chunk_rows = chunk_rows or infer.CHUNK_ROWS
+        args, kw = self._infer_args(), self._infer_kw(nodes, chunk_rows)
         if self.rank_path:
-            return infer.full_inference_parts(*args, self.comm, owner=self.owner, nodes=nodes, chunk_rows=chunk_rows)
-        return infer.full_inference(*args, nodes=nodes, chunk_rows=chunk_rows)
+            return infer.full_inference_parts(*args, self.comm, owner=self.owner, **kw)
+        return infer.full_inference(*args, **kw)
 
     def owns(self, nodes):
         """bool mask over `nodes`: the nodes this rank owns, i.e. the rows predict(nodes) returns on the rank path"""
@@ -431,11 +437,11 @@ class Trainer(object):
         trainer's labels) by full-neighbour inference; see predict().  Rank path: collective, the same dict on every
         rank (cslicer.infer.evaluate_parts)."""
         from . import infer
-        args = self._infer_args()
-        chunk_rows = chunk_rows or infer.CHUNK_ROWS
+        args, kw = self._infer_args(), self._infer_kw(nodes, chunk_rows)
         if self.rank_path:
-            return infer.evaluate_parts(*args, self.comm, nodes, self.labels, owner=self.owner, chunk_rows=chunk_rows)
-        return infer.evaluate(*args, nodes=nodes, labels=self.labels, chunk_rows=chunk_rows)
+            del kw["nodes"]
+            return infer.evaluate_parts(*args, self.comm, nodes, self.labels, owner=self.owner, **kw)
+        return infer.evaluate(*args, labels=self.labels, **kw)
 
     def close(self):
         from . import infer

@@ -7,6 +7,10 @@
 // column q of a 64 / G-float4 column tile), and each lane keeps U independent row loads in flight per step: G * U edges of
 // the item are read at once.  The groups' sums are combined by a fixed xor butterfly, the hub partials in part order:
 // no atomics, every result is bitwise reproducible.
+//
+// The GraphSAGE kernels are templated on the element type E of the table they gather (csrc/feat_elem.h): the first layer
+// reads a float16 / bfloat16 feature table in place (include/cslicer_infer16.h), a lane loading four elements (8 bytes)
+// and upcasting them in registers; everything after the load is the float32 code.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -14,6 +18,8 @@
 
 #include "cslicer_hip.h"
 #include "cslicer_infer.h"
+#include "cslicer_infer16.h"
+#include "feat_elem.h"
 
 namespace {
 
@@ -40,12 +46,13 @@ __device__ __forceinline__ float elu1(const float v) { return v > 0.f ? v : expm
 // ---------------------------------------------------------------- GraphSAGE
 
 // the end of a row: aggregate-first writes the operand [x[v] | mean], project-first act(x[v, :W) + mean + bias)
-__device__ __forceinline__ void sage_finish(const float* __restrict__ x, long long ldx, int W, int proj,
+template <typename E>
+__device__ __forceinline__ void sage_finish(const E* __restrict__ x, long long ldx, int W, int proj,
                                             const float* __restrict__ bias, int relu, float* __restrict__ out, long long ldo,
                                             long long k, int row, int deg, int c4, float4 acc) {
   const float d = (float)(deg > 0 ? deg : 1);
   acc.x /= d, acc.y /= d, acc.z /= d, acc.w /= d;
-  const float4 self = ld4(x + (long long)row * ldx + 4 * c4);
+  const float4 self = feat::Elem<E>::up(feat::Elem<E>::ld(x + (long long)row * ldx + 4 * c4));
   if (!proj) {
     st4(out + k * ldo + 4 * c4, self);
     st4(out + k * ldo + W + 4 * c4, acc);
@@ -58,10 +65,10 @@ __device__ __forceinline__ void sage_finish(const float* __restrict__ x, long lo
   st4(out + k * ldo + 4 * c4, y);
 }
 
-template <int G>
+template <int G, typename E = float>
 __global__ __launch_bounds__(BLK) void k_infer_sage(const int* __restrict__ indptr, const int* __restrict__ indices,
                                                     const int4* __restrict__ items, long long n_items, long long pos0,
-                                                    long long part0, const float* __restrict__ x, long long ldx, int W,
+                                                    long long part0, const E* __restrict__ x, long long ldx, int W,
                                                     int proj, const float* __restrict__ bias, int relu,
                                                     float* __restrict__ partial, float* __restrict__ out, long long ldo) {
   constexpr int LG = 64 / G;
@@ -82,15 +89,15 @@ __global__ __launch_bounds__(BLK) void k_infer_sage(const int* __restrict__ indp
       const int nb = min(64, e1 - eb);
       const int mine = lane < nb ? indices[eb + lane] : 0;     // 64 edges' sources, one coalesced load
       for (int j = 0; j < nb; j += G * U) {
-        float4 v[U];
+        typename feat::Elem<E>::Raw v[U];                      // (a 16-bit table: 8 bytes a load, upcast when added)
 #pragma unroll
         for (int u = 0; u < U; u++) {
           const int jj = j + u * G + g;
           const int src = __shfl(mine, jj & 63);
-          v[u] = (on && jj < nb) ? ld4(x + (long long)src * ldx + noff + 4 * c4) : f4zero();
+          v[u] = (on && jj < nb) ? feat::Elem<E>::ld(x + (long long)src * ldx + noff + 4 * c4) : feat::Elem<E>::zero();
         }
 #pragma unroll
-        for (int u = 0; u < U; u++) add4(acc, v[u]);
+        for (int u = 0; u < U; u++) add4(acc, feat::Elem<E>::up(v[u]));
       }
     }
 #pragma unroll
@@ -105,9 +112,10 @@ __global__ __launch_bounds__(BLK) void k_infer_sage(const int* __restrict__ indp
 }
 
 // one wave per hub row: its partials added in part order, then the row's end
+template <typename E = float>
 __global__ __launch_bounds__(BLK) void k_infer_sage_hubs(const int* __restrict__ indptr, const int4* __restrict__ hubs,
                                                          long long n_hubs, long long pos0, long long part0,
-                                                         const float* __restrict__ x, long long ldx, int W, int proj,
+                                                         const E* __restrict__ x, long long ldx, int W, int proj,
                                                          const float* __restrict__ bias, int relu,
                                                          const float* __restrict__ partial, float* __restrict__ out,
                                                          long long ldo) {
@@ -269,6 +277,19 @@ __global__ __launch_bounds__(BLK) void k_infer_gat_hubs(const int4* __restrict__
   if (last) gat_head_mean(stage, H, D, n_cls, out, ldo, (long long)hub.y - pos0, lane);
 }
 
+// ---------------------------------------------------------------- a 16-bit table's rows as a float32 GEMM operand
+
+// dst[k, 0:H) = float32(src[k, 0:H)) for n consecutive rows: 1 << lg lanes per row (lane q the quads q, q + 2^lg, ...),
+// an 8-byte load and a 16-byte store per quad
+template <typename E>
+__global__ __launch_bounds__(BLK) void k_upcast_rows(const E* __restrict__ src, long long lds, long long n,
+                                                     float* __restrict__ dst, long long ldd, int H4, int lg) {
+  const long long k = ((long long)blockIdx.x * BLK + threadIdx.x) >> lg;
+  if (k >= n) return;
+  for (int c4 = threadIdx.x & ((1 << lg) - 1); c4 < H4; c4 += 1 << lg)
+    st4(dst + k * ldd + 4 * c4, feat::Elem<E>::up(feat::Elem<E>::ld(src + k * lds + 4 * c4)));
+}
+
 // ---------------------------------------------------------------- evaluation head
 
 __global__ __launch_bounds__(BLK) void k_infer_eval_rows(const float* __restrict__ L, long long ld, long long n, int C,
@@ -355,6 +376,52 @@ bool plan_ok(const int32_t* indptr, const int32_t* indices, const int32_t* items
     default: hipLaunchKernelGGL(KERNEL<16>, dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break;            \
   }
 
+#define LAUNCH_G_E(G, E, KERNEL, grid, ...)                                                                     \
+  switch (G) {                                                                                                \
+    case 1: hipLaunchKernelGGL((KERNEL<1, E>), dim3(grid), dim3(BLK), 0, st, __VA_ARGS__); break;              \
+    case 2: hipLaunchKernelGGL((KERNEL<2, E>), dim3(grid), dim3(BLK), 0, st, __VA_ARGS__); break;              \
+    case 4: hipLaunchKernelGGL((KERNEL<4, E>), dim3(grid), dim3(BLK), 0, st, __VA_ARGS__); break;              \
+    case 8: hipLaunchKernelGGL((KERNEL<8, E>), dim3(grid), dim3(BLK), 0, st, __VA_ARGS__); break;              \
+    default: hipLaunchKernelGGL((KERNEL<16, E>), dim3(grid), dim3(BLK), 0, st, __VA_ARGS__); break;            \
+  }
+
+// what csl_infer_sage_f32 and csl_infer_sage_x16 check alike (everything but the table itself)
+bool sage_args_ok(const int32_t* indptr, const int32_t* indices, const int32_t* items, int64_t n_items,
+                  const int32_t* hubs, int64_t n_hubs, int64_t pos0, int64_t part0, int64_t ldx, int32_t W, int32_t proj,
+                  const void* partial, int64_t ldo) {
+  if (!plan_ok(indptr, indices, items, n_items, hubs, n_hubs, pos0, part0, partial)) return false;
+  return !(W < 4 || W % 4 != 0 || ldx % 4 != 0 || ldo % 4 != 0 || ldx < (proj ? 2 * (int64_t)W : W) ||
+           ldo < (proj ? W : 2 * (int64_t)W));
+}
+
+// the two launches of a GraphSAGE layer call over a table of element type E (arguments checked by the caller)
+template <typename E>
+int sage_launch(const int32_t* indptr, const int32_t* indices, const int32_t* items, int64_t n_items, const int32_t* hubs,
+                int64_t n_hubs, int64_t pos0, int64_t part0, const E* x, int64_t ldx, int32_t W, int32_t proj,
+                const float* bias, int32_t relu, float* partial, float* out, int64_t ldo, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const int G = groups_for(W / 4);
+  const int rl = relu != 0, pj = proj != 0;
+  if (n_items)
+    LAUNCH_G_E(G, E, k_infer_sage, blocks_of(n_items), indptr, indices, reinterpret_cast<const int4*>(items),
+               (long long)n_items, (long long)pos0, (long long)part0, x, (long long)ldx, (int)W, pj, bias, rl, partial, out,
+               (long long)ldo);
+  if (n_hubs)
+    hipLaunchKernelGGL(k_infer_sage_hubs<E>, dim3(blocks_of(n_hubs)), dim3(BLK), 0, st, indptr,
+                       reinterpret_cast<const int4*>(hubs), (long long)n_hubs, (long long)pos0, (long long)part0, x,
+                       (long long)ldx, (int)W, pj, bias, rl, partial, out, (long long)ldo);
+  return done();
+}
+
+template <typename E>
+void upcast_launch(const void* src, int64_t lds, int64_t n, float* dst, int64_t ldd, int32_t H, hipStream_t st) {
+  int lg = 2;                                                  // 4 .. 64 lanes per row: the quads of a row, rounded up
+  while (lg < 6 && (1 << lg) < H / 4) lg++;
+  const long long rpb = BLK >> lg;
+  hipLaunchKernelGGL(k_upcast_rows<E>, dim3((unsigned)((n + rpb - 1) / rpb)), dim3(BLK), 0, st, static_cast<const E*>(src),
+                     (long long)lds, (long long)n, dst, (long long)ldd, (int)(H / 4), lg);
+}
+
 }  // namespace
 
 extern "C" {
@@ -365,23 +432,41 @@ int csl_infer_sage_f32(const int32_t* indptr, const int32_t* indices, const int3
                        const int32_t* hubs, int64_t n_hubs, int64_t pos0, int64_t part0, const float* x, int64_t ldx,
                        int32_t W, int32_t proj, const float* bias, int32_t relu, float* partial, float* out, int64_t ldo,
                        void* stream) {
-  if (!plan_ok(indptr, indices, items, n_items, hubs, n_hubs, pos0, part0, partial)) return CSL_E_INVALID;
-  if (W < 4 || W % 4 != 0 || ldx % 4 != 0 || ldo % 4 != 0 || ldx < (proj ? 2 * (int64_t)W : W) ||
-      ldo < (proj ? W : 2 * (int64_t)W))
+  if (!sage_args_ok(indptr, indices, items, n_items, hubs, n_hubs, pos0, part0, ldx, W, proj, partial, ldo))
     return CSL_E_INVALID;
   if (n_items == 0 && n_hubs == 0) return CSL_OK;
   if (!x || !out || !al16(x) || !al16(out) || (bias && !al16(bias))) return CSL_E_INVALID;
-  hipStream_t st = (hipStream_t)stream;
-  const int G = groups_for(W / 4);
-  const int rl = relu != 0, pj = proj != 0;
-  if (n_items)
-    LAUNCH_G(G, k_infer_sage, blocks_of(n_items), 0, indptr, indices, reinterpret_cast<const int4*>(items),
-             (long long)n_items, (long long)pos0, (long long)part0, x, (long long)ldx, (int)W, pj, bias, rl, partial, out,
-             (long long)ldo);
-  if (n_hubs)
-    hipLaunchKernelGGL(k_infer_sage_hubs, dim3(blocks_of(n_hubs)), dim3(BLK), 0, st, indptr,
-                       reinterpret_cast<const int4*>(hubs), (long long)n_hubs, (long long)pos0, (long long)part0, x,
-                       (long long)ldx, (int)W, pj, bias, rl, partial, out, (long long)ldo);
+  return sage_launch<float>(indptr, indices, items, n_items, hubs, n_hubs, pos0, part0, x, ldx, W, proj, bias, relu, partial,
+                            out, ldo, stream);
+}
+
+int csl_infer_sage_x16(const int32_t* indptr, const int32_t* indices, const int32_t* items, int64_t n_items,
+                       const int32_t* hubs, int64_t n_hubs, int64_t pos0, int64_t part0, const void* x, int32_t kind,
+                       int64_t ldx, int32_t W, int32_t proj, const float* bias, int32_t relu, float* partial, float* out,
+                       int64_t ldo, void* stream) {
+  if (!feat::table_ok(x, kind, ldx) || proj != 0) return CSL_E_INVALID;
+  if (!sage_args_ok(indptr, indices, items, n_items, hubs, n_hubs, pos0, part0, ldx, W, 0, partial, ldo))
+    return CSL_E_INVALID;
+  if (n_items == 0 && n_hubs == 0) return CSL_OK;
+  if (!out || !al16(out) || (bias && !al16(bias))) return CSL_E_INVALID;
+  if (kind == CSL_FEAT_F16)
+    return sage_launch(indptr, indices, items, n_items, hubs, n_hubs, pos0, part0, static_cast<const feat::f16*>(x), ldx, W,
+                       0, bias, relu, partial, out, ldo, stream);
+  return sage_launch(indptr, indices, items, n_items, hubs, n_hubs, pos0, part0, static_cast<const feat::bf16*>(x), ldx, W,
+                     0, bias, relu, partial, out, ldo, stream);
+}
+
+int csl_upcast_rows_x16(const void* src, int32_t kind, int64_t lds, int64_t n, float* dst, int64_t ldd, int32_t H,
+                        void* stream) {
+  if (!feat::table_ok(src, kind, lds) || H < 4 || H % 4 != 0 || lds < H || ldd < H || ldd % 4 != 0 || n < 0 ||
+      n >= (1ll << 31))
+    return CSL_E_INVALID;
+  if (n == 0) return CSL_OK;
+  if (!dst || !al16(dst)) return CSL_E_INVALID;
+  if (kind == CSL_FEAT_F16)
+    upcast_launch<feat::f16>(src, lds, n, dst, ldd, H, (hipStream_t)stream);
+  else
+    upcast_launch<feat::bf16>(src, lds, n, dst, ldd, H, (hipStream_t)stream);
   return done();
 }
 

@@ -10,6 +10,9 @@
 // G groups of 64 / (R G) lanes walk the row's column tiles.  Every lane loads the source index of its own edge, so a
 // slot needs no cross-lane index broadcast.  The caller passes R = 1: packing was measured slower at every width
 // (a slot's narrower tiles walk its edges once per tile).  No atomics anywhere.
+//
+// The GraphSAGE kernels that read the layer's input table (k_sage_part its rows, k_sage_merge the self row) are
+// templated on its element type (csrc/feat_elem.h, include/cslicer_infer16.h), as csrc/infer.hip's are.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -17,7 +20,9 @@
 
 #include "cslicer_hip.h"
 #include "cslicer_infer.h"
+#include "cslicer_infer16.h"
 #include "cslicer_infer_parts.h"
+#include "feat_elem.h"
 
 namespace {
 
@@ -69,12 +74,13 @@ __device__ __forceinline__ void lse_merge_hub(float& m, float& s, float4& n, con
   m = M;
 }
 
-__device__ __forceinline__ void sage_finish(const float* __restrict__ x, long long ldx, int W, int proj,
+template <typename E>
+__device__ __forceinline__ void sage_finish(const E* __restrict__ x, long long ldx, int W, int proj,
                                             const float* __restrict__ bias, int relu, float* __restrict__ out, long long ldo,
                                             long long k, int row, int deg, int c4, float4 acc) {
   const float d = (float)(deg > 0 ? deg : 1);
   acc.x /= d, acc.y /= d, acc.z /= d, acc.w /= d;
-  const float4 self = ld4(x + (long long)row * ldx + 4 * c4);
+  const float4 self = feat::Elem<E>::up(feat::Elem<E>::ld(x + (long long)row * ldx + 4 * c4));
   if (!proj) {
     st4(out + k * ldo + 4 * c4, self);
     st4(out + k * ldo + W + 4 * c4, acc);
@@ -132,10 +138,10 @@ __device__ __forceinline__ Slot slot_item(const int* __restrict__ indptr, const 
 
 // ---------------------------------------------------------------- GraphSAGE
 
-template <int G, int R>
+template <int G, int R, typename E = float>
 __global__ __launch_bounds__(BLK) void k_sage_part(const int* __restrict__ indptr, const int* __restrict__ indices,
                                                    const int4* __restrict__ items, long long n_items, long long pos0,
-                                                   long long part0, const float* __restrict__ y, long long ldy, int W,
+                                                   long long part0, const E* __restrict__ y, long long ldy, int W,
                                                    float* __restrict__ partial, float* __restrict__ send) {
   constexpr int SL = 64 / R, LG = SL / G, T = G * U < 64 ? G * U : 64;
   const int lane = threadIdx.x & 63, sl = lane % SL, g = sl / LG, q = sl % LG;
@@ -146,16 +152,16 @@ __global__ __launch_bounds__(BLK) void k_sage_part(const int* __restrict__ indpt
     const bool on = c4 < W4;
     float4 acc = f4zero();
     for (int j = 0; j < it.n; j += T) {
-      float4 v[U];
+      typename feat::Elem<E>::Raw v[U];
 #pragma unroll
       for (int u = 0; u < U; u++) {
         const int jj = j + u * G + g;
         const bool ok = on && u * G + g < T && jj < it.n;
         const int src = ok ? indices[it.e0 + jj] : 0;
-        v[u] = ok ? ld4(y + (long long)src * ldy + 4 * c4) : f4zero();
+        v[u] = ok ? feat::Elem<E>::ld(y + (long long)src * ldy + 4 * c4) : feat::Elem<E>::zero();
       }
 #pragma unroll
-      for (int u = 0; u < U; u++) add4(acc, v[u]);
+      for (int u = 0; u < U; u++) add4(acc, feat::Elem<E>::up(v[u]));
     }
 #pragma unroll
     for (int d = LG; d < SL; d <<= 1) add4(acc, shfl_xor4(acc, d));
@@ -192,9 +198,9 @@ __global__ __launch_bounds__(BLK) void k_sage_part_hubs(const int4* __restrict__
 }
 
 // G destinations per wave, 64 / G lanes each: the received partials in list order, then the row's end
-template <int G>
+template <int G, typename E = float>
 __global__ __launch_bounds__(BLK) void k_sage_merge(const int2* __restrict__ dst, const int* __restrict__ lists, long long n,
-                                                    int P, const float* __restrict__ recv, const float* __restrict__ x,
+                                                    int P, const float* __restrict__ recv, const E* __restrict__ x,
                                                     long long ldx, int W, int proj, const float* __restrict__ bias, int relu,
                                                     float* __restrict__ out, long long ldo) {
   constexpr int LG = 64 / G;
@@ -376,14 +382,72 @@ bool merge_ok(const int32_t* lists, int64_t n, int32_t P, const float* recv) {
     default: hipLaunchKernelGGL((KERNEL<16, 1>), dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break;          \
   }
 
-#define LAUNCH_G(G, KERNEL, grid, ...)                                                                          \
-  switch (G) {                                                                                                \
-    case 1: hipLaunchKernelGGL(KERNEL<1>, dim3(grid), dim3(BLK), 0, st, __VA_ARGS__); break;                   \
-    case 2: hipLaunchKernelGGL(KERNEL<2>, dim3(grid), dim3(BLK), 0, st, __VA_ARGS__); break;                   \
-    case 4: hipLaunchKernelGGL(KERNEL<4>, dim3(grid), dim3(BLK), 0, st, __VA_ARGS__); break;                   \
-    case 8: hipLaunchKernelGGL(KERNEL<8>, dim3(grid), dim3(BLK), 0, st, __VA_ARGS__); break;                   \
-    default: hipLaunchKernelGGL(KERNEL<16>, dim3(grid), dim3(BLK), 0, st, __VA_ARGS__); break;                 \
+// the same for a kernel with an element type: KERNEL<G, R, E>
+#define LAUNCH_GR_E(G, R, E, KERNEL, grid, shmem, ...)                                                            \
+  switch (G * 8 + R) {                                                                                          \
+    case 1 * 8 + 1: hipLaunchKernelGGL((KERNEL<1, 1, E>), dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break; \
+    case 1 * 8 + 2: hipLaunchKernelGGL((KERNEL<1, 2, E>), dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break; \
+    case 1 * 8 + 4: hipLaunchKernelGGL((KERNEL<1, 4, E>), dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break; \
+    case 2 * 8 + 1: hipLaunchKernelGGL((KERNEL<2, 1, E>), dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break; \
+    case 2 * 8 + 2: hipLaunchKernelGGL((KERNEL<2, 2, E>), dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break; \
+    case 2 * 8 + 4: hipLaunchKernelGGL((KERNEL<2, 4, E>), dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break; \
+    case 4 * 8 + 1: hipLaunchKernelGGL((KERNEL<4, 1, E>), dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break; \
+    case 4 * 8 + 2: hipLaunchKernelGGL((KERNEL<4, 2, E>), dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break; \
+    case 4 * 8 + 4: hipLaunchKernelGGL((KERNEL<4, 4, E>), dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break; \
+    case 8 * 8 + 1: hipLaunchKernelGGL((KERNEL<8, 1, E>), dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break; \
+    case 8 * 8 + 2: hipLaunchKernelGGL((KERNEL<8, 2, E>), dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break; \
+    default: hipLaunchKernelGGL((KERNEL<16, 1, E>), dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break;       \
   }
+
+#define LAUNCH_G_E(G, E, KERNEL, grid, ...)                                                                     \
+  switch (G) {                                                                                                \
+    case 1: hipLaunchKernelGGL((KERNEL<1, E>), dim3(grid), dim3(BLK), 0, st, __VA_ARGS__); break;              \
+    case 2: hipLaunchKernelGGL((KERNEL<2, E>), dim3(grid), dim3(BLK), 0, st, __VA_ARGS__); break;              \
+    case 4: hipLaunchKernelGGL((KERNEL<4, E>), dim3(grid), dim3(BLK), 0, st, __VA_ARGS__); break;              \
+    case 8: hipLaunchKernelGGL((KERNEL<8, E>), dim3(grid), dim3(BLK), 0, st, __VA_ARGS__); break;              \
+    default: hipLaunchKernelGGL((KERNEL<16, E>), dim3(grid), dim3(BLK), 0, st, __VA_ARGS__); break;            \
+  }
+
+// what the float32 and the 16-bit entry point of a GraphSAGE kernel check alike (everything but the table itself), and
+// their launches over a table of element type E
+bool sage_part_ok(const int32_t* indptr, const int32_t* indices, const int32_t* items, int64_t n_items,
+                  const int32_t* hubs, int64_t n_hubs, int64_t pos0, int64_t part0, int64_t ldy, int32_t W, int32_t pack,
+                  const void* partial) {
+  if (!plan_ok(indptr, indices, items, n_items, hubs, n_hubs, pos0, part0, partial)) return false;
+  return !(W < 4 || W % 4 != 0 || ldy % 4 != 0 || ldy < W || pack < 1);
+}
+
+template <typename E>
+int sage_part_launch(const int32_t* indptr, const int32_t* indices, const int32_t* items, int64_t n_items,
+                     const int32_t* hubs, int64_t n_hubs, int64_t pos0, int64_t part0, const E* y, int64_t ldy, int32_t W,
+                     int32_t pack, float* partial, float* send, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const int G = groups_for(W / 4), R = pack_for(G, pack);
+  if (n_items)
+    LAUNCH_GR_E(G, R, E, k_sage_part, blocks_of(n_items, R), 0, indptr, indices, reinterpret_cast<const int4*>(items),
+              (long long)n_items, (long long)pos0, (long long)part0, y, (long long)ldy, (int)W, partial, send);
+  if (n_hubs)
+    hipLaunchKernelGGL(k_sage_part_hubs, dim3(blocks_of(n_hubs)), dim3(BLK), 0, st, reinterpret_cast<const int4*>(hubs),
+                       (long long)n_hubs, (long long)pos0, (long long)part0, (int)W, partial, send);
+  return done();
+}
+
+bool sage_merge_ok(const int32_t* lists, int64_t n, int32_t P, const float* recv, int64_t ldx, int32_t W, int32_t proj,
+                   int64_t ldo) {
+  if (!merge_ok(lists, n, P, recv)) return false;
+  return !(W < 4 || W % 4 != 0 || ldx % 4 != 0 || ldo % 4 != 0 || ldx < W || ldo < (proj ? W : 2 * (int64_t)W));
+}
+
+template <typename E>
+int sage_merge_launch(const int32_t* dst, const int32_t* lists, int64_t n, int32_t P, const float* recv, const E* x,
+                      int64_t ldx, int32_t W, int32_t proj, const float* bias, int32_t relu, float* out, int64_t ldo,
+                      void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const int G = groups_for(W / 4);
+  LAUNCH_G_E(G, E, k_sage_merge, blocks_of(n, G), reinterpret_cast<const int2*>(dst), lists, (long long)n, (int)P, recv, x,
+           (long long)ldx, (int)W, proj != 0, bias, relu != 0, out, (long long)ldo);
+  return done();
+}
 
 }  // namespace
 
@@ -392,35 +456,49 @@ extern "C" {
 int csl_infer_sage_part_f32(const int32_t* indptr, const int32_t* indices, const int32_t* items, int64_t n_items,
                             const int32_t* hubs, int64_t n_hubs, int64_t pos0, int64_t part0, const float* y, int64_t ldy,
                             int32_t W, int32_t pack, float* partial, float* send, void* stream) {
-  if (!plan_ok(indptr, indices, items, n_items, hubs, n_hubs, pos0, part0, partial)) return CSL_E_INVALID;
-  if (W < 4 || W % 4 != 0 || ldy % 4 != 0 || ldy < W || pack < 1) return CSL_E_INVALID;
+  if (!sage_part_ok(indptr, indices, items, n_items, hubs, n_hubs, pos0, part0, ldy, W, pack, partial)) return CSL_E_INVALID;
   if (n_items == 0 && n_hubs == 0) return CSL_OK;
   if (!y || !send || !al16(y) || !al16(send)) return CSL_E_INVALID;
-  hipStream_t st = (hipStream_t)stream;
-  const int G = groups_for(W / 4), R = pack_for(G, pack);
-  if (n_items)
-    LAUNCH_GR(G, R, k_sage_part, blocks_of(n_items, R), 0, indptr, indices, reinterpret_cast<const int4*>(items),
-              (long long)n_items, (long long)pos0, (long long)part0, y, (long long)ldy, (int)W, partial, send);
-  if (n_hubs)
-    hipLaunchKernelGGL(k_sage_part_hubs, dim3(blocks_of(n_hubs)), dim3(BLK), 0, st, reinterpret_cast<const int4*>(hubs),
-                       (long long)n_hubs, (long long)pos0, (long long)part0, (int)W, partial, send);
-  return done();
+  return sage_part_launch<float>(indptr, indices, items, n_items, hubs, n_hubs, pos0, part0, y, ldy, W, pack, partial, send,
+                                 stream);
+}
+
+int csl_infer_sage_part_x16(const int32_t* indptr, const int32_t* indices, const int32_t* items, int64_t n_items,
+                            const int32_t* hubs, int64_t n_hubs, int64_t pos0, int64_t part0, const void* y, int32_t kind,
+                            int64_t ldy, int32_t W, int32_t pack, float* partial, float* send, void* stream) {
+  if (!feat::table_ok(y, kind, ldy)) return CSL_E_INVALID;
+  if (!sage_part_ok(indptr, indices, items, n_items, hubs, n_hubs, pos0, part0, ldy, W, pack, partial)) return CSL_E_INVALID;
+  if (n_items == 0 && n_hubs == 0) return CSL_OK;
+  if (!send || !al16(send)) return CSL_E_INVALID;
+  if (kind == CSL_FEAT_F16)
+    return sage_part_launch(indptr, indices, items, n_items, hubs, n_hubs, pos0, part0, static_cast<const feat::f16*>(y),
+                            ldy, W, pack, partial, send, stream);
+  return sage_part_launch(indptr, indices, items, n_items, hubs, n_hubs, pos0, part0, static_cast<const feat::bf16*>(y), ldy,
+                          W, pack, partial, send, stream);
 }
 
 int csl_infer_sage_merge_f32(const int32_t* dst, const int32_t* lists, int64_t n, int32_t P, const float* recv,
                              const float* x, int64_t ldx, int32_t W, int32_t proj, const float* bias, int32_t relu,
                              float* out, int64_t ldo, void* stream) {
-  if (!merge_ok(lists, n, P, recv)) return CSL_E_INVALID;
-  if (W < 4 || W % 4 != 0 || ldx % 4 != 0 || ldo % 4 != 0 || ldx < W || ldo < (proj ? W : 2 * (int64_t)W))
-    return CSL_E_INVALID;
+  if (!sage_merge_ok(lists, n, P, recv, ldx, W, proj, ldo)) return CSL_E_INVALID;
   if (n == 0) return CSL_OK;
   if (!dst || (reinterpret_cast<uintptr_t>(dst) & 7u) || !x || !out || !al16(x) || !al16(out) || (bias && !al16(bias)))
     return CSL_E_INVALID;
-  hipStream_t st = (hipStream_t)stream;
-  const int G = groups_for(W / 4);
-  LAUNCH_G(G, k_sage_merge, blocks_of(n, G), reinterpret_cast<const int2*>(dst), lists, (long long)n, (int)P, recv, x,
-           (long long)ldx, (int)W, proj != 0, bias, relu != 0, out, (long long)ldo);
-  return done();
+  return sage_merge_launch<float>(dst, lists, n, P, recv, x, ldx, W, proj, bias, relu, out, ldo, stream);
+}
+
+int csl_infer_sage_merge_x16(const int32_t* dst, const int32_t* lists, int64_t n, int32_t P, const float* recv,
+                             const void* x, int32_t kind, int64_t ldx, int32_t W, int32_t proj, const float* bias,
+                             int32_t relu, float* out, int64_t ldo, void* stream) {
+  if (!feat::table_ok(x, kind, ldx) || proj != 0) return CSL_E_INVALID;
+  if (!sage_merge_ok(lists, n, P, recv, ldx, W, 0, ldo)) return CSL_E_INVALID;
+  if (n == 0) return CSL_OK;
+  if (!dst || (reinterpret_cast<uintptr_t>(dst) & 7u) || !out || !al16(out) || (bias && !al16(bias))) return CSL_E_INVALID;
+  if (kind == CSL_FEAT_F16)
+    return sage_merge_launch(dst, lists, n, P, recv, static_cast<const feat::f16*>(x), ldx, W, 0, bias, relu, out, ldo,
+                             stream);
+  return sage_merge_launch(dst, lists, n, P, recv, static_cast<const feat::bf16*>(x), ldx, W, 0, bias, relu, out, ldo,
+                           stream);
 }
 
 int csl_infer_gat_part_f32(const int32_t* indptr, const int32_t* indices, const int32_t* items, int64_t n_items,

@@ -3,10 +3,17 @@
 after a warm-up, median and spread of repeated runs), the algorithmic bytes they gather and write, and the fraction of
 8 TB/s that is; then the whole inference call.
 
-    python profiles/infer_bench.py [--reps 7] [--out FILE]
+    python profiles/infer_bench.py [--reps 7] [--out FILE] [--feature-dtype float32,float16,bfloat16]
 
-Algorithmic bytes of a layer's aggregation (every row counted once per use, fp32, padded widths):
-  SAGE aggregate first (w = input width):  E w 4 (neighbour rows) + N w 4 (own row) + N 2w 4 (operand written)
+--feature-dtype: the element types of the feature table, one pass each in the same run (default float32 alone).  Only a
+model's first layer reads the table, so a 16-bit pass times that layer -- GraphSAGE's aggregate-first kernels on the table
+in place (csl_infer_sage_x16), the attention model's first projection (per-chunk upcast + GEMM against the float32 GEMM
+in place) and the upcast kernel alone over the whole table -- then the whole call, and the rise of torch's allocated
+bytes over it.
+
+Algorithmic bytes of a layer's aggregation (every row counted once per use, padded widths; e = 4, or 2 where the rows
+gathered are those of a 16-bit feature table):
+  SAGE aggregate first (w = input width):  E w e (neighbour rows) + N w e (own row) + N 2w 4 (operand written)
   SAGE project first   (w = output width): E w 4 (neighbour half of P) + N w 4 (own half) + N w 4 (output written)
   GAT                  (C = H D):          E (C + H) 4 (z and el rows) + N (C + H) 4 (er, output written)
 """
@@ -41,11 +48,27 @@ def timed(fn, reps):
     return float(np.median(ts)), float(min(ts)), float(max(ts))
 
 
+def peak_rise(fn):
+    """bytes by which torch's allocations rise over one call"""
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_allocated()
+    fn()
+    torch.cuda.synchronize()
+    return torch.cuda.max_memory_allocated() - base
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--feature-dtype", default="float32",
+                    help="comma-separated element types of the feature table (float32, float16, bfloat16), one pass each")
     a = ap.parse_args()
+    dtypes = a.feature_dtype.split(",")
+    for d in dtypes:
+        if d not in l0.FEATURE_DTYPES:
+            ap.error("--feature-dtype: %r is not one of %s" % (d, ", ".join(l0.FEATURE_DTYPES)))
     dev = torch.device("cuda", 0)
     n, d, F, C = l0.PRESETS["products-like"]
     t0 = time.time()
@@ -54,13 +77,14 @@ def main():
     E = g.n_edges
     lines = ["products-like: N %d, E %d (self loops removed), max degree %d, hub rows (> %d edges) %d, graph + plan %.1f s"
              % (g.N, E, int(np.diff(g.host_indptr).max()), infer.SEG, g.all_rows.plan["hubs"].shape[0], time.time() - t0)]
-    feats = torch.rand((n, F), device=dev)
+    feats32 = torch.rand((n, F), device=dev)
     res = {"graph": {"N": g.N, "E": E}, "models": {}}
     torch.manual_seed(0)
     models = {"sage": splitgnn.DistSAGEModel(F, 256, C, n_layers=3).to(dev),
               "gat": splitgnn.DistGATModel(F, 32, C, heads=8, n_layers=3).to(dev)}
     chunk = infer.CHUNK_ROWS
-    for name, model in models.items():
+    feats = feats32
+    for name, model in (models.items() if "float32" in dtypes else ()):
         layers = []
         with torch.no_grad():
             h = feats
@@ -113,12 +137,76 @@ def main():
         lines.append("%-5s whole full_inference (all nodes): %.1f ms (min %.1f, max %.1f)" % (name, tw[0] * 1e3, tw[1] * 1e3,
                                                                                             tw[2] * 1e3))
         res["models"][name] = {"layers": layers, "total_s": tw[0], "total_min_s": tw[1], "total_max_s": tw[2]}
+        if len(dtypes) > 1:
+            first_layer_f32(name, model, feats, g, indptr, indices, chunk, a.reps, lines, res)
+    for fd in dtypes:                                       # (after the float32 pass: its figures are the comparison)
+        if fd != "float32":
+            first_layer_16(fd, feats32.to(getattr(torch, fd)), g, models, indptr, indices, chunk, a.reps, lines, res)
     txt = "\n".join(lines)
     print(txt)
     print(json.dumps(res))
     if a.out:
         with open(a.out, "w") as f:
             f.write(txt + "\n" + json.dumps(res) + "\n")
+
+
+def first_projection(model, h, g, chunk):
+    """the attention model's first projection z = h W^T over every row, as _gat_layer runs it: chunk by chunk, a 16-bit
+    table's rows upcast into one buffer first (the preset's widths are multiples of 4: the weight needs no padding)"""
+    wz = model.convs[0].fc.weight.detach()
+    z = torch.empty((g.N, wz.shape[0]), device=h.device)
+    return lambda: infer._project_rows(h, wz, z, chunk)
+
+
+def first_layer_f32(name, model, feats, g, indptr, indices, chunk, reps, lines, res):
+    """what first_layer_16 times, on the float32 table in place: the figures a 16-bit pass is compared with"""
+    rec = res["models"][name]
+    if name == "gat":
+        tp = timed(first_projection(model, feats, g, chunk), reps)
+        lines.append("gat   float32  layer 0 projection z = h W^T (GEMM on the table in place) %.3f ms (min %.3f, max %.3f of %d)"
+                     % (tp[0] * 1e3, tp[1] * 1e3, tp[2] * 1e3, reps))
+        rec["projection_s"] = tp
+    rise = peak_rise(lambda: infer.full_inference(model, indptr, indices, feats))
+    lines.append("%-5s float32  whole full_inference: torch's allocated bytes rise by %.1f MB (table %.1f MB, in place)"
+                 % (name, rise / 1e6, feats.numel() * 4 / 1e6))
+    rec["peak_rise_bytes"] = rise
+
+
+def first_layer_16(fd, feats, g, models, indptr, indices, chunk, reps, lines, res):
+    """one pass over a 16-bit table: the first layer's readers, the whole calls"""
+    dev = feats.device
+    E, F = g.n_edges, feats.shape[1]
+    out = res.setdefault(fd, {})
+    cat = torch.empty((chunk, 2 * F), device=dev)
+    tk = timed(lambda: infer.sage_rows(g, g.all_rows, feats, feats.stride(0), F, False, None, False,
+                                       lambda k0, k1: cat[:k1 - k0], chunk), reps)
+    byt = (E * F + g.N * F) * 2 + g.N * 2 * F * 4
+    lines.append("sage  %-8s layer 0 %d -> 256 aggregate first, table in place  aggregation %.3f ms (min %.3f, max %.3f of %d), "
+                 "%.2f GB, %.2f TB/s = %.0f %% of 8 TB/s" % (fd, F, tk[0] * 1e3, tk[1] * 1e3, tk[2] * 1e3, reps, byt / 1e9,
+                                                            byt / tk[0] / 1e12, 100 * byt / tk[0] / PEAK))
+    out["sage_layer0"] = {"kernel_s": tk[0], "min_s": tk[1], "max_s": tk[2], "bytes": byt}
+    del cat
+    tp = timed(first_projection(models["gat"], feats, g, chunk), reps)
+    lines.append("gat   %-8s layer 0 projection z = h W^T (per-chunk upcast + GEMM)         %.3f ms (min %.3f, max %.3f of %d)"
+                 % (fd, tp[0] * 1e3, tp[1] * 1e3, tp[2] * 1e3, reps))
+    rows = infer._RowChunks(feats, chunk)
+
+    def upcast():
+        for r0 in range(0, g.N, chunk):
+            rows(r0, min(g.N, r0 + chunk))
+    tu = timed(upcast, reps)
+    ub = g.N * F * 6
+    lines.append("      %-8s csl_upcast_rows_x16 over the whole table, chunk by chunk       %.3f ms (min %.3f, max %.3f of %d), "
+                 "%.2f GB, %.2f TB/s" % (fd, tu[0] * 1e3, tu[1] * 1e3, tu[2] * 1e3, reps, ub / 1e9, ub / tu[0] / 1e12))
+    out["gat_projection_s"], out["upcast_s"] = tp, tu
+    del rows
+    for name, model in models.items():
+        tw = timed(lambda model=model: infer.full_inference(model, indptr, indices, feats), max(3, reps // 2))
+        rise = peak_rise(lambda model=model: infer.full_inference(model, indptr, indices, feats))
+        lines.append("%-5s %-8s whole full_inference (all nodes): %.1f ms (min %.1f, max %.1f); torch's allocated bytes rise "
+                     "by %.1f MB (table %.1f MB, in place)" % (name, fd, tw[0] * 1e3, tw[1] * 1e3, tw[2] * 1e3, rise / 1e6,
+                                                              feats.numel() * 2 / 1e6))
+        out[name] = {"total_s": tw[0], "total_min_s": tw[1], "total_max_s": tw[2], "peak_rise_bytes": rise}
 
 
 if __name__ == "__main__":
