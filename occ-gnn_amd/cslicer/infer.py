@@ -25,6 +25,7 @@ the library GEMM reads the table (GraphSAGE project-first, the attention model's
 upcast into one reusable float32 buffer first.  Both upcasts are exact and everything behind them is the float32 code, so
 the logits are bitwise those of the same call on the table upcast to float32 -- without ever holding that copy.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -62,6 +63,11 @@ def _r4(x):
 def _kind(t):
     """None for a float32 table, the element kind (CSL_FEAT_F16 / CSL_FEAT_BF16) of a 16-bit one"""
     return None if t.dtype == torch.float32 else aggr.FEAT_KINDS[t.dtype]
+
+
+def _node_ids(nodes):
+    """a list of node ids (array, list or tensor) as a contiguous int64 [n] host array"""
+    return np.ascontiguousarray(np.asarray(nodes.cpu() if torch.is_tensor(nodes) else nodes).astype(np.int64).reshape(-1))
 
 
 # ------------------------------------------------------------------ graph and work list (host)
@@ -126,15 +132,21 @@ def build_plan(indptr, rows=None, seg=SEG):
             "hub_pos": hp.astype(np.int64), "n": n, "n_parts": int(part_first[-1])}
 
 
+# a chunk of output positions [k0, k1): its items [i0, i1), hubs [h0, h1) and partial rows part0 .. part0 + n_parts
+Chunk = collections.namedtuple("Chunk", "k0 k1 i0 i1 h0 h1 part0 n_parts")
+# the same over the sub-rows [s0, s1) a rank sends, with its own destinations [o0, o1) and receive rows [r0, r1)
+PartsChunk = collections.namedtuple("PartsChunk", "s0 s1 i0 i1 h0 h1 part0 n_parts o0 o1 r0 r1")
+
+
 def plan_chunks(plan, chunk_rows):
-    """[(k0, k1, i0, i1, h0, h1, part0, n_parts)] per chunk of `chunk_rows` output positions"""
+    """[Chunk] per chunk of `chunk_rows` output positions"""
     out = []
     n = plan["n"]
     for k0 in range(0, n, chunk_rows):
         k1 = min(n, k0 + chunk_rows)
         h0, h1 = (int(x) for x in np.searchsorted(plan["hub_pos"], [k0, k1]))
         p0, p1 = int(plan["part_first"][k0]), int(plan["part_first"][k1])
-        out.append((k0, k1, int(plan["item_first"][k0]), int(plan["item_first"][k1]), h0, h1, p0, p1 - p0))
+        out.append(Chunk(k0, k1, int(plan["item_first"][k0]), int(plan["item_first"][k1]), h0, h1, p0, p1 - p0))
     return out
 
 
@@ -264,35 +276,58 @@ def _partial(n_rows, width, device):
     return torch.empty((max(n_rows, 1), width), dtype=torch.float32, device=device)
 
 
+def _list_args(indptr, indices, items, hubs, c, pos0):
+    """the leading arguments of every kernel that walks a work list: the CSR, chunk c's slice of items and hubs, the
+    chunk's first position and first partial row"""
+    return (_ptr(indptr), _ptr(indices), _ptr(items, 4 * c.i0), c.i1 - c.i0,
+            _ptr(hubs, 4 * c.h0) if c.h1 > c.h0 else C.c_void_p(0), c.h1 - c.h0, pos0, c.part0)
+
+
 def sage_rows(g, dplan, x, ldx, W, proj, bias, relu, out, chunk_rows, scratch=None):
     """csl_infer_sage_f32 over every chunk of the plan; out row k of the plan is out[k] (proj) -- for the aggregate-first
     form `out` is a callable (k0, k1) -> the chunk's operand buffer, and `scratch` is called after each chunk.  x may be
     a 16-bit feature table (aggregate-first only): csl_infer_sage_x16 reads it in place."""
     twins, kind = aggr._twins("infer_sage"), _kind(x)
     st = aggr._stream()
-    for (k0, k1, i0, i1, h0, h1, p0, npart) in dplan.chunks(chunk_rows):
-        part = _partial(npart, W, x.device) if npart else None
-        dst = out(k0, k1) if callable(out) else out[k0:k1]
-        aggr._table_call(twins, kind,
-                         (_ptr(g.indptr), _ptr(g.indices), _ptr(dplan.items, 4 * i0), i1 - i0,
-                          _ptr(dplan.hubs, 4 * h0) if h1 > h0 else C.c_void_p(0), h1 - h0, k0, p0, _ptr(x)),
+    for c in dplan.chunks(chunk_rows):
+        part = _partial(c.n_parts, W, x.device) if c.n_parts else None
+        dst = out(c.k0, c.k1) if callable(out) else out[c.k0:c.k1]
+        aggr._table_call(twins, kind, _list_args(g.indptr, g.indices, dplan.items, dplan.hubs, c, c.k0) + (_ptr(x),),
                          (ldx, W, int(proj), _ptr(bias), int(relu), _ptr(part), _ptr(dst), dst.stride(0), st), _chk)
         if scratch is not None:
-            scratch(k0, k1, dst)
+            scratch(c.k0, c.k1, dst)
 
 
 def gat_rows(g, dplan, z, el, er, H, D, slope, bias, last, n_cls, out, chunk_rows):
     L = _lib()
     st = aggr._stream()
     pld = int(L.csl_infer_gat_partial_ld(H, D))
-    for (k0, k1, i0, i1, h0, h1, p0, npart) in dplan.chunks(chunk_rows):
-        part = _partial(npart, pld, z.device) if npart else None
-        dst = out[k0:k1]
-        _chk(L.csl_infer_gat_f32(_ptr(g.indptr), _ptr(g.indices), _ptr(dplan.items, 4 * i0), i1 - i0,
-                                 _ptr(dplan.hubs, 4 * h0) if h1 > h0 else C.c_void_p(0), h1 - h0, k0, p0, _ptr(z), _ptr(el),
+    for c in dplan.chunks(chunk_rows):
+        part = _partial(c.n_parts, pld, z.device) if c.n_parts else None
+        dst = out[c.k0:c.k1]
+        _chk(L.csl_infer_gat_f32(*_list_args(g.indptr, g.indices, dplan.items, dplan.hubs, c, c.k0), _ptr(z), _ptr(el),
                                  _ptr(er), H, D, float(slope), _ptr(bias), int(last), int(n_cls), _ptr(part), _ptr(dst),
                                  dst.stride(0), st),
              "csl_infer_gat_f32")
+
+
+def _sage_operands(conv, hp, dev):
+    """(agg_first, weight, bias) of a DistSageConv on an [*, hp] input table (hp % 4 == 0).  Aggregate first (out >= in):
+    the Linear's weight [out, 2 hp] over the operand [h[v] | mean h[u]], its halves at columns 0 and hp, and its bias.
+    Project first: [W_self; W_neigh] as [2 op, hp] (op = round4(out)), the halves at rows 0 and op, and the bias padded
+    to op.  Every padding entry is zero."""
+    W, b = conv.fc.weight.detach().float(), conv.fc.bias.detach().float()
+    out_w, in_w = W.shape[0], W.shape[1] // 2
+    if out_w >= in_w:
+        wc = torch.zeros((out_w, 2 * hp), dtype=torch.float32, device=dev)
+        wc[:, :in_w], wc[:, hp:hp + in_w] = W[:, :in_w], W[:, in_w:]
+        return True, wc, b
+    op = _r4(out_w)
+    wp = torch.zeros((2 * op, hp), dtype=torch.float32, device=dev)
+    wp[:out_w, :in_w], wp[op:op + out_w, :in_w] = W[:, :in_w], W[:, in_w:]
+    bp = torch.zeros((op,), dtype=torch.float32, device=dev)
+    bp[:out_w] = b
+    return False, wp, bp
 
 
 def _sage_layer(g, dplan, h, conv, relu, chunk_rows):
@@ -300,39 +335,34 @@ def _sage_layer(g, dplan, h, conv, relu, chunk_rows):
     first layer's feature table in its stored 16-bit type, row stride h.stride(0)).  Aggregate first when out >= in,
     project first otherwise.  Returns the [rows, round4(out)] float32 table (padding columns zero)."""
     dev = h.device
-    W, b = conv.fc.weight.detach().float(), conv.fc.bias.detach().float()
-    out_w, in_w = W.shape[0], W.shape[1] // 2
+    agg_first, w, b = _sage_operands(conv, h.shape[1], dev)
+    out_w = conv.fc.weight.shape[0]
     hp, op = h.shape[1], _r4(out_w)
     n_rows = dplan.plan["n"]
-    if out_w >= in_w:
+    if agg_first:
         # (a) [h[v] | mean h[u]] chunk by chunk, then the Linear with its bias / ReLU epilogue into the output table
-        wc = torch.zeros((out_w, 2 * hp), dtype=torch.float32, device=dev)
-        wc[:, :in_w], wc[:, hp:hp + in_w] = W[:, :in_w], W[:, in_w:]
         y = torch.zeros((n_rows, op), dtype=torch.float32, device=dev)
         cat = torch.empty((min(chunk_rows, max(n_rows, 1)), 2 * hp), dtype=torch.float32, device=dev)
         sage_rows(g, dplan, h, h.stride(0), hp, False, None, False, lambda k0, k1: cat[:k1 - k0], chunk_rows,
-                  scratch=lambda k0, k1, c: _gemm_into(y[k0:k1, :out_w], c, wc, b, relu))
+                  scratch=lambda k0, k1, c: _gemm_into(y[k0:k1, :out_w], c, w, b, relu))
         return y
     # (b) P = h . [W_self; W_neigh]^T once for every node, then act(P[v, :out] + mean P[u, out:] + b) in one pass
-    wp = torch.zeros((2 * op, hp), dtype=torch.float32, device=dev)
-    wp[:out_w, :in_w], wp[op:op + out_w, :in_w] = W[:, :in_w], W[:, in_w:]
-    bp = torch.zeros((op,), dtype=torch.float32, device=dev)
-    bp[:out_w] = b
     P = torch.empty((g.N, 2 * op), dtype=torch.float32, device=dev)
-    _project_rows(h, wp, P, chunk_rows)
+    _project_rows(h, w, P, chunk_rows)
     y = torch.empty((n_rows, op), dtype=torch.float32, device=dev)
-    sage_rows(g, dplan, P, 2 * op, op, True, bp, relu, y, chunk_rows)
+    sage_rows(g, dplan, P, 2 * op, op, True, b, relu, y, chunk_rows)
     return y
 
 
-def _gat_layer(g, dplan, h, in_map, conv, last, n_cls, chunk_rows):
-    """One DistGATConv over the rows of `dplan`; h: [N, hp] table whose logical column c sits at in_map[c] (float32, or
-    the first layer's feature table in its stored 16-bit type: its rows reach the GEMMs through _RowChunks).  Returns
-    (table, its column map): hidden layers [N, H * round4(D)], the last [rows, n_cls]."""
-    dev = h.device
+_GatOps = collections.namedtuple("_GatOps", "H D Dp wz al ar bz vl vr cmap")
+
+
+def _gat_operands(conv, in_map, hp, dev):
+    """The operands of a DistGATConv on an [*, hp] input table whose logical column c sits at in_map[c], every head
+    padded to Dp = round4(D) columns with zeros: wz [H Dp, hp], al / ar / bz [H, Dp], cmap (where the layer's logical
+    output column sits in its [*, H Dp] table), and for Dp > 256 vl / vr [H, hp] (else None)."""
     H, D = conv.H, conv.D
     Dp = _r4(D)
-    hp = h.shape[1]
     Wt = conv.fc.weight.detach().float().view(H, D, -1)
     wz = torch.zeros((H, Dp, hp), dtype=torch.float32, device=dev)
     wz[:, :D, in_map] = Wt
@@ -341,37 +371,47 @@ def _gat_layer(g, dplan, h, in_map, conv, last, n_cls, chunk_rows):
     ar = torch.zeros((H, Dp), dtype=torch.float32, device=dev)
     bz = torch.zeros((H, Dp), dtype=torch.float32, device=dev)
     al[:, :D], ar[:, :D], bz[:, :D] = conv.attn_l.detach(), conv.attn_r.detach(), conv.bias.detach().view(H, D)
-    Cz = H * Dp
-    z = torch.empty((g.N, Cz), dtype=torch.float32, device=dev)
-    el = torch.empty((g.N, H), dtype=torch.float32, device=dev)
-    er = torch.empty((g.N, H), dtype=torch.float32, device=dev)
-    AL = aggr._lib()
+    vl = vr = None
     if Dp > 256:
         # csl_gat_logits_fwd_f32 holds a head in one wave (D <= 256): wider heads take el = h . (W_h^T a_l[h]) and er
         # likewise, two [N, H] GEMMs on the layer's input (the same logits, summed in another order)
         wv = wz.view(H, Dp, hp)
         vl, vr = torch.einsum("hdf,hd->hf", wv, al).contiguous(), torch.einsum("hdf,hd->hf", wv, ar).contiguous()
-    rows = _RowChunks(h, chunk_rows)
-    for r0 in range(0, g.N, chunk_rows):
-        r1 = min(g.N, r0 + chunk_rows)
-        hc = rows(r0, r1)
-        _gemm_into(z[r0:r1], hc, wz)
-        if Dp > 256:
-            _gemm_into(el[r0:r1], hc, vl)
-            _gemm_into(er[r0:r1], hc, vr)
-        else:
-            _chk(AL.csl_gat_logits_fwd_f32(_ptr(z[r0]), _ptr(al), _ptr(ar), r1 - r0, H, Dp, _ptr(el[r0]), _ptr(er[r0]),
-                                           aggr._stream()), "csl_gat_logits_fwd_f32")
-    rows = hc = None      # (the upcast buffer of a 16-bit table goes back before the layer's outputs are allocated)
-    n_rows = dplan.plan["n"]
-    if last:
-        out = torch.empty((n_rows, n_cls), dtype=torch.float32, device=dev)
-        gat_rows(g, dplan, z, el, er, H, Dp, conv.slope, bz, True, n_cls, out, chunk_rows)
-        return out, None
-    out = torch.empty((n_rows, Cz), dtype=torch.float32, device=dev)
-    gat_rows(g, dplan, z, el, er, H, Dp, conv.slope, bz, False, 0, out, chunk_rows)
     cmap = (torch.arange(H, device=dev)[:, None] * Dp + torch.arange(D, device=dev)[None, :]).reshape(-1)
-    return out, cmap
+    return _GatOps(H, D, Dp, wz, al, ar, bz, vl, vr, cmap)
+
+
+def _gat_project(h, ops, n_rows, chunk_rows):
+    """(z [n_rows, H Dp], el, er [max(n_rows, 1), H]) of the rows of h, chunk by chunk.  (The upcast buffer of a 16-bit
+    table goes back on return: before the caller allocates the layer's outputs or exchange buffers.)"""
+    dev, H, Dp = h.device, ops.H, ops.Dp
+    z = torch.empty((n_rows, H * Dp), dtype=torch.float32, device=dev)
+    el = torch.empty((max(n_rows, 1), H), dtype=torch.float32, device=dev)
+    er = torch.empty((max(n_rows, 1), H), dtype=torch.float32, device=dev)
+    AL, st = aggr._lib(), aggr._stream()
+    rows = _RowChunks(h, chunk_rows)
+    for r0 in range(0, n_rows, chunk_rows):
+        r1 = min(n_rows, r0 + chunk_rows)
+        hc = rows(r0, r1)
+        _gemm_into(z[r0:r1], hc, ops.wz)
+        if ops.vl is not None:
+            _gemm_into(el[r0:r1], hc, ops.vl)
+            _gemm_into(er[r0:r1], hc, ops.vr)
+        else:
+            _chk(AL.csl_gat_logits_fwd_f32(_ptr(z[r0]), _ptr(ops.al), _ptr(ops.ar), r1 - r0, H, Dp, _ptr(el[r0]),
+                                           _ptr(er[r0]), st), "csl_gat_logits_fwd_f32")
+    return z, el, er
+
+
+def _gat_layer(g, dplan, h, in_map, conv, last, n_cls, chunk_rows):
+    """One DistGATConv over the rows of `dplan`; h: [N, hp] table whose logical column c sits at in_map[c] (float32, or
+    the first layer's feature table in its stored 16-bit type: its rows reach the GEMMs through _RowChunks).  Returns
+    (table, its column map): hidden layers [N, H * round4(D)], the last [rows, n_cls]."""
+    ops = _gat_operands(conv, in_map, h.shape[1], h.device)
+    z, el, er = _gat_project(h, ops, g.N, chunk_rows)
+    out = torch.empty((dplan.plan["n"], n_cls if last else ops.H * ops.Dp), dtype=torch.float32, device=h.device)
+    gat_rows(g, dplan, z, el, er, ops.H, ops.Dp, conv.slope, ops.bz, last, n_cls if last else 0, out, chunk_rows)
+    return out, (None if last else ops.cmap)
 
 
 # ------------------------------------------------------------------ public interface
@@ -414,6 +454,29 @@ def _table16(features, rows, view, dtype, dev):
     return h
 
 
+def _first_table(features, rows, zero_padded, dev):
+    """How the first layer's input table [rows, round4(F)] comes about, decided before anything is allocated:
+    (make, feat_size, feat_copy, upload_bytes).  make() returns the table -- to be called once the memory check has
+    passed; feat_size: bytes per element of the feature table, feat_copy: whether a 16-bit device copy is made
+    (_need_bytes counts it), upload_bytes: those of the padded float32 device copy of a float32 input that cannot be
+    used in place (a device tensor with F % 4 == 0 and dense rows can)."""
+    F = features.shape[1]
+    dt16 = _feat16_dtype(features)
+    if dt16 is not None:
+        view = _feat16_in_place(features, zero_padded)
+        return (lambda: _table16(features, rows, view, dt16, dev)), 2, view is None, 0
+    if (torch.is_tensor(features) and features.is_cuda and features.dtype == torch.float32 and F % 4 == 0
+            and features.stride(1) == 1 and features.stride(0) == F):
+        return (lambda: features), 4, False, 0
+
+    def upload():
+        h = torch.zeros((rows, _r4(F)), dtype=torch.float32, device=dev)
+        if rows:
+            h[:, :F] = torch.as_tensor(features).to(dev, torch.float32)
+        return h
+    return upload, 4, False, rows * _r4(F) * 4
+
+
 def _input_bytes(k, rows, width, chunk_rows, gemm_form, feat_size, feat_copy):
     """the bytes layer k's input table contributes: rows width 4 for a float32 table (every layer after the first, and
     a float32 feature table); for a 16-bit feature table (k == 0, feat_size == 2) rows width 2 only if a device copy of
@@ -451,11 +514,34 @@ def _need_bytes(model, N, n_out, F, chunk_rows, max_parts, feat_size=4, feat_cop
     return need
 
 
-def _check_memory(need, device):
+def _free_bytes(device):
     free, _ = torch.cuda.mem_get_info(device)
-    free += torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)   # torch's cached blocks
+    return free + torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)   # torch's cached blocks
+
+
+def _check_memory(need, device):
+    free = _free_bytes(device)
     if need > free:
         raise MemoryError("full_inference needs %d bytes of device memory, %d are free" % (need, free))
+
+
+def _check_model(model, who):
+    """what `who` (full_inference / full_inference_parts) refuses about its model before anything else"""
+    if not isinstance(model, (splitgnn.DistSAGEModel, splitgnn.DistGATModel)):
+        raise TypeError(who + " takes a DistSAGEModel or a DistGATModel")
+    if isinstance(model, splitgnn.DistGATModel) and model.convs[-1].H * _r4(model.convs[-1].D) > GAT_LAST_MAX_C:
+        raise ValueError("%s: the attention model's last layer has heads x classes (padded to 4) = %d > %d columns%s"
+                         % (who, model.convs[-1].H * _r4(model.convs[-1].D), GAT_LAST_MAX_C,
+                            "; its head mean stages a row in LDS" if who == "full_inference" else ""))
+
+
+def _class_columns(model, h):
+    """the last table without a GraphSAGE model's padding columns (the attention model's last layer writes none)"""
+    if isinstance(model, splitgnn.DistSAGEModel):
+        n_cls = model.convs[-1].fc.weight.shape[0]
+        if h.shape[1] != n_cls:
+            h = h[:, :n_cls].contiguous()
+    return h
 
 
 def full_inference(model, indptr, indices, features, nodes=None, chunk_rows=CHUNK_ROWS, _zero_padded=False):
@@ -472,12 +558,7 @@ def full_inference(model, indptr, indices, features, nodes=None, chunk_rows=CHUN
     except an attention model whose last layer has more than GAT_LAST_MAX_C = 4096 heads x padded-class columns
     (ValueError).  Before allocating, the device bytes it needs (tables, scratch and, on first use of a graph, the
     graph's CSR and work list) are checked against the free memory: MemoryError with both counts."""
-    if not isinstance(model, (splitgnn.DistSAGEModel, splitgnn.DistGATModel)):
-        raise TypeError("full_inference takes a DistSAGEModel or a DistGATModel")
-    if isinstance(model, splitgnn.DistGATModel) and model.convs[-1].H * _r4(model.convs[-1].D) > GAT_LAST_MAX_C:
-        raise ValueError("full_inference: the attention model's last layer has heads x classes (padded to 4) = %d > %d "
-                         "columns; its head mean stages a row in LDS" % (model.convs[-1].H * _r4(model.convs[-1].D),
-                                                                       GAT_LAST_MAX_C))
+    _check_model(model, "full_inference")
     chunk_rows = int(chunk_rows)
     if chunk_rows < 1:
         raise ValueError("chunk_rows must be positive")
@@ -490,28 +571,19 @@ def full_inference(model, indptr, indices, features, nodes=None, chunk_rows=CHUN
         if features.shape[0] != N:
             raise ValueError("features must have one row per node (%d), got %d" % (N, features.shape[0]))
         if nodes is not None:
-            nodes = np.asarray(nodes.cpu() if torch.is_tensor(nodes) else nodes).astype(np.int64).reshape(-1)
+            nodes = _node_ids(nodes)
             if nodes.size and (nodes.min() < 0 or nodes.max() >= N):
                 raise ValueError("nodes outside [0, %d)" % N)
         dlast = g.plan(nodes)
         n_out = dlast.plan["n"]
-        max_parts = max([c[7] for c in g.all_rows.chunks(chunk_rows)] + [c[7] for c in dlast.chunks(chunk_rows)] + [0])
-        dt16 = _feat16_dtype(features)
-        view = _feat16_in_place(features, _zero_padded) if dt16 is not None else None
-        need = _need_bytes(model, N, n_out, F, chunk_rows, max_parts, 4 if dt16 is None else 2, view is None)
+        max_parts = max([c.n_parts for c in g.all_rows.chunks(chunk_rows) + dlast.chunks(chunk_rows)] + [0])
+        first_table, feat_size, feat_copy, upload_bytes = _first_table(features, N, _zero_padded, dev)
+        need = _need_bytes(model, N, n_out, F, chunk_rows, max_parts, feat_size, feat_copy)
         need += (0 if g.uploaded() else g.device_bytes()) + (dlast.nbytes() if nodes is not None else 0)
-        upload = dt16 is None and not (torch.is_tensor(features) and features.is_cuda and features.dtype == torch.float32
-                                       and F % 4 == 0 and features.stride(1) == 1 and features.stride(0) == F)
-        _check_memory(need + (N * _r4(F) * 4 if upload else 0), dev)
+        _check_memory(need + upload_bytes, dev)
         g.upload()
         dlast.upload()
-        if dt16 is not None:
-            h = _table16(features, N, view, dt16, dev)
-        elif upload:
-            h = torch.zeros((N, _r4(F)), dtype=torch.float32, device=dev)
-            h[:, :F] = torch.as_tensor(features).to(dev, torch.float32)
-        else:
-            h = features
+        h = first_table()
         in_map = torch.arange(F, device=dev)
         L = len(model.convs)
         for k, conv in enumerate(model.convs):
@@ -521,11 +593,7 @@ def full_inference(model, indptr, indices, features, nodes=None, chunk_rows=CHUN
                 h = _sage_layer(g, dplan, h, conv, not last, chunk_rows)
             else:
                 h, in_map = _gat_layer(g, dplan, h, in_map, conv, last, model.n_classes, chunk_rows)
-        if isinstance(model, splitgnn.DistSAGEModel):
-            n_cls = model.convs[-1].fc.weight.shape[0]
-            if h.shape[1] != n_cls:
-                h = h[:, :n_cls].contiguous()
-        return h
+        return _class_columns(model, h)
 
 
 def eval_head(logits, labels):
@@ -546,7 +614,7 @@ def eval_head(logits, labels):
 def evaluate(model, indptr, indices, features, nodes, labels, chunk_rows=CHUNK_ROWS, _zero_padded=False):
     """{"accuracy", "loss", "n"} of the model on `nodes` by full-neighbour inference: argmax accuracy and mean
     cross-entropy.  labels: int [N], the label of every node of the graph (those of `nodes` are used)."""
-    nodes = np.asarray(nodes.cpu() if torch.is_tensor(nodes) else nodes).astype(np.int64).reshape(-1)
+    nodes = _node_ids(nodes)
     lab = torch.as_tensor(labels)
     if lab.dim() != 1 or lab.shape[0] != features.shape[0]:
         raise ValueError("labels must hold one label per node of the graph ([%d])" % features.shape[0])
@@ -684,17 +752,16 @@ class PartsPlan(object):
         self.dev = None
 
     def chunks(self):
-        """[(s0, s1, i0, i1, h0, h1, part0, n_parts, o0, o1, r0, r1)] per chunk: its sub-rows, items, hubs and parts,
-        own destinations and receive rows"""
+        """[PartsChunk] per chunk: its sub-rows, items, hubs and parts, own destinations and receive rows"""
         w = self.work
         out = []
         for c in range(self.n_chunks):
             s0, s1 = int(self.sub_first[c]), int(self.sub_first[c + 1])
             h0, h1 = (int(x) for x in np.searchsorted(w["hub_pos"], [s0, s1]))
             p0, p1 = int(w["part_first"][s0]), int(w["part_first"][s1])
-            out.append((s0, s1, int(w["item_first"][s0]), int(w["item_first"][s1]), h0, h1, p0, p1 - p0,
-                        int(self.own_first[c]), int(self.own_first[c + 1]), int(self.recv_first[c]),
-                        int(self.recv_first[c + 1])))
+            out.append(PartsChunk(s0, s1, int(w["item_first"][s0]), int(w["item_first"][s1]), h0, h1, p0, p1 - p0,
+                                  int(self.own_first[c]), int(self.own_first[c + 1]), int(self.recv_first[c]),
+                                  int(self.recv_first[c + 1])))
         return out
 
     def device_bytes(self, gat):
@@ -750,56 +817,49 @@ def _exchange(comm, recv, R, send, S, send_counts, recv_counts):
     comm.exchange_into(recv[:R], send[:S], [int(c) for c in send_counts], [int(c) for c in recv_counts])
 
 
+def _buffer_rows(pp):
+    """(send rows, receive rows, partial rows) of the largest chunk of a plan, each at least 1: a layer's buffers"""
+    ch = [PartsChunk(*c) for c in pp.chunks()]
+    return (max([c.s1 - c.s0 for c in ch] + [1]), max([c.r1 - c.r0 for c in ch] + [1]),
+            max([c.n_parts for c in ch] + [1]))
+
+
 def _sage_layer_parts(pp, dp, h, conv, relu, comm):
     """One DistSageConv over the rank's destinations of `pp`; h: [n_own, hp] own rows (float32, or the first layer's
     feature rows in their stored 16-bit type: the aggregate-first kernels read them in place, the projection through
     _RowChunks).  Returns [m, round4(out)]."""
-    L = _lib()
-    kind = _kind(h)
+    L, st, dev, kind = _lib(), aggr._stream(), h.device, _kind(h)
     part_twins, merge_twins = aggr._twins("infer_sage_part"), aggr._twins("infer_sage_merge")
-    st = aggr._stream()
-    dev = h.device
-    W, b = conv.fc.weight.detach().float(), conv.fc.bias.detach().float()
-    out_w, in_w = W.shape[0], W.shape[1] // 2
+    agg_first, w, b = _sage_operands(conv, h.shape[1], dev)
+    out_w = conv.fc.weight.shape[0]
     hp, op = h.shape[1], _r4(out_w)
-    chunks = pp.chunks()
-    agg_first = out_w >= in_w
     if agg_first:
-        wc = torch.zeros((out_w, 2 * hp), dtype=torch.float32, device=dev)
-        wc[:, :in_w], wc[:, hp:hp + in_w] = W[:, :in_w], W[:, in_w:]
         y = torch.zeros((pp.m, op), dtype=torch.float32, device=dev)
         cat = torch.empty((min(pp.chunk_rows, max(pp.m, 1)), 2 * hp), dtype=torch.float32, device=dev)
         Y, ldy, Wy = h, h.stride(0), hp
     else:
-        wp = torch.zeros((2 * op, hp), dtype=torch.float32, device=dev)
-        wp[:out_w, :in_w], wp[op:op + out_w, :in_w] = W[:, :in_w], W[:, in_w:]
-        bp = torch.zeros((op,), dtype=torch.float32, device=dev)
-        bp[:out_w] = b
         Y = torch.empty((h.shape[0], 2 * op), dtype=torch.float32, device=dev)
-        _project_rows(h, wp, Y, pp.chunk_rows)
+        _project_rows(h, w, Y, pp.chunk_rows)
         ldy, Wy = 2 * op, op
         y = torch.empty((pp.m, op), dtype=torch.float32, device=dev)
     pack = pp.pack(Wy)
-    S_max = max([c[1] - c[0] for c in chunks] + [1])
-    R_max = max([c[11] - c[10] for c in chunks] + [1])
+    S_max, R_max, parts = _buffer_rows(pp)
     send = torch.empty((S_max, Wy), dtype=torch.float32, device=dev)
     recv = torch.empty((R_max, Wy), dtype=torch.float32, device=dev)
-    part = _partial(max([c[7] for c in chunks] + [0]), Wy, dev)
-    for c, (s0, s1, i0, i1, h0, h1, p0, npart, o0, o1, r0, r1) in enumerate(chunks):
+    part = _partial(parts, Wy, dev)
+    for i, c in enumerate(pp.chunks()):
         # (Y is the layer's input table itself in the aggregate-first form, else the float32 projection)
         aggr._table_call(part_twins, kind if agg_first else None,
-                         (_ptr(dp["ip"]), _ptr(dp["ix"]), _ptr(dp["items"], 4 * i0), i1 - i0,
-                          _ptr(dp["hubs"], 4 * h0) if h1 > h0 else C.c_void_p(0), h1 - h0, s0, p0,
-                          _ptr(Y, 0 if agg_first else op)), (ldy, Wy, pack, _ptr(part), _ptr(send), st), _chk)
-        _exchange(comm, recv, r1 - r0, send, s1 - s0, pp.sub_counts[c], pp.own_counts[c])
+                         _list_args(dp["ip"], dp["ix"], dp["items"], dp["hubs"], c, c.s0)
+                         + (_ptr(Y, 0 if agg_first else op),), (ldy, Wy, pack, _ptr(part), _ptr(send), st), _chk)
+        _exchange(comm, recv, c.r1 - c.r0, send, c.s1 - c.s0, pp.sub_counts[i], pp.own_counts[i])
+        merge = (_ptr(dp["dst"], 2 * c.o0), _ptr(dp["ml"], pp.P * c.o0), c.o1 - c.o0, pp.P, _ptr(recv))
         if agg_first:
-            aggr._table_call(merge_twins, kind,
-                             (_ptr(dp["dst"], 2 * o0), _ptr(dp["ml"], pp.P * o0), o1 - o0, pp.P, _ptr(recv), _ptr(h)),
+            aggr._table_call(merge_twins, kind, merge + (_ptr(h),),
                              (h.stride(0), hp, 0, None, 0, _ptr(cat), 2 * hp, st), _chk)
-            _gemm_into(y[o0:o1, :out_w], cat[:o1 - o0], wc, b, relu)
+            _gemm_into(y[c.o0:c.o1, :out_w], cat[:c.o1 - c.o0], w, b, relu)
         else:
-            _chk(L.csl_infer_sage_merge_f32(_ptr(dp["dst"], 2 * o0), _ptr(dp["ml"], pp.P * o0), o1 - o0, pp.P, _ptr(recv),
-                                            _ptr(Y), 2 * op, op, 1, _ptr(bp), int(relu), _ptr(y, o0 * op), op, st),
+            _chk(L.csl_infer_sage_merge_f32(*merge, _ptr(Y), 2 * op, op, 1, _ptr(b), int(relu), _ptr(y, c.o0 * op), op, st),
                  "csl_infer_sage_merge_f32")
     return y
 
@@ -808,66 +868,30 @@ def _gat_layer_parts(pp, dp, h, in_map, conv, last, n_cls, comm):
     """One DistGATConv over the rank's destinations of `pp`; h: [n_own, hp] own rows whose logical column c sits at
     in_map[c] (float32, or the first layer's feature rows in their stored 16-bit type).  Returns (table, column map) as
     _gat_layer."""
-    L, AL = _lib(), aggr._lib()
-    st = aggr._stream()
-    dev = h.device
-    H, D = conv.H, conv.D
-    Dp = _r4(D)
-    hp = h.shape[1]
-    n_own = h.shape[0]
-    Wt = conv.fc.weight.detach().float().view(H, D, -1)
-    wz = torch.zeros((H, Dp, hp), dtype=torch.float32, device=dev)
-    wz[:, :D, in_map] = Wt
-    wz = wz.view(H * Dp, hp)
-    al = torch.zeros((H, Dp), dtype=torch.float32, device=dev)
-    ar = torch.zeros((H, Dp), dtype=torch.float32, device=dev)
-    bz = torch.zeros((H, Dp), dtype=torch.float32, device=dev)
-    al[:, :D], ar[:, :D], bz[:, :D] = conv.attn_l.detach(), conv.attn_r.detach(), conv.bias.detach().view(H, D)
-    Cz = H * Dp
-    z = torch.empty((n_own, Cz), dtype=torch.float32, device=dev)
-    el = torch.empty((max(n_own, 1), H), dtype=torch.float32, device=dev)
-    er = torch.empty((max(n_own, 1), H), dtype=torch.float32, device=dev)
-    if Dp > 256:
-        wv = wz.view(H, Dp, hp)
-        vl, vr = torch.einsum("hdf,hd->hf", wv, al).contiguous(), torch.einsum("hdf,hd->hf", wv, ar).contiguous()
-    rows = _RowChunks(h, pp.chunk_rows)
-    for r0 in range(0, n_own, pp.chunk_rows):
-        r1 = min(n_own, r0 + pp.chunk_rows)
-        hc = rows(r0, r1)
-        _gemm_into(z[r0:r1], hc, wz)
-        if Dp > 256:
-            _gemm_into(el[r0:r1], hc, vl)
-            _gemm_into(er[r0:r1], hc, vr)
-        else:
-            _chk(AL.csl_gat_logits_fwd_f32(_ptr(z[r0]), _ptr(al), _ptr(ar), r1 - r0, H, Dp, _ptr(el[r0]), _ptr(er[r0]),
-                                           st), "csl_gat_logits_fwd_f32")
-    rows = hc = None      # (the upcast buffer of a 16-bit table goes back before the exchange buffers are allocated)
+    L, st, dev = _lib(), aggr._stream(), h.device
+    ops = _gat_operands(conv, in_map, h.shape[1], dev)
+    H, Dp = ops.H, ops.Dp
+    z, el, er = _gat_project(h, ops, h.shape[0], pp.chunk_rows)
     pld = int(L.csl_infer_gat_partial_ld(H, Dp))
-    chunks = pp.chunks()
-    pack = pp.pack(Cz)
-    S_max = max([c[1] - c[0] for c in chunks] + [1])
-    R_max = max([c[11] - c[10] for c in chunks] + [1])
+    pack = pp.pack(H * Dp)
+    S_max, R_max, parts = _buffer_rows(pp)
     send = torch.empty((S_max, pld), dtype=torch.float32, device=dev)
     recv = torch.empty((R_max, pld), dtype=torch.float32, device=dev)
     er_in = torch.empty((S_max, H), dtype=torch.float32, device=dev)
-    part = _partial(max([c[7] for c in chunks] + [0]), pld, dev)
-    out = torch.empty((pp.m, n_cls if last else Cz), dtype=torch.float32, device=dev)
-    for c, (s0, s1, i0, i1, h0, h1, p0, npart, o0, o1, r0, r1) in enumerate(chunks):
+    part = _partial(parts, pld, dev)
+    out = torch.empty((pp.m, n_cls if last else H * Dp), dtype=torch.float32, device=dev)
+    for i, c in enumerate(pp.chunks()):
         # er of the owned destinations out to the ranks holding their neighbours (the partials' path, reversed)
-        er_out = er.index_select(0, dp["er_src"][r0:r1]) if r1 > r0 else er[:0]
-        _exchange(comm, er_in, s1 - s0, er_out, r1 - r0, pp.own_counts[c], pp.sub_counts[c])
-        _chk(L.csl_infer_gat_part_f32(_ptr(dp["ip"]), _ptr(dp["ix"]), _ptr(dp["items"], 4 * i0), i1 - i0,
-                                      _ptr(dp["hubs"], 4 * h0) if h1 > h0 else C.c_void_p(0), h1 - h0, s0, p0, _ptr(z),
+        er_out = er.index_select(0, dp["er_src"][c.r0:c.r1]) if c.r1 > c.r0 else er[:0]
+        _exchange(comm, er_in, c.s1 - c.s0, er_out, c.r1 - c.r0, pp.own_counts[i], pp.sub_counts[i])
+        _chk(L.csl_infer_gat_part_f32(*_list_args(dp["ip"], dp["ix"], dp["items"], dp["hubs"], c, c.s0), _ptr(z),
                                       _ptr(el), _ptr(er_in), H, Dp, float(conv.slope), pack, _ptr(part), _ptr(send), st),
              "csl_infer_gat_part_f32")
-        _exchange(comm, recv, r1 - r0, send, s1 - s0, pp.sub_counts[c], pp.own_counts[c])
-        dst = out[o0:o1]
-        _chk(L.csl_infer_gat_merge_f32(_ptr(dp["ml"], pp.P * o0), o1 - o0, pp.P, _ptr(recv), H, Dp, _ptr(bz), int(last),
-                                       int(n_cls), _ptr(dst), dst.stride(0), st), "csl_infer_gat_merge_f32")
-    if last:
-        return out, None
-    cmap = (torch.arange(H, device=dev)[:, None] * Dp + torch.arange(D, device=dev)[None, :]).reshape(-1)
-    return out, cmap
+        _exchange(comm, recv, c.r1 - c.r0, send, c.s1 - c.s0, pp.sub_counts[i], pp.own_counts[i])
+        dst = out[c.o0:c.o1]
+        _chk(L.csl_infer_gat_merge_f32(_ptr(dp["ml"], pp.P * c.o0), c.o1 - c.o0, pp.P, _ptr(recv), H, Dp, _ptr(ops.bz),
+                                       int(last), int(n_cls), _ptr(dst), dst.stride(0), st), "csl_infer_gat_merge_f32")
+    return out, (None if last else ops.cmap)
 
 
 def _need_bytes_parts(model, n_own, F, plans, feat_size=4, feat_copy=False):
@@ -875,13 +899,9 @@ def _need_bytes_parts(model, n_own, F, plans, feat_size=4, feat_copy=False):
     copies not included): as _need_bytes, over the rank's n_own rows"""
     hid, lastp = plans
     need, width = 0, _r4(F)
-
-    def chunk_max(pp, k):
-        return max([c[k + 1] - c[k] for c in pp.chunks()] + [1])
     for k, conv in enumerate(model.convs):
         pp = lastp if k + 1 == len(model.convs) else hid
-        S, R = chunk_max(pp, 0), chunk_max(pp, 10)
-        parts = max([c[7] for c in pp.chunks()] + [1])
+        S, R, parts = _buffer_rows(pp)
         if isinstance(model, splitgnn.DistSAGEModel):
             out_w, in_w = conv.fc.weight.shape[0], conv.fc.weight.shape[1] // 2
             op = _r4(out_w)
@@ -922,11 +942,7 @@ def full_inference_parts(model, indptr, indices, features_own, comm, owner=None,
     another rank's feature or hidden rows.  `nodes` is compared across ranks (length and a 64-bit hash: ValueError on
     every rank if they differ), and the device-memory check is agreed on: if one rank would raise MemoryError, every rank
     does, before the first exchange.  With one part the result is bitwise that of full_inference."""
-    if not isinstance(model, (splitgnn.DistSAGEModel, splitgnn.DistGATModel)):
-        raise TypeError("full_inference_parts takes a DistSAGEModel or a DistGATModel")
-    if isinstance(model, splitgnn.DistGATModel) and model.convs[-1].H * _r4(model.convs[-1].D) > GAT_LAST_MAX_C:
-        raise ValueError("full_inference_parts: the attention model's last layer has heads x classes (padded to 4) = %d > "
-                         "%d columns" % (model.convs[-1].H * _r4(model.convs[-1].D), GAT_LAST_MAX_C))
+    _check_model(model, "full_inference_parts")
     chunk_rows = int(chunk_rows)
     if chunk_rows < 1:
         raise ValueError("chunk_rows must be positive")
@@ -934,8 +950,7 @@ def full_inference_parts(model, indptr, indices, features_own, comm, owner=None,
     N = np.asarray(indptr).shape[0] - 1
     dev = features_own.device if torch.is_tensor(features_own) and features_own.is_cuda else comm.device
     if nodes is not None:
-        nodes = np.ascontiguousarray(np.asarray(nodes.cpu() if torch.is_tensor(nodes) else nodes).astype(np.int64)
-                                     .reshape(-1))
+        nodes = _node_ids(nodes)
     # arguments that could differ between ranks are agreed on before anything else, so that no rank is left waiting
     err = None
     try:
@@ -962,29 +977,15 @@ def full_inference_parts(model, indptr, indices, features_own, comm, owner=None,
         hid = rg.plan(chunk_rows)
         lastp = hid if nodes is None else rg.plan(chunk_rows, nodes)
         F = features_own.shape[1]
-        dt16 = _feat16_dtype(features_own)
-        view = _feat16_in_place(features_own, _zero_padded) if dt16 is not None else None
-        upload = dt16 is None and not (torch.is_tensor(features_own) and features_own.is_cuda
-                                       and features_own.dtype == torch.float32 and F % 4 == 0
-                                       and features_own.stride(1) == 1 and features_own.stride(0) == F)
-        need = _need_bytes_parts(model, n_own, F, (hid, lastp), 4 if dt16 is None else 2, view is None)
-        need += n_own * _r4(F) * 4 if upload else 0
+        first_table, feat_size, feat_copy, upload_bytes = _first_table(features_own, n_own, _zero_padded, dev)
+        need = _need_bytes_parts(model, n_own, F, (hid, lastp), feat_size, feat_copy) + upload_bytes
         need += (0 if hid.dev is not None else hid.device_bytes(gat)) + (lastp.device_bytes(gat) if lastp is not hid else 0)
-        free, _ = torch.cuda.mem_get_info(dev)
-        free += torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
-        short = [g for g in _gather(comm, [int(need), int(free)]) if g[0] > g[1]]
+        short = [g for g in _gather(comm, [int(need), int(_free_bytes(dev))]) if g[0] > g[1]]
         if short:
             raise MemoryError("full_inference_parts needs %d bytes of device memory on a rank where %d are free"
                               % (short[0][0], short[0][1]))
         dh, dl = hid.upload(dev, gat), lastp.upload(dev, gat)
-        if dt16 is not None:
-            h = _table16(features_own, n_own, view, dt16, dev)
-        elif upload:
-            h = torch.zeros((n_own, _r4(F)), dtype=torch.float32, device=dev)
-            if n_own:
-                h[:, :F] = torch.as_tensor(features_own).to(dev, torch.float32)
-        else:
-            h = features_own
+        h = first_table()
         in_map = torch.arange(F, device=dev)
         Lc = len(model.convs)
         for k, conv in enumerate(model.convs):
@@ -994,16 +995,12 @@ def full_inference_parts(model, indptr, indices, features_own, comm, owner=None,
                 h, in_map = _gat_layer_parts(pp, dp, h, in_map, conv, last, model.n_classes, comm)
             else:
                 h = _sage_layer_parts(pp, dp, h, conv, not last, comm)
-        if not gat:
-            n_cls = model.convs[-1].fc.weight.shape[0]
-            if h.shape[1] != n_cls:
-                h = h[:, :n_cls].contiguous()
-        return h
+        return _class_columns(model, h)
 
 
 def owns(N, P, rank, nodes, owner=None):
     """bool [len(nodes)]: which of `nodes` rank `rank` owns (the rows full_inference_parts returns on that rank)"""
-    nodes = np.asarray(nodes.cpu() if torch.is_tensor(nodes) else nodes).astype(np.int64).reshape(-1)
+    nodes = _node_ids(nodes)
     own = (nodes % P) if owner is None else np.asarray(owner)[nodes]
     return own == rank
 
@@ -1014,7 +1011,7 @@ def evaluate_parts(model, indptr, indices, features_own, comm, nodes, labels_own
     of the model on `nodes`, the same dict on every rank.  labels_own: int [n_own], the labels of the rank's own nodes in
     ascending node order.  Each rank scores its own nodes among `nodes`; the per-rank (correct, float64 loss sum, n) are
     all-gathered and added in rank order, so the result is reproducible bit for bit."""
-    nodes = np.ascontiguousarray(np.asarray(nodes.cpu() if torch.is_tensor(nodes) else nodes).astype(np.int64).reshape(-1))
+    nodes = _node_ids(nodes)
     lab = torch.as_tensor(labels_own)
 
     def check(n_own):

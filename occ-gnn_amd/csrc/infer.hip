@@ -11,59 +11,14 @@
 // The GraphSAGE kernels are templated on the element type E of the table they gather (csrc/feat_elem.h): the first layer
 // reads a float16 / bfloat16 feature table in place (include/cslicer_infer16.h), a lane loading four elements (8 bytes)
 // and upcasting them in registers; everything after the load is the float32 code.
-#include <hip/hip_runtime.h>
-
-#include <cmath>
-#include <cstdint>
-
-#include "cslicer_hip.h"
-#include "cslicer_infer.h"
-#include "cslicer_infer16.h"
-#include "feat_elem.h"
+//
+// The float4 helpers, the row ends (sage_finish, gat_finish, gat_head_mean, lse_merge) and the host helpers live in
+// csrc/infer_dev.h, shared with csrc/infer_parts.hip.
+#include "infer_dev.h"
 
 namespace {
 
-constexpr int BLK = 256;
-constexpr int WPB = BLK / 64;   // waves (items) per block
-constexpr int SEG = CSL_INFER_SEG;
-constexpr int U = 8;            // row loads in flight per lane and step
-constexpr int GAT_LAST_MAX_C = 4096;  // H * D of a last layer: its head mean stages a row per wave in LDS (64 KiB a block)
-constexpr long long GAT_MAX_C = 1ll << 24;  // H * D of a hidden layer (nothing staged; column indices stay int)
-
-__device__ __forceinline__ float4 f4zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, const float4 v) { *reinterpret_cast<float4*>(p) = v; }
-__device__ __forceinline__ void add4(float4& a, const float4 b) { a.x += b.x, a.y += b.y, a.z += b.z, a.w += b.w; }
-__device__ __forceinline__ void scale4(float4& a, const float s) { a.x *= s, a.y *= s, a.z *= s, a.w *= s; }
-__device__ __forceinline__ void fma4(float4& a, const float s, const float4 b) {
-  a.x += s * b.x, a.y += s * b.y, a.z += s * b.z, a.w += s * b.w;
-}
-__device__ __forceinline__ float4 shfl_xor4(const float4 v, const int d) {
-  return make_float4(__shfl_xor(v.x, d), __shfl_xor(v.y, d), __shfl_xor(v.z, d), __shfl_xor(v.w, d));
-}
-__device__ __forceinline__ float elu1(const float v) { return v > 0.f ? v : expm1f(v); }
-
 // ---------------------------------------------------------------- GraphSAGE
-
-// the end of a row: aggregate-first writes the operand [x[v] | mean], project-first act(x[v, :W) + mean + bias)
-template <typename E>
-__device__ __forceinline__ void sage_finish(const E* __restrict__ x, long long ldx, int W, int proj,
-                                            const float* __restrict__ bias, int relu, float* __restrict__ out, long long ldo,
-                                            long long k, int row, int deg, int c4, float4 acc) {
-  const float d = (float)(deg > 0 ? deg : 1);
-  acc.x /= d, acc.y /= d, acc.z /= d, acc.w /= d;
-  const float4 self = feat::Elem<E>::up(feat::Elem<E>::ld(x + (long long)row * ldx + 4 * c4));
-  if (!proj) {
-    st4(out + k * ldo + 4 * c4, self);
-    st4(out + k * ldo + W + 4 * c4, acc);
-    return;
-  }
-  float4 y = self;
-  add4(y, acc);
-  if (bias) add4(y, ld4(bias + 4 * c4));
-  if (relu) y.x = fmaxf(y.x, 0.f), y.y = fmaxf(y.y, 0.f), y.z = fmaxf(y.z, 0.f), y.w = fmaxf(y.w, 0.f);
-  st4(out + k * ldo + 4 * c4, y);
-}
 
 template <int G, typename E = float>
 __global__ __launch_bounds__(BLK) void k_infer_sage(const int* __restrict__ indptr, const int* __restrict__ indices,
@@ -142,41 +97,6 @@ __global__ __launch_bounds__(BLK) void k_infer_sage_hubs(const int* __restrict__
 }
 
 // ---------------------------------------------------------------- GAT
-
-// merge softmax state (m2, s2, n2) into (m, s, n)
-__device__ __forceinline__ void lse_merge(float& m, float& s, float4& n, const float m2, const float s2, const float4 n2) {
-  const float M = fmaxf(m, m2);
-  const float a = expf(m - M), b = expf(m2 - M);
-  s = s * a + s2 * b;
-  scale4(n, a);
-  fma4(n, b, n2);
-  m = M;
-}
-
-// the end of a row: hidden layers ELU(n / s + bias) in place of the output row; the last layer stages n / s + bias of the
-// row in the wave's LDS region (the head mean follows once every column tile is there)
-__device__ __forceinline__ void gat_finish(const float* __restrict__ bias, int last, float* __restrict__ out, long long ldo,
-                                           float* stage, long long k, int c4, float s, float4 n) {
-  float4 y = s > 0.f ? make_float4(n.x / s, n.y / s, n.z / s, n.w / s) : f4zero();
-  if (bias) add4(y, ld4(bias + 4 * c4));
-  if (last) {
-    st4(stage + 4 * c4, y);
-    return;
-  }
-  st4(out + k * ldo + 4 * c4, make_float4(elu1(y.x), elu1(y.y), elu1(y.z), elu1(y.w)));
-}
-
-__device__ __forceinline__ void gat_head_mean(const float* stage, int H, int D, int n_cls, float* __restrict__ out,
-                                              long long ldo, long long k, int lane) {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  for (int j = lane; j < n_cls; j += 64) {
-    float t = 0.f;
-    for (int h = 0; h < H; h++) t += stage[h * D + j];
-    out[k * ldo + j] = t / (float)H;
-  }
-}
 
 template <int G>
 __global__ __launch_bounds__(BLK) void k_infer_gat(const int* __restrict__ indptr, const int* __restrict__ indices,
@@ -346,50 +266,11 @@ __global__ __launch_bounds__(BLK) void k_infer_eval_sum(const long long* __restr
 
 // ---------------------------------------------------------------- host side
 
-bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-int done() { return hipGetLastError() == hipSuccess ? CSL_OK : CSL_E_HIP; }
-unsigned blocks_of(long long n) { return (unsigned)((n + WPB - 1) / WPB); }
-
-// G groups of 64 / G lanes: the smallest group that holds a column tile of min(C4, 64) float4s (at most 16 groups)
-int groups_for(int C4) {
-  int lg = 4;
-  while (lg < 64 && lg < C4) lg <<= 1;
-  return 64 / lg;
-}
-
-// the checks shared by both layer kernels: a plan slice that is there when it is used
-bool plan_ok(const int32_t* indptr, const int32_t* indices, const int32_t* items, int64_t n_items, const int32_t* hubs,
-             int64_t n_hubs, int64_t pos0, int64_t part0, const void* partial) {
-  if (n_items < 0 || n_hubs < 0 || pos0 < 0 || part0 < 0 || n_items >= (1ll << 31) * WPB || n_hubs >= (1ll << 31) * WPB)
-    return false;
-  if (n_items && (!indptr || !indices || !items || !al16(items))) return false;
-  if (n_hubs && (!indptr || !hubs || !al16(hubs) || !partial || !al16(partial))) return false;
-  return true;
-}
-
-#define LAUNCH_G(G, KERNEL, grid, shmem, ...)                                                                   \
-  switch (G) {                                                                                                \
-    case 1: hipLaunchKernelGGL(KERNEL<1>, dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break;              \
-    case 2: hipLaunchKernelGGL(KERNEL<2>, dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break;              \
-    case 4: hipLaunchKernelGGL(KERNEL<4>, dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break;              \
-    case 8: hipLaunchKernelGGL(KERNEL<8>, dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break;              \
-    default: hipLaunchKernelGGL(KERNEL<16>, dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break;            \
-  }
-
-#define LAUNCH_G_E(G, E, KERNEL, grid, ...)                                                                     \
-  switch (G) {                                                                                                \
-    case 1: hipLaunchKernelGGL((KERNEL<1, E>), dim3(grid), dim3(BLK), 0, st, __VA_ARGS__); break;              \
-    case 2: hipLaunchKernelGGL((KERNEL<2, E>), dim3(grid), dim3(BLK), 0, st, __VA_ARGS__); break;              \
-    case 4: hipLaunchKernelGGL((KERNEL<4, E>), dim3(grid), dim3(BLK), 0, st, __VA_ARGS__); break;              \
-    case 8: hipLaunchKernelGGL((KERNEL<8, E>), dim3(grid), dim3(BLK), 0, st, __VA_ARGS__); break;              \
-    default: hipLaunchKernelGGL((KERNEL<16, E>), dim3(grid), dim3(BLK), 0, st, __VA_ARGS__); break;            \
-  }
-
 // what csl_infer_sage_f32 and csl_infer_sage_x16 check alike (everything but the table itself)
 bool sage_args_ok(const int32_t* indptr, const int32_t* indices, const int32_t* items, int64_t n_items,
                   const int32_t* hubs, int64_t n_hubs, int64_t pos0, int64_t part0, int64_t ldx, int32_t W, int32_t proj,
                   const void* partial, int64_t ldo) {
-  if (!plan_ok(indptr, indices, items, n_items, hubs, n_hubs, pos0, part0, partial)) return false;
+  if (!plan_ok(indptr, indices, items, n_items, hubs, n_hubs, pos0, part0, partial, true)) return false;
   return !(W < 4 || W % 4 != 0 || ldx % 4 != 0 || ldo % 4 != 0 || ldx < (proj ? 2 * (int64_t)W : W) ||
            ldo < (proj ? W : 2 * (int64_t)W));
 }
@@ -403,9 +284,11 @@ int sage_launch(const int32_t* indptr, const int32_t* indices, const int32_t* it
   const int G = groups_for(W / 4);
   const int rl = relu != 0, pj = proj != 0;
   if (n_items)
-    LAUNCH_G_E(G, E, k_infer_sage, blocks_of(n_items), indptr, indices, reinterpret_cast<const int4*>(items),
-               (long long)n_items, (long long)pos0, (long long)part0, x, (long long)ldx, (int)W, pj, bias, rl, partial, out,
-               (long long)ldo);
+    with_groups(G, [&](auto g) {
+      hipLaunchKernelGGL((k_infer_sage<g(), E>), dim3(blocks_of(n_items)), dim3(BLK), 0, st, indptr, indices,
+                         reinterpret_cast<const int4*>(items), (long long)n_items, (long long)pos0, (long long)part0, x,
+                         (long long)ldx, (int)W, pj, bias, rl, partial, out, (long long)ldo);
+    });
   if (n_hubs)
     hipLaunchKernelGGL(k_infer_sage_hubs<E>, dim3(blocks_of(n_hubs)), dim3(BLK), 0, st, indptr,
                        reinterpret_cast<const int4*>(hubs), (long long)n_hubs, (long long)pos0, (long long)part0, x,
@@ -449,11 +332,11 @@ int csl_infer_sage_x16(const int32_t* indptr, const int32_t* indices, const int3
     return CSL_E_INVALID;
   if (n_items == 0 && n_hubs == 0) return CSL_OK;
   if (!out || !al16(out) || (bias && !al16(bias))) return CSL_E_INVALID;
-  if (kind == CSL_FEAT_F16)
-    return sage_launch(indptr, indices, items, n_items, hubs, n_hubs, pos0, part0, static_cast<const feat::f16*>(x), ldx, W,
-                       0, bias, relu, partial, out, ldo, stream);
-  return sage_launch(indptr, indices, items, n_items, hubs, n_hubs, pos0, part0, static_cast<const feat::bf16*>(x), ldx, W,
-                     0, bias, relu, partial, out, ldo, stream);
+  return with_elem(kind, [&](auto e) {
+    typedef typename decltype(e)::type E;
+    return sage_launch(indptr, indices, items, n_items, hubs, n_hubs, pos0, part0, static_cast<const E*>(x), ldx, W, 0, bias,
+                       relu, partial, out, ldo, stream);
+  });
 }
 
 int csl_upcast_rows_x16(const void* src, int32_t kind, int64_t lds, int64_t n, float* dst, int64_t ldd, int32_t H,
@@ -463,10 +346,7 @@ int csl_upcast_rows_x16(const void* src, int32_t kind, int64_t lds, int64_t n, f
     return CSL_E_INVALID;
   if (n == 0) return CSL_OK;
   if (!dst || !al16(dst)) return CSL_E_INVALID;
-  if (kind == CSL_FEAT_F16)
-    upcast_launch<feat::f16>(src, lds, n, dst, ldd, H, (hipStream_t)stream);
-  else
-    upcast_launch<feat::bf16>(src, lds, n, dst, ldd, H, (hipStream_t)stream);
+  with_elem(kind, [&](auto e) { upcast_launch<typename decltype(e)::type>(src, lds, n, dst, ldd, H, (hipStream_t)stream); });
   return done();
 }
 
@@ -479,7 +359,7 @@ int csl_infer_gat_f32(const int32_t* indptr, const int32_t* indices, const int32
                       const int32_t* hubs, int64_t n_hubs, int64_t pos0, int64_t part0, const float* z, const float* el,
                       const float* er, int32_t H, int32_t D, float slope, const float* bias, int32_t last, int32_t n_cls,
                       float* partial, float* out, int64_t ldo, void* stream) {
-  if (!plan_ok(indptr, indices, items, n_items, hubs, n_hubs, pos0, part0, partial)) return CSL_E_INVALID;
+  if (!plan_ok(indptr, indices, items, n_items, hubs, n_hubs, pos0, part0, partial, true)) return CSL_E_INVALID;
   if (H < 1 || D < 4 || D % 4 != 0 || (int64_t)H * D > (last ? GAT_LAST_MAX_C : GAT_MAX_C)) return CSL_E_INVALID;
   if (last ? (n_cls < 1 || n_cls > D || ldo < n_cls) : (ldo % 4 != 0 || ldo < (int64_t)H * D)) return CSL_E_INVALID;
   if (n_items == 0 && n_hubs == 0) return CSL_OK;
@@ -491,9 +371,11 @@ int csl_infer_gat_f32(const int32_t* indptr, const int32_t* indices, const int32
   const size_t shmem = last ? (size_t)WPB * C * sizeof(float) : 0;
   const int ls = last != 0;
   if (n_items)
-    LAUNCH_G(G, k_infer_gat, blocks_of(n_items), shmem, indptr, indices, reinterpret_cast<const int4*>(items),
-             (long long)n_items, (long long)pos0, (long long)part0, z, el, er, (int)H, (int)D, slope, bias, ls, (int)n_cls,
-             partial, pld, out, (long long)ldo);
+    with_groups(G, [&](auto g) {
+      hipLaunchKernelGGL(k_infer_gat<g()>, dim3(blocks_of(n_items)), dim3(BLK), shmem, st, indptr, indices,
+                         reinterpret_cast<const int4*>(items), (long long)n_items, (long long)pos0, (long long)part0, z, el,
+                         er, (int)H, (int)D, slope, bias, ls, (int)n_cls, partial, pld, out, (long long)ldo);
+    });
   if (n_hubs)
     hipLaunchKernelGGL(k_infer_gat_hubs, dim3(blocks_of(n_hubs)), dim3(BLK), shmem, st,
                        reinterpret_cast<const int4*>(hubs), (long long)n_hubs, (long long)pos0, (long long)part0, (int)H,

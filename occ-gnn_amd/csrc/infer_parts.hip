@@ -4,7 +4,8 @@
 // for the destinations it owns (merge kernels).  The partial kernels keep the arithmetic of csrc/infer.hip exactly: a
 // row's edges are split over the same G lane groups (edge j of an item to group j % G), each group adds its edges in
 // ascending order (the attention kernel: in steps of T = min(G U, 64) edges with one rescale per step), and the groups
-// are combined by the same xor butterfly.  So with one part the results are bitwise those of csl_infer_*_f32.
+// are combined by the same xor butterfly; a row is then finished by csrc/infer.hip's own row ends (csrc/infer_dev.h,
+// which both files include).  So with one part the results are bitwise those of csl_infer_*_f32.
 //
 // A wave may take `R` sub-CSR rows at once (the `pack` argument): slot s of the wave (64 / R lanes) holds one item, its
 // G groups of 64 / (R G) lanes walk the row's column tiles.  Every lane loads the source index of its own edge, so a
@@ -13,108 +14,10 @@
 //
 // The GraphSAGE kernels that read the layer's input table (k_sage_part its rows, k_sage_merge the self row) are
 // templated on its element type (csrc/feat_elem.h, include/cslicer_infer16.h), as csrc/infer.hip's are.
-#include <hip/hip_runtime.h>
-
-#include <cmath>
-#include <cstdint>
-
-#include "cslicer_hip.h"
-#include "cslicer_infer.h"
-#include "cslicer_infer16.h"
 #include "cslicer_infer_parts.h"
-#include "feat_elem.h"
+#include "infer_dev.h"
 
 namespace {
-
-constexpr int BLK = 256;
-constexpr int WPB = BLK / 64;   // waves per block
-constexpr int SEG = CSL_INFER_SEG;
-constexpr int U = 8;            // row loads in flight per lane and step (as csrc/infer.hip: the attention steps depend on it)
-constexpr int GAT_LAST_MAX_C = 4096;
-constexpr long long GAT_MAX_C = 1ll << 24;
-
-// the element helpers and row ends of csrc/infer.hip, restated: with one part the two files must round alike
-__device__ __forceinline__ float4 f4zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, const float4 v) { *reinterpret_cast<float4*>(p) = v; }
-__device__ __forceinline__ void add4(float4& a, const float4 b) { a.x += b.x, a.y += b.y, a.z += b.z, a.w += b.w; }
-__device__ __forceinline__ void scale4(float4& a, const float s) { a.x *= s, a.y *= s, a.z *= s, a.w *= s; }
-__device__ __forceinline__ void fma4(float4& a, const float s, const float4 b) {
-  a.x += s * b.x, a.y += s * b.y, a.z += s * b.z, a.w += s * b.w;
-}
-__device__ __forceinline__ float4 shfl_xor4(const float4 v, const int d) {
-  return make_float4(__shfl_xor(v.x, d), __shfl_xor(v.y, d), __shfl_xor(v.z, d), __shfl_xor(v.w, d));
-}
-__device__ __forceinline__ float elu1(const float v) { return v > 0.f ? v : expm1f(v); }
-
-__device__ __forceinline__ void lse_merge(float& m, float& s, float4& n, const float m2, const float s2, const float4 n2) {
-  const float M = fmaxf(m, m2);
-  const float a = expf(m - M), b = expf(m2 - M);
-  s = s * a + s2 * b;
-  scale4(n, a);
-  fma4(n, b, n2);
-  m = M;
-}
-
-// the hub merge of csrc/infer.hip's k_infer_gat_hubs with its rounding spelled out: there the compiler forms
-// s = s a + s2 b from two rounded products, n.xyz = fma(n, a, b n2) and n.w = fma(b, n2.w, n.w a) (gfx950, as
-// contracted and paired by its vectoriser).  Left to contract freely, the same expression compiles differently in a
-// kernel that stores the state instead of finishing the row, and a hub row with one part would differ in its last bit.
-// (Only the hub pass needs it: a merge into the zero state, as the owner's first, is exact in every form.)
-__device__ __forceinline__ void lse_merge_hub(float& m, float& s, float4& n, const float m2, const float s2,
-                                              const float4 n2) {
-#pragma clang fp contract(off)
-  const float M = fmaxf(m, m2);
-  const float a = expf(m - M), b = expf(m2 - M);
-  s = s * a + s2 * b;
-  n.x = __builtin_fmaf(n.x, a, b * n2.x);
-  n.y = __builtin_fmaf(n.y, a, b * n2.y);
-  n.z = __builtin_fmaf(n.z, a, b * n2.z);
-  n.w = __builtin_fmaf(b, n2.w, n.w * a);
-  m = M;
-}
-
-template <typename E>
-__device__ __forceinline__ void sage_finish(const E* __restrict__ x, long long ldx, int W, int proj,
-                                            const float* __restrict__ bias, int relu, float* __restrict__ out, long long ldo,
-                                            long long k, int row, int deg, int c4, float4 acc) {
-  const float d = (float)(deg > 0 ? deg : 1);
-  acc.x /= d, acc.y /= d, acc.z /= d, acc.w /= d;
-  const float4 self = feat::Elem<E>::up(feat::Elem<E>::ld(x + (long long)row * ldx + 4 * c4));
-  if (!proj) {
-    st4(out + k * ldo + 4 * c4, self);
-    st4(out + k * ldo + W + 4 * c4, acc);
-    return;
-  }
-  float4 y = self;
-  add4(y, acc);
-  if (bias) add4(y, ld4(bias + 4 * c4));
-  if (relu) y.x = fmaxf(y.x, 0.f), y.y = fmaxf(y.y, 0.f), y.z = fmaxf(y.z, 0.f), y.w = fmaxf(y.w, 0.f);
-  st4(out + k * ldo + 4 * c4, y);
-}
-
-__device__ __forceinline__ void gat_finish(const float* __restrict__ bias, int last, float* __restrict__ out, long long ldo,
-                                           float* stage, long long k, int c4, float s, float4 n) {
-  float4 y = s > 0.f ? make_float4(n.x / s, n.y / s, n.z / s, n.w / s) : f4zero();
-  if (bias) add4(y, ld4(bias + 4 * c4));
-  if (last) {
-    st4(stage + 4 * c4, y);
-    return;
-  }
-  st4(out + k * ldo + 4 * c4, make_float4(elu1(y.x), elu1(y.y), elu1(y.z), elu1(y.w)));
-}
-
-__device__ __forceinline__ void gat_head_mean(const float* stage, int H, int D, int n_cls, float* __restrict__ out,
-                                              long long ldo, long long k, int lane) {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  for (int j = lane; j < n_cls; j += 64) {
-    float t = 0.f;
-    for (int h = 0; h < H; h++) t += stage[h * D + j];
-    out[k * ldo + j] = t / (float)H;
-  }
-}
 
 // the item of slot `slot` of this wave and its edge range [e0, e0 + n); n = 0 for a slot past the end of the list
 struct Slot {
@@ -329,20 +232,7 @@ __global__ __launch_bounds__(BLK) void k_gat_merge(const int* __restrict__ lists
   if (last) gat_head_mean(stage, H, D, n_cls, out, ldo, i, lane);
 }
 
-// ---------------------------------------------------------------- host side
-
-bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-int done() { return hipGetLastError() == hipSuccess ? CSL_OK : CSL_E_HIP; }
-unsigned blocks_of(long long n, int per_wave = 1) {
-  return (unsigned)((n + (long long)WPB * per_wave - 1) / ((long long)WPB * per_wave));
-}
-
-// as csrc/infer.hip: G groups of 64 / G lanes, the smallest group that holds min(C4, 64) float4 columns
-int groups_for(int C4) {
-  int lg = 4;
-  while (lg < 64 && lg < C4) lg <<= 1;
-  return 64 / lg;
-}
+// ---------------------------------------------------------------- host side (al16 .. plan_ok, with_*: csrc/infer_dev.h)
 
 // rows per wave: as asked, but a group keeps at least 4 lanes
 int pack_for(int G, int pack) {
@@ -351,69 +241,18 @@ int pack_for(int G, int pack) {
   return R;
 }
 
-bool plan_ok(const int32_t* indptr, const int32_t* indices, const int32_t* items, int64_t n_items, const int32_t* hubs,
-             int64_t n_hubs, int64_t pos0, int64_t part0, const void* partial) {
-  if (n_items < 0 || n_hubs < 0 || pos0 < 0 || part0 < 0 || n_items >= (1ll << 31) * WPB || n_hubs >= (1ll << 31) * WPB)
-    return false;
-  if (n_items && (!indptr || !indices || !items || !al16(items))) return false;
-  if (n_hubs && (!hubs || !al16(hubs) || !partial || !al16(partial))) return false;
-  return true;
-}
-
 bool merge_ok(const int32_t* lists, int64_t n, int32_t P, const float* recv) {
   if (n < 0 || P < 1 || n >= (1ll << 31) * WPB) return false;
   if (n && (!lists || !recv || !al16(recv))) return false;
   return true;
 }
 
-#define LAUNCH_GR(G, R, KERNEL, grid, shmem, ...)                                                                 \
-  switch (G * 8 + R) {                                                                                          \
-    case 1 * 8 + 1: hipLaunchKernelGGL((KERNEL<1, 1>), dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break;    \
-    case 1 * 8 + 2: hipLaunchKernelGGL((KERNEL<1, 2>), dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break;    \
-    case 1 * 8 + 4: hipLaunchKernelGGL((KERNEL<1, 4>), dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break;    \
-    case 2 * 8 + 1: hipLaunchKernelGGL((KERNEL<2, 1>), dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break;    \
-    case 2 * 8 + 2: hipLaunchKernelGGL((KERNEL<2, 2>), dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break;    \
-    case 2 * 8 + 4: hipLaunchKernelGGL((KERNEL<2, 4>), dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break;    \
-    case 4 * 8 + 1: hipLaunchKernelGGL((KERNEL<4, 1>), dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break;    \
-    case 4 * 8 + 2: hipLaunchKernelGGL((KERNEL<4, 2>), dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break;    \
-    case 4 * 8 + 4: hipLaunchKernelGGL((KERNEL<4, 4>), dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break;    \
-    case 8 * 8 + 1: hipLaunchKernelGGL((KERNEL<8, 1>), dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break;    \
-    case 8 * 8 + 2: hipLaunchKernelGGL((KERNEL<8, 2>), dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break;    \
-    default: hipLaunchKernelGGL((KERNEL<16, 1>), dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break;          \
-  }
-
-// the same for a kernel with an element type: KERNEL<G, R, E>
-#define LAUNCH_GR_E(G, R, E, KERNEL, grid, shmem, ...)                                                            \
-  switch (G * 8 + R) {                                                                                          \
-    case 1 * 8 + 1: hipLaunchKernelGGL((KERNEL<1, 1, E>), dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break; \
-    case 1 * 8 + 2: hipLaunchKernelGGL((KERNEL<1, 2, E>), dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break; \
-    case 1 * 8 + 4: hipLaunchKernelGGL((KERNEL<1, 4, E>), dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break; \
-    case 2 * 8 + 1: hipLaunchKernelGGL((KERNEL<2, 1, E>), dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break; \
-    case 2 * 8 + 2: hipLaunchKernelGGL((KERNEL<2, 2, E>), dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break; \
-    case 2 * 8 + 4: hipLaunchKernelGGL((KERNEL<2, 4, E>), dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break; \
-    case 4 * 8 + 1: hipLaunchKernelGGL((KERNEL<4, 1, E>), dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break; \
-    case 4 * 8 + 2: hipLaunchKernelGGL((KERNEL<4, 2, E>), dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break; \
-    case 4 * 8 + 4: hipLaunchKernelGGL((KERNEL<4, 4, E>), dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break; \
-    case 8 * 8 + 1: hipLaunchKernelGGL((KERNEL<8, 1, E>), dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break; \
-    case 8 * 8 + 2: hipLaunchKernelGGL((KERNEL<8, 2, E>), dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break; \
-    default: hipLaunchKernelGGL((KERNEL<16, 1, E>), dim3(grid), dim3(BLK), shmem, st, __VA_ARGS__); break;       \
-  }
-
-#define LAUNCH_G_E(G, E, KERNEL, grid, ...)                                                                     \
-  switch (G) {                                                                                                \
-    case 1: hipLaunchKernelGGL((KERNEL<1, E>), dim3(grid), dim3(BLK), 0, st, __VA_ARGS__); break;              \
-    case 2: hipLaunchKernelGGL((KERNEL<2, E>), dim3(grid), dim3(BLK), 0, st, __VA_ARGS__); break;              \
-    case 4: hipLaunchKernelGGL((KERNEL<4, E>), dim3(grid), dim3(BLK), 0, st, __VA_ARGS__); break;              \
-    case 8: hipLaunchKernelGGL((KERNEL<8, E>), dim3(grid), dim3(BLK), 0, st, __VA_ARGS__); break;              \
-    default: hipLaunchKernelGGL((KERNEL<16, E>), dim3(grid), dim3(BLK), 0, st, __VA_ARGS__); break;            \
-  }
-
 // what the float32 and the 16-bit entry point of a GraphSAGE kernel check alike (everything but the table itself), and
 // their launches over a table of element type E
 bool sage_part_ok(const int32_t* indptr, const int32_t* indices, const int32_t* items, int64_t n_items,
                   const int32_t* hubs, int64_t n_hubs, int64_t pos0, int64_t part0, int64_t ldy, int32_t W, int32_t pack,
                   const void* partial) {
-  if (!plan_ok(indptr, indices, items, n_items, hubs, n_hubs, pos0, part0, partial)) return false;
+  if (!plan_ok(indptr, indices, items, n_items, hubs, n_hubs, pos0, part0, partial, false)) return false;
   return !(W < 4 || W % 4 != 0 || ldy % 4 != 0 || ldy < W || pack < 1);
 }
 
@@ -424,8 +263,11 @@ int sage_part_launch(const int32_t* indptr, const int32_t* indices, const int32_
   hipStream_t st = (hipStream_t)stream;
   const int G = groups_for(W / 4), R = pack_for(G, pack);
   if (n_items)
-    LAUNCH_GR_E(G, R, E, k_sage_part, blocks_of(n_items, R), 0, indptr, indices, reinterpret_cast<const int4*>(items),
-              (long long)n_items, (long long)pos0, (long long)part0, y, (long long)ldy, (int)W, partial, send);
+    with_groups_rows(G, R, [&](auto g, auto r) {
+      hipLaunchKernelGGL((k_sage_part<g(), r(), E>), dim3(blocks_of(n_items, R)), dim3(BLK), 0,
+                         st, indptr, indices, reinterpret_cast<const int4*>(items), (long long)n_items, (long long)pos0,
+                         (long long)part0, y, (long long)ldy, (int)W, partial, send);
+    });
   if (n_hubs)
     hipLaunchKernelGGL(k_sage_part_hubs, dim3(blocks_of(n_hubs)), dim3(BLK), 0, st, reinterpret_cast<const int4*>(hubs),
                        (long long)n_hubs, (long long)pos0, (long long)part0, (int)W, partial, send);
@@ -444,8 +286,11 @@ int sage_merge_launch(const int32_t* dst, const int32_t* lists, int64_t n, int32
                       void* stream) {
   hipStream_t st = (hipStream_t)stream;
   const int G = groups_for(W / 4);
-  LAUNCH_G_E(G, E, k_sage_merge, blocks_of(n, G), reinterpret_cast<const int2*>(dst), lists, (long long)n, (int)P, recv, x,
-           (long long)ldx, (int)W, proj != 0, bias, relu != 0, out, (long long)ldo);
+  with_groups(G, [&](auto g) {
+    hipLaunchKernelGGL((k_sage_merge<g(), E>), dim3(blocks_of(n, G)), dim3(BLK), 0, st,
+                       reinterpret_cast<const int2*>(dst), lists, (long long)n, (int)P, recv, x, (long long)ldx, (int)W,
+                       proj != 0, bias, relu != 0, out, (long long)ldo);
+  });
   return done();
 }
 
@@ -470,11 +315,11 @@ int csl_infer_sage_part_x16(const int32_t* indptr, const int32_t* indices, const
   if (!sage_part_ok(indptr, indices, items, n_items, hubs, n_hubs, pos0, part0, ldy, W, pack, partial)) return CSL_E_INVALID;
   if (n_items == 0 && n_hubs == 0) return CSL_OK;
   if (!send || !al16(send)) return CSL_E_INVALID;
-  if (kind == CSL_FEAT_F16)
-    return sage_part_launch(indptr, indices, items, n_items, hubs, n_hubs, pos0, part0, static_cast<const feat::f16*>(y),
-                            ldy, W, pack, partial, send, stream);
-  return sage_part_launch(indptr, indices, items, n_items, hubs, n_hubs, pos0, part0, static_cast<const feat::bf16*>(y), ldy,
-                          W, pack, partial, send, stream);
+  return with_elem(kind, [&](auto e) {
+    typedef typename decltype(e)::type E;
+    return sage_part_launch(indptr, indices, items, n_items, hubs, n_hubs, pos0, part0, static_cast<const E*>(y), ldy, W,
+                            pack, partial, send, stream);
+  });
 }
 
 int csl_infer_sage_merge_f32(const int32_t* dst, const int32_t* lists, int64_t n, int32_t P, const float* recv,
@@ -494,18 +339,17 @@ int csl_infer_sage_merge_x16(const int32_t* dst, const int32_t* lists, int64_t n
   if (!sage_merge_ok(lists, n, P, recv, ldx, W, 0, ldo)) return CSL_E_INVALID;
   if (n == 0) return CSL_OK;
   if (!dst || (reinterpret_cast<uintptr_t>(dst) & 7u) || !out || !al16(out) || (bias && !al16(bias))) return CSL_E_INVALID;
-  if (kind == CSL_FEAT_F16)
-    return sage_merge_launch(dst, lists, n, P, recv, static_cast<const feat::f16*>(x), ldx, W, 0, bias, relu, out, ldo,
-                             stream);
-  return sage_merge_launch(dst, lists, n, P, recv, static_cast<const feat::bf16*>(x), ldx, W, 0, bias, relu, out, ldo,
-                           stream);
+  return with_elem(kind, [&](auto e) {
+    typedef typename decltype(e)::type E;
+    return sage_merge_launch(dst, lists, n, P, recv, static_cast<const E*>(x), ldx, W, 0, bias, relu, out, ldo, stream);
+  });
 }
 
 int csl_infer_gat_part_f32(const int32_t* indptr, const int32_t* indices, const int32_t* items, int64_t n_items,
                            const int32_t* hubs, int64_t n_hubs, int64_t pos0, int64_t part0, const float* z,
                            const float* el, const float* er_rows, int32_t H, int32_t D, float slope, int32_t pack,
                            float* partial, float* send, void* stream) {
-  if (!plan_ok(indptr, indices, items, n_items, hubs, n_hubs, pos0, part0, partial)) return CSL_E_INVALID;
+  if (!plan_ok(indptr, indices, items, n_items, hubs, n_hubs, pos0, part0, partial, false)) return CSL_E_INVALID;
   if (H < 1 || D < 4 || D % 4 != 0 || (int64_t)H * D > GAT_MAX_C || pack < 1) return CSL_E_INVALID;
   if (n_items == 0 && n_hubs == 0) return CSL_OK;
   if (!z || !el || !er_rows || !send || !al16(z) || !al16(send)) return CSL_E_INVALID;
@@ -513,9 +357,11 @@ int csl_infer_gat_part_f32(const int32_t* indptr, const int32_t* indices, const 
   const int G = groups_for(H * D / 4), R = pack_for(G, pack);
   const long long pld = csl_infer_gat_partial_ld(H, D);
   if (n_items)
-    LAUNCH_GR(G, R, k_gat_part, blocks_of(n_items, R), 0, indptr, indices, reinterpret_cast<const int4*>(items),
-              (long long)n_items, (long long)pos0, (long long)part0, z, el, er_rows, (int)H, (int)D, slope, partial, pld,
-              send);
+    with_groups_rows(G, R, [&](auto g, auto r) {
+      hipLaunchKernelGGL((k_gat_part<g(), r()>), dim3(blocks_of(n_items, R)), dim3(BLK), 0, st,
+                         indptr, indices, reinterpret_cast<const int4*>(items), (long long)n_items, (long long)pos0,
+                         (long long)part0, z, el, er_rows, (int)H, (int)D, slope, partial, pld, send);
+    });
   if (n_hubs)
     hipLaunchKernelGGL(k_gat_part_hubs, dim3(blocks_of(n_hubs)), dim3(BLK), 0, st, reinterpret_cast<const int4*>(hubs),
                        (long long)n_hubs, (long long)pos0, (long long)part0, (int)H, (int)D, partial, pld, send);

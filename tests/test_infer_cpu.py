@@ -39,6 +39,11 @@ def test_bad_arguments_are_refused_without_a_gpu():
     assert L.csl_infer_sage_f32(fake, fake, fake, 10, null, 0, 0, 0, null, 100, 100, 0, null, 0, null, fake, 200, st) == -1
     # nothing to do: accepted without a launch
     assert L.csl_infer_sage_f32(null, null, null, 0, null, 0, 0, 0, null, 100, 100, 0, null, 0, null, null, 200, st) == 0
+    # hub rows only, everything there but indptr: these hub passes read a row's degree from it (the one check the rank
+    # path's csl_infer_*_part_f32 do not make)
+    assert L.csl_infer_sage_f32(null, null, null, 0, fake, 3, 0, 0, fake, 100, 100, 0, null, 0, fake, fake, 200, st) == -1
+    assert L.csl_infer_gat_f32(null, null, null, 0, fake, 3, 0, 0, fake, fake, fake, 8, 32, 0.2, null, 0, 0, fake, fake,
+                               256, st) == -1
     # GAT: D % 4, H * D > 4096, n_cls > D, ldo of a hidden layer too small
     assert L.csl_infer_gat_f32(fake, fake, fake, 10, null, 0, 0, 0, fake, fake, fake, 8, 6, 0.2, null, 0, 0, null, fake,
                                48, st) == -1
@@ -100,6 +105,68 @@ def test_plan_segment_layout():
     assert [c[:2] for c in ch] == [(0, 3), (3, 6), (6, 7)]
     assert [(c[6], c[7]) for c in ch] == [(0, 0), (0, 5), (5, 3)]
     assert [(c[4], c[5]) for c in ch] == [(0, 0), (0, 2), (2, 3)]
+    # a chunk is a record that still compares and unpacks as the tuple it was
+    assert ch[0] == (0, 3, 0, 3, 0, 0, 0, 0) and ch[1] == (3, 6, 3, 9, 0, 2, 0, 5)
+    assert ch[0].n_parts == 0 and ch[1].n_parts == 5 and (ch[1].k0, ch[1].i1, ch[1].h1, ch[1].part0) == (3, 9, 2, 0)
+
+
+def test_parts_plan_chunks_are_records():
+    S = infer.SEG
+    indptr, indices = _csr([3, 2 * S + 5, 1, 0, 4, 2, S + 1], seed=3)
+    N, P = 7, 2
+    rg = infer.RankGraph(indptr, indices, infer.owner_table(N, P), P, 0)
+    pp = rg.plan(3)
+    ch, w = pp.chunks(), pp.work
+    assert len(ch) == pp.n_chunks == 3
+    for c, rec in enumerate(ch):
+        s0, s1 = int(pp.sub_first[c]), int(pp.sub_first[c + 1])
+        h0, h1 = (int(x) for x in np.searchsorted(w["hub_pos"], [s0, s1]))
+        p0, p1 = int(w["part_first"][s0]), int(w["part_first"][s1])
+        assert rec == (s0, s1, int(w["item_first"][s0]), int(w["item_first"][s1]), h0, h1, p0, p1 - p0,
+                       int(pp.own_first[c]), int(pp.own_first[c + 1]), int(pp.recv_first[c]), int(pp.recv_first[c + 1]))
+        assert (rec.r0, rec.r1) == (int(pp.recv_first[c]), int(pp.recv_first[c + 1])) and rec.n_parts == p1 - p0
+        assert (rec.s0, rec.o1) == (s0, int(pp.own_first[c + 1])) and len(tuple(rec)) == 12
+    assert sum(r.n_parts for r in ch) == w["n_parts"] > 0          # (the hub rows were cut)
+
+
+def test_sage_operands_place_both_halves_and_pad_with_zeros():
+    import torch
+    from cslicer import splitgnn
+    cpu = torch.device("cpu")
+    conv = splitgnn.DistSageConv(5, 7)                              # out >= in: aggregate first, table width 8
+    W, b = conv.fc.weight.detach(), conv.fc.bias.detach()
+    agg_first, w, bias = infer._sage_operands(conv, 8, cpu)
+    want = torch.zeros((7, 16))
+    want[:, 0:5], want[:, 8:13] = W[:, :5], W[:, 5:]
+    assert agg_first is True and torch.equal(w, want) and torch.equal(bias, b)
+    conv = splitgnn.DistSageConv(7, 3)                              # out < in: project first, op = 4
+    W, b = conv.fc.weight.detach(), conv.fc.bias.detach()
+    agg_first, w, bias = infer._sage_operands(conv, 8, cpu)
+    want = torch.zeros((8, 8))
+    want[0:3, :7], want[4:7, :7] = W[:, :7], W[:, 7:]
+    assert agg_first is False and torch.equal(w, want)
+    assert bias.shape == (4,) and torch.equal(bias[:3], b) and bias[3] == 0
+
+
+def test_gat_operands_follow_the_column_map_and_pad_with_zeros():
+    import torch
+    from cslicer import splitgnn
+    H, D, Dp, hp = 2, 3, 4, 8
+    conv = splitgnn.DistGATConv(6, D, H)
+    with torch.no_grad():
+        conv.bias.copy_(torch.arange(1, H * D + 1, dtype=torch.float32))
+    in_map = torch.tensor([0, 1, 2, 4, 5, 6])
+    ops = infer._gat_operands(conv, in_map, hp, torch.device("cpu"))
+    W = conv.fc.weight.detach()
+    want = torch.zeros((H * Dp, hp))
+    for h in range(H):
+        for d in range(D):
+            for c in range(6):
+                want[h * Dp + d, int(in_map[c])] = W[h * D + d, c]
+    assert torch.equal(ops.wz, want) and (ops.H, ops.D, ops.Dp) == (H, D, Dp)
+    for got, src in ((ops.al, conv.attn_l), (ops.ar, conv.attn_r), (ops.bz, conv.bias.view(H, D))):
+        assert got.shape == (H, Dp) and torch.equal(got[:, :D], src.detach()) and (got[:, D:] == 0).all()
+    assert ops.cmap.tolist() == [0, 1, 2, 4, 5, 6] and ops.vl is None and ops.vr is None
 
 
 def test_splits_round_trip(tmp_path):
