@@ -19,7 +19,9 @@
 #include "cslicer_aggr.h"
 #include "cslicer_feat16.h"
 #include "cslicer_hip.h"
+#include "dev_common.h"
 #include "feat_elem.h"
+#include "table_readers.h"
 
 namespace {
 
@@ -42,12 +44,6 @@ __device__ __forceinline__ void st4(float* p, int c, int H, float4 v) {
   if (c < H) p[c] = v.x;
   if (c + 1 < H) p[c + 1] = v.y;
   if (c + 2 < H) p[c + 2] = v.z;
-}
-__device__ __forceinline__ void add4(float4& a, const float4 b) {
-  a.x += b.x;
-  a.y += b.y;
-  a.z += b.z;
-  a.w += b.w;
 }
 
 // a quad of a source row: of a float32 matrix as before (whole quads when vec_ok, else element-wise at the row's tail),
@@ -1280,91 +1276,104 @@ int group_for(int H) {
   while (g < q && g < 64) g <<= 1;
   return g;
 }
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 int vec_ok(const void* a, long long lda, const void* b, long long ldb, int H) {
   return (H % 4 == 0) && (lda % 4 == 0) && (ldb % 4 == 0) && aligned16(a) && aligned16(b);
 }
 
-#define DISPATCH_G(G, KERNEL, grid_rows, ...)                                                        \
-  switch (G) {                                                                                       \
-    case 1: hipLaunchKernelGGL(KERNEL<1>, dim3((unsigned)(((grid_rows) + BLK - 1) / BLK)), dim3(BLK), 0, st, __VA_ARGS__); break; \
-    case 2: hipLaunchKernelGGL(KERNEL<2>, dim3((unsigned)(((grid_rows) + BLK / 2 - 1) / (BLK / 2))), dim3(BLK), 0, st, __VA_ARGS__); break; \
-    case 4: hipLaunchKernelGGL(KERNEL<4>, dim3((unsigned)(((grid_rows) + BLK / 4 - 1) / (BLK / 4))), dim3(BLK), 0, st, __VA_ARGS__); break; \
-    case 8: hipLaunchKernelGGL(KERNEL<8>, dim3((unsigned)(((grid_rows) + BLK / 8 - 1) / (BLK / 8))), dim3(BLK), 0, st, __VA_ARGS__); break; \
-    case 16: hipLaunchKernelGGL(KERNEL<16>, dim3((unsigned)(((grid_rows) + BLK / 16 - 1) / (BLK / 16))), dim3(BLK), 0, st, __VA_ARGS__); break; \
-    case 32: hipLaunchKernelGGL(KERNEL<32>, dim3((unsigned)(((grid_rows) + BLK / 32 - 1) / (BLK / 32))), dim3(BLK), 0, st, __VA_ARGS__); break; \
-    default: hipLaunchKernelGGL(KERNEL<64>, dim3((unsigned)(((grid_rows) + BLK / 64 - 1) / (BLK / 64))), dim3(BLK), 0, st, __VA_ARGS__); break; \
-  }
-
-// the same with a 16-bit table: KERNEL<G, E> for E = feat::f16 or feat::bf16 (`kind` checked by the caller)
-#define DISPATCH_G_E(G, E, KERNEL, grid_rows, ...)                                                                        \
-  switch (G) {                                                                                                            \
-    case 1: hipLaunchKernelGGL((KERNEL<1, E>), dim3((unsigned)(((grid_rows) + BLK - 1) / BLK)), dim3(BLK), 0, st, __VA_ARGS__); break; \
-    case 2: hipLaunchKernelGGL((KERNEL<2, E>), dim3((unsigned)(((grid_rows) + BLK / 2 - 1) / (BLK / 2))), dim3(BLK), 0, st, __VA_ARGS__); break; \
-    case 4: hipLaunchKernelGGL((KERNEL<4, E>), dim3((unsigned)(((grid_rows) + BLK / 4 - 1) / (BLK / 4))), dim3(BLK), 0, st, __VA_ARGS__); break; \
-    case 8: hipLaunchKernelGGL((KERNEL<8, E>), dim3((unsigned)(((grid_rows) + BLK / 8 - 1) / (BLK / 8))), dim3(BLK), 0, st, __VA_ARGS__); break; \
-    case 16: hipLaunchKernelGGL((KERNEL<16, E>), dim3((unsigned)(((grid_rows) + BLK / 16 - 1) / (BLK / 16))), dim3(BLK), 0, st, __VA_ARGS__); break; \
-    case 32: hipLaunchKernelGGL((KERNEL<32, E>), dim3((unsigned)(((grid_rows) + BLK / 32 - 1) / (BLK / 32))), dim3(BLK), 0, st, __VA_ARGS__); break; \
-    default: hipLaunchKernelGGL((KERNEL<64, E>), dim3((unsigned)(((grid_rows) + BLK / 64 - 1) / (BLK / 64))), dim3(BLK), 0, st, __VA_ARGS__); break; \
-  }
-#define DISPATCH_G_KIND(G, kind, KERNEL, grid_rows, XPTR, ...)                                          \
-  if ((kind) == CSL_FEAT_F16) {                                                                        \
-    const feat::f16* XPTR##_e = static_cast<const feat::f16*>(XPTR);                                   \
-    DISPATCH_G_E(G, feat::f16, KERNEL, grid_rows, __VA_ARGS__)                                         \
-  } else {                                                                                             \
-    const feat::bf16* XPTR##_e = static_cast<const feat::bf16*>(XPTR);                                 \
-    DISPATCH_G_E(G, feat::bf16, KERNEL, grid_rows, __VA_ARGS__)                                        \
-  }
-
-int done() { return hipGetLastError() == hipSuccess ? CSL_OK : CSL_E_HIP; }
+// the grid of a kernel whose rows take G lanes each: BLK / G rows per block
+template <int G>
+dim3 row_grid(long long rows) {
+  return dim3((unsigned)((rows + BLK / G - 1) / (BLK / G)));
+}
 
 }  // namespace
 
-extern "C" {
+// ---- the readers of the feature table (table_readers.h): one host path for float32 and 16-bit elements each
 
-static int spmm_sum_impl(const int32_t* indptr, const int32_t* indices, const int32_t* rows, int64_t n_rows,
-                         const float* x, int64_t ldx, float* out, int64_t ldo, int32_t H, int compact, void* stream,
-                         const int32_t* rowmap = nullptr) {
+// (the destination decides whether whole quads are stored; a 16-bit table's quads are always whole, a float32 matrix's
+// when vec_ok says so)
+int rd::spmm_sum_map(const int32_t* indptr, const int32_t* indices, const int32_t* rows, int64_t n_rows, const void* x,
+                     int32_t kind, int64_t ldx, const int32_t* rowmap, float* out, int64_t ldo, int32_t H, int32_t compact,
+                     void* stream) {
+  if (rd::table16_bad(x, kind, ldx, H) || (kind && H < 1)) return CSL_E_INVALID;
   if (n_rows == 0) return CSL_OK;  // nothing to do: empty lists come with null pointers
   if (n_rows < 0 || H < 1 || !indptr || !out || ldx < H || ldo < H || (compact && !rows)) return CSL_E_INVALID;
   hipStream_t st = (hipStream_t)stream;
-  const int G = group_for(H), v = vec_ok(x, ldx, out, ldo, H);
-  DISPATCH_G(G, k_spmm_sum, n_rows, indptr, indices, rows,
-             (long long)n_rows, x, (long long)ldx, out, (long long)ldo, (int)H, v, compact, rowmap);
+  const int v = kind ? vec_ok(out, ldo, out, ldo, H) : vec_ok(x, ldx, out, ldo, H), cp = compact ? 1 : 0;
+  with_table(kind, [&](auto e) {
+    typedef typename decltype(e)::type E;
+    with_groups<1, 64>(group_for(H), [&](auto g) {
+      hipLaunchKernelGGL((k_spmm_sum<g(), E>), row_grid<g()>(n_rows), dim3(BLK), 0, st, indptr, indices, rows,
+                         (long long)n_rows, static_cast<const E*>(x), (long long)ldx, out, (long long)ldo, (int)H, v, cp, rowmap);
+    });
+  });
   return done();
 }
 
+int rd::gather_rows(const void* src, int32_t kind, int64_t lds, const int32_t* idx, int64_t n, float* dst, int64_t ldd,
+                    int32_t H, void* stream) {
+  if (rd::table16_bad(src, kind, lds, H) || (kind && H < 1)) return CSL_E_INVALID;
+  if (n == 0) return CSL_OK;
+  if (n < 0 || H < 1 || !idx || !dst || !src || lds < H || ldd < H) return CSL_E_INVALID;
+  hipStream_t st = (hipStream_t)stream;
+  const int v = kind ? vec_ok(dst, ldd, dst, ldd, H) : vec_ok(src, lds, dst, ldd, H);
+  with_table(kind, [&](auto e) {
+    typedef typename decltype(e)::type E;
+    with_groups<1, 64>(group_for(H), [&](auto g) {
+      hipLaunchKernelGGL((k_gather_rows<g(), E>), row_grid<g()>(n), dim3(BLK), 0, st, static_cast<const E*>(src),
+                         (long long)lds, idx, (long long)n, dst, (long long)ldd, (int)H, v);
+    });
+  });
+  return done();
+}
+
+int rd::sage_cat(const int32_t* indptr, const int32_t* indices, const int32_t* self_ids, const int32_t* owned,
+                 const int32_t* deg, const int32_t* rowmap, const void* x, int32_t kind, int64_t ldx, const float* agg,
+                 int64_t lda, int64_t n, int64_t n_pad, float* cat, int64_t ldc, int32_t H, int32_t relu_in, void* stream) {
+  if (rd::table16_bad(x, kind, ldx, H)) return CSL_E_INVALID;
+  if (n_pad == 0) return CSL_OK;
+  if (n < 0 || n_pad < n || H < 4 || H % 4 != 0 || !cat || ldc < 2 * (int64_t)H || ldc % 4 != 0 || !aligned16(cat))
+    return CSL_E_INVALID;
+  if (n > 0) {
+    if (!self_ids || (kind == 0 && (!x || ldx < H || ldx % 4 != 0 || !aligned16(x)))) return CSL_E_INVALID;
+    if (!indptr && (!owned || !deg || !agg || lda < H || lda % 4 != 0 || !aligned16(agg))) return CSL_E_INVALID;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  with_table(kind, [&](auto e) {
+    typedef typename decltype(e)::type E;
+    with_groups<1, 64>(group_for(H), [&](auto g) {
+      hipLaunchKernelGGL((k_sage_cat<g(), E>), row_grid<g()>(n_pad), dim3(BLK), 0, st, indptr, indices, self_ids, owned, deg,
+                         rowmap, static_cast<const E*>(x), (long long)ldx, agg, (long long)lda, (long long)n, (long long)n_pad,
+                         cat, (long long)ldc, (int)H, (int)relu_in);
+    });
+  });
+  return done();
+}
+
+extern "C" {
+
 int csl_spmm_sum_map_f32(const int32_t* indptr, const int32_t* indices, const int32_t* rows, int64_t n_rows, const float* x,
                          int64_t ldx, const int32_t* rowmap, float* out, int64_t ldo, int32_t H, int32_t compact, void* stream) {
-  return spmm_sum_impl(indptr, indices, rows, n_rows, x, ldx, out, ldo, H, compact ? 1 : 0, stream, rowmap);
+  return rd::spmm_sum_map(indptr, indices, rows, n_rows, x, 0, ldx, rowmap, out, ldo, H, compact, stream);
 }
 
 int csl_spmm_sum_map_x16(const int32_t* indptr, const int32_t* indices, const int32_t* rows, int64_t n_rows, const void* x,
                          int32_t kind, int64_t ldx, const int32_t* rowmap, float* out, int64_t ldo, int32_t H,
                          int32_t compact, void* stream) {
-  if (!feat::table_ok(x, kind, ldx) || H < 1 || ldx < H) return CSL_E_INVALID;
-  if (n_rows == 0) return CSL_OK;
-  if (n_rows < 0 || !indptr || !out || ldo < H || (compact && !rows)) return CSL_E_INVALID;
-  hipStream_t st = (hipStream_t)stream;
-  // (the destination decides whether whole quads are stored; the table's quads are always whole)
-  const int G = group_for(H), v = vec_ok(out, ldo, out, ldo, H), cp = compact ? 1 : 0;
-  DISPATCH_G_KIND(G, kind, k_spmm_sum, n_rows, x, indptr, indices, rows, (long long)n_rows, x_e, (long long)ldx, out,
-                  (long long)ldo, (int)H, v, cp, rowmap);
-  return done();
+  if (!feat::kind_ok(kind)) return CSL_E_INVALID;
+  return rd::spmm_sum_map(indptr, indices, rows, n_rows, x, kind, ldx, rowmap, out, ldo, H, compact, stream);
 }
 
 int csl_spmm_sum_f32(const int32_t* indptr, const int32_t* indices, const int32_t* rows, int64_t n_rows,
                      const float* x, int64_t ldx, float* out, int64_t ldo, int32_t H, void* stream) {
-  return spmm_sum_impl(indptr, indices, rows, n_rows, x, ldx, out, ldo, H, 0, stream);
+  return rd::spmm_sum_map(indptr, indices, rows, n_rows, x, 0, ldx, nullptr, out, ldo, H, 0, stream);
 }
 
 int csl_spmm_sum_compact_f32(const int32_t* indptr, const int32_t* indices, const int32_t* rows, int64_t n_rows,
                              const float* x, int64_t ldx, float* out, int64_t ldo, int32_t H, void* stream) {
-  return spmm_sum_impl(indptr, indices, rows, n_rows, x, ldx, out, ldo, H, 1, stream);
+  return rd::spmm_sum_map(indptr, indices, rows, n_rows, x, 0, ldx, nullptr, out, ldo, H, 1, stream);
 }
 
-// gradient of csl_sage_cat_f32's merged-sums form: gx [n_x, H] and gagg [n_agg, H] are zeroed here, then
-// gx[self_ids[r]] = gcat[r, 0:H) and gagg[owned[r]] = gcat[r, H:2H) / max(deg[r], 1) (both index lists are unique)
 int csl_gat_bwd_t_f32(const int32_t* t_indptr, const int32_t* t_indices, int64_t n_src, int64_t n_pad, const float* el,
                       const float* er, const float* z, int32_t H, int32_t D, float slope, const float* m_in,
                       const float* g_s, const float* g_n, float* g_el, float* g_er, float* g_z, void* stream) {
@@ -1470,10 +1479,6 @@ int csl_gat_finish_bwd_f32(const float* g, int64_t ldg, const float* out, const 
   return done();
 }
 
-int csl_sage_cat_rows_bwd_f32(const int32_t* self_ids, const int32_t* owned, const int32_t* deg, int64_t n,
-                              const float* gcat, int64_t ldg, float* gx, int64_t n_x, float* gagg, int64_t n_agg,
-                              int32_t H, void* stream);
-
 int csl_spmm_sum_bwd_f32(const int32_t* indptr, const int32_t* indices, const int32_t* rows, int64_t n_rows,
                          const float* grad_out, int64_t ldg, int32_t compact, float* grad_x, int64_t ldx, int32_t H,
                          void* stream) {
@@ -1488,23 +1493,13 @@ int csl_spmm_sum_bwd_f32(const int32_t* indptr, const int32_t* indices, const in
 
 int csl_gather_rows_f32(const float* src, int64_t lds, const int32_t* idx, int64_t n, float* dst, int64_t ldd,
                         int32_t H, void* stream) {
-  if (n == 0) return CSL_OK;
-  if (n < 0 || H < 1 || !idx || !dst || !src || lds < H || ldd < H) return CSL_E_INVALID;
-  hipStream_t st = (hipStream_t)stream;
-  const int G = group_for(H), v = vec_ok(src, lds, dst, ldd, H);
-  DISPATCH_G(G, k_gather_rows, n, src, (long long)lds, idx, (long long)n, dst, (long long)ldd, (int)H, v);
-  return done();
+  return rd::gather_rows(src, 0, lds, idx, n, dst, ldd, H, stream);
 }
 
 int csl_gather_rows_x16(const void* src, int32_t kind, int64_t lds, const int32_t* idx, int64_t n, float* dst, int64_t ldd,
                         int32_t H, void* stream) {
-  if (!feat::table_ok(src, kind, lds) || H < 1 || lds < H) return CSL_E_INVALID;
-  if (n == 0) return CSL_OK;
-  if (n < 0 || !idx || !dst || ldd < H) return CSL_E_INVALID;
-  hipStream_t st = (hipStream_t)stream;
-  const int G = group_for(H), v = vec_ok(dst, ldd, dst, ldd, H);
-  DISPATCH_G_KIND(G, kind, k_gather_rows, n, src, src_e, (long long)lds, idx, (long long)n, dst, (long long)ldd, (int)H, v);
-  return done();
+  if (!feat::kind_ok(kind)) return CSL_E_INVALID;
+  return rd::gather_rows(src, kind, lds, idx, n, dst, ldd, H, stream);
 }
 
 int csl_scatter_add_rows_f32(float* dst, int64_t ldd, const int32_t* idx, int64_t n, const float* src, int64_t lds,
@@ -1512,9 +1507,11 @@ int csl_scatter_add_rows_f32(float* dst, int64_t ldd, const int32_t* idx, int64_
   if (n == 0) return CSL_OK;
   if (n < 0 || H < 1 || !idx || !dst || !src) return CSL_E_INVALID;
   hipStream_t st = (hipStream_t)stream;
-  const int G = group_for(H), v = vec_ok(src, lds, dst, ldd, H);
-  DISPATCH_G(G, k_scatter_add_rows, n, dst, (long long)ldd, idx, (long long)n, src, (long long)lds,
-             (int)H, v);
+  const int v = vec_ok(src, lds, dst, ldd, H);
+  with_groups<1, 64>(group_for(H), [&](auto g) {
+    hipLaunchKernelGGL(k_scatter_add_rows<g()>, row_grid<g()>(n), dim3(BLK), 0, st, dst, (long long)ldd, idx, (long long)n,
+                       src, (long long)lds, (int)H, v);
+  });
   return done();
 }
 
@@ -1531,8 +1528,10 @@ int csl_div_rows_f32(float* x, int64_t ldx, const int32_t* deg, int64_t n, int32
   if (n == 0) return CSL_OK;
   if (n < 0 || H < 1 || !x || !deg) return CSL_E_INVALID;
   hipStream_t st = (hipStream_t)stream;
-  const int G = group_for(H), v = vec_ok(x, ldx, x, ldx, H);
-  DISPATCH_G(G, k_div_rows, n, x, (long long)ldx, deg, (long long)n, (int)H, v);
+  const int v = vec_ok(x, ldx, x, ldx, H);
+  with_groups<1, 64>(group_for(H), [&](auto g) {
+    hipLaunchKernelGGL(k_div_rows<g()>, row_grid<g()>(n), dim3(BLK), 0, st, x, (long long)ldx, deg, (long long)n, (int)H, v);
+  });
   return done();
 }
 
@@ -1565,42 +1564,21 @@ int csl_gat_bwd_f32(const int32_t* indptr, const int32_t* indices, int64_t n_row
   return done();
 }
 
-
 int csl_sage_cat_f32(const int32_t* indptr, const int32_t* indices, const int32_t* self_ids, const int32_t* owned,
                      const int32_t* deg, const int32_t* rowmap, const float* x, int64_t ldx, const float* agg,
                      int64_t lda, int64_t n, int64_t n_pad, float* cat, int64_t ldc, int32_t H, int32_t relu_in,
                      void* stream) {
-  if (n_pad == 0) return CSL_OK;
-  if (n < 0 || n_pad < n || H < 4 || H % 4 != 0 || !cat || ldc < 2 * (int64_t)H || ldc % 4 != 0 || !aligned16(cat))
-    return CSL_E_INVALID;
-  if (n > 0) {
-    if (!self_ids || !x || ldx < H || ldx % 4 != 0 || !aligned16(x)) return CSL_E_INVALID;
-    if (!indptr && (!owned || !deg || !agg || lda < H || lda % 4 != 0 || !aligned16(agg))) return CSL_E_INVALID;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const int G = group_for(H);
-  DISPATCH_G(G, k_sage_cat, n_pad, indptr, indices, self_ids, owned, deg, rowmap, x, (long long)ldx, agg, (long long)lda,
-             (long long)n, (long long)n_pad, cat, (long long)ldc, (int)H, (int)relu_in);
-  return done();
+  return rd::sage_cat(indptr, indices, self_ids, owned, deg, rowmap, x, 0, ldx, agg, lda, n, n_pad, cat, ldc, H, relu_in,
+                      stream);
 }
 
 int csl_sage_cat_x16(const int32_t* indptr, const int32_t* indices, const int32_t* self_ids, const int32_t* owned,
                      const int32_t* deg, const int32_t* rowmap, const void* x, int32_t kind, int64_t ldx, const float* agg,
                      int64_t lda, int64_t n, int64_t n_pad, float* cat, int64_t ldc, int32_t H, int32_t relu_in,
                      void* stream) {
-  if (!feat::table_ok(x, kind, ldx) || ldx < H) return CSL_E_INVALID;
-  if (n_pad == 0) return CSL_OK;
-  if (n < 0 || n_pad < n || H < 4 || H % 4 != 0 || !cat || ldc < 2 * (int64_t)H || ldc % 4 != 0 || !aligned16(cat))
-    return CSL_E_INVALID;
-  if (n > 0) {
-    if (!self_ids) return CSL_E_INVALID;
-    if (!indptr && (!owned || !deg || !agg || lda < H || lda % 4 != 0 || !aligned16(agg))) return CSL_E_INVALID;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const int G = group_for(H);
-  DISPATCH_G_KIND(G, kind, k_sage_cat, n_pad, x, indptr, indices, self_ids, owned, deg, rowmap, x_e, (long long)ldx, agg,
-                  (long long)lda, (long long)n, (long long)n_pad, cat, (long long)ldc, (int)H, (int)relu_in);
-  return done();
+  if (!feat::kind_ok(kind)) return CSL_E_INVALID;
+  return rd::sage_cat(indptr, indices, self_ids, owned, deg, rowmap, x, kind, ldx, agg, lda, n, n_pad, cat, ldc, H, relu_in,
+                      stream);
 }
 
 int csl_sage_cat_bwd_f32(const int32_t* indptr, const int32_t* indices, const int32_t* self_ids, int64_t n,
@@ -1638,14 +1616,11 @@ int csl_sage_cat_bwd_t_f32(const int32_t* t_indptr, const int32_t* t_indices, co
     if (n_src > 0 && (!t_indptr || !t_indices || !gcat || ldg < 2 * (int64_t)H || ldg % 4 != 0 || !aligned16(gcat)))
       return CSL_E_INVALID;
     if (y && (ldy < H || ldy % 4 != 0 || !aligned16(y))) return CSL_E_INVALID;
-#define LAUNCH_BWD_T(G)                                                                                           \
-  hipLaunchKernelGGL(k_sage_cat_bwd_t<G>, dim3((unsigned)blocks), dim3(BLK), 0, st, t_indptr, t_indices, indptr, gcat, \
-                     (long long)ldg, y, (long long)ldy, (long long)n_src, (long long)n_pad, out, (long long)ldo, scratch, \
-                     (int)H, rpb, 0)
-    if (H > 128) LAUNCH_BWD_T(64);
-    else if (H > 64) LAUNCH_BWD_T(32);
-    else LAUNCH_BWD_T(16);
-#undef LAUNCH_BWD_T
+    with_groups<16, 64>(group_for(H), [&](auto g) {   // 16 lanes a row up to H = 64, 32 up to 128, 64 beyond
+      hipLaunchKernelGGL(k_sage_cat_bwd_t<g()>, dim3((unsigned)blocks), dim3(BLK), 0, st, t_indptr, t_indices, indptr, gcat,
+                         (long long)ldg, y, (long long)ldy, (long long)n_src, (long long)n_pad, out, (long long)ldo, scratch,
+                         (int)H, rpb, 0);
+    });
   }
   // colsum == NULL: the per-block sums stay in scratch[blocks][H] for the caller's own second stage (csl_reduce_multi_f32)
   if (colsum) hipLaunchKernelGGL(k_colsum_finish, dim3((unsigned)((H + 63) / 64)), dim3(BLK), 0, st, scratch, blocks, (int)H, colsum);
@@ -1659,8 +1634,10 @@ int csl_sage_rank_g2_f32(const int32_t* owned, const int32_t* deg, int64_t n_own
       ldg % 4 != 0 || ld2 % 4 != 0 || !aligned16(gcat) || !aligned16(g2))
     return CSL_E_INVALID;
   hipStream_t st = (hipStream_t)stream;
-  const int G = group_for(H);
-  DISPATCH_G(G, k_rank_g2, n_owned, owned, deg, (long long)n_owned, gcat, (long long)ldg, g2, (long long)ld2, (int)H);
+  with_groups<1, 64>(group_for(H), [&](auto g) {
+    hipLaunchKernelGGL(k_rank_g2<g()>, row_grid<g()>(n_owned), dim3(BLK), 0, st, owned, deg, (long long)n_owned, gcat,
+                       (long long)ldg, g2, (long long)ld2, (int)H);
+  });
   return done();
 }
 
@@ -1671,8 +1648,10 @@ int csl_scatter_rows_f32(float* dst, int64_t ldd, const int32_t* idx, int64_t n,
       !aligned16(dst) || !aligned16(src))
     return CSL_E_INVALID;
   hipStream_t st = (hipStream_t)stream;
-  const int G = group_for(H);
-  DISPATCH_G(G, k_scatter_rows_set, n, dst, (long long)ldd, idx, (long long)n, src, (long long)lds, (int)H);
+  with_groups<1, 64>(group_for(H), [&](auto g) {
+    hipLaunchKernelGGL(k_scatter_rows_set<g()>, row_grid<g()>(n), dim3(BLK), 0, st, dst, (long long)ldd, idx, (long long)n, src,
+                       (long long)lds, (int)H);
+  });
   return done();
 }
 
@@ -1697,21 +1676,16 @@ int csl_sage_cat_bwd_t_hub_f32(const int32_t* t_indptr, const int32_t* t_indices
     const int thr = CSL_T_SORTED_MAX;
     const long long segs = (t_entries + HUB_SEG - 1) / HUB_SEG;
     float* part2 = scratch + blocks * H;
-#define LAUNCH_HUB(G)                                                                                                  \
-  do {                                                                                                                 \
-    hipLaunchKernelGGL(k_sage_cat_bwd_t<G>, dim3((unsigned)blocks), dim3(BLK), 0, st, t_indptr, t_indices, indptr, gcat, \
-                       (long long)ldg, y, (long long)ldy, (long long)n_src, (long long)n_pad, out, (long long)ldo,     \
-                       scratch, (int)H, rpb, thr);                                                                     \
-    if (segs > 0 && n_src > 0)                                                                                         \
-      hipLaunchKernelGGL(k_sage_cat_bwd_t_hub<G>, dim3((unsigned)segs), dim3(BLK), 0, st, t_indptr, t_indices, indptr,  \
-                         gcat, (long long)ldg, (long long)n_src, out, (long long)ldo, (int)H, thr);                    \
-    hipLaunchKernelGGL(k_sage_cat_bwd_t_hubfin<G>, dim3((unsigned)blocks), dim3(BLK), 0, st, t_indptr, y, (long long)ldy, \
-                       (long long)n_src, out, (long long)ldo, part2, (int)H, rpb, thr);                                \
-  } while (0)
-    if (H > 128) LAUNCH_HUB(64);
-    else if (H > 64) LAUNCH_HUB(32);
-    else LAUNCH_HUB(16);
-#undef LAUNCH_HUB
+    with_groups<16, 64>(group_for(H), [&](auto g) {   // (the groups of csl_sage_cat_bwd_t_f32)
+      hipLaunchKernelGGL(k_sage_cat_bwd_t<g()>, dim3((unsigned)blocks), dim3(BLK), 0, st, t_indptr, t_indices, indptr, gcat,
+                         (long long)ldg, y, (long long)ldy, (long long)n_src, (long long)n_pad, out, (long long)ldo,
+                         scratch, (int)H, rpb, thr);
+      if (segs > 0 && n_src > 0)
+        hipLaunchKernelGGL(k_sage_cat_bwd_t_hub<g()>, dim3((unsigned)segs), dim3(BLK), 0, st, t_indptr, t_indices, indptr,
+                           gcat, (long long)ldg, (long long)n_src, out, (long long)ldo, (int)H, thr);
+      hipLaunchKernelGGL(k_sage_cat_bwd_t_hubfin<g()>, dim3((unsigned)blocks), dim3(BLK), 0, st, t_indptr, y, (long long)ldy,
+                         (long long)n_src, out, (long long)ldo, part2, (int)H, rpb, thr);
+    });
   }
   if (colsum) hipLaunchKernelGGL(k_colsum_finish, dim3((unsigned)((H + 63) / 64)), dim3(BLK), 0, st, scratch, 2 * blocks, (int)H, colsum);
   return done();
@@ -1725,20 +1699,12 @@ int csl_relu_bwd_colsum_f32(const float* g, int64_t ldg, const float* y, int64_t
   const long long blocks = (n_pad + rpb - 1) / rpb;
   if (blocks > 0) {
     if (!scratch || !out || ldo < H || (n > 0 && (!g || ldg < H)) || (y && ldy < H)) return CSL_E_INVALID;
-    const int G = group_for(H);
     const int vec = (H % 4 == 0) && (ldg % 4 == 0) && (ldo % 4 == 0) && (!y || ldy % 4 == 0) && aligned16(g) &&
                     aligned16(out) && (!y || aligned16(y));
-#define LAUNCH_RBC(GG)                                                                                         \
-  hipLaunchKernelGGL(k_relu_bwd_colsum<GG>, dim3((unsigned)blocks), dim3(BLK), 0, st, g, (long long)ldg, y,    \
-                     (long long)ldy, (long long)n, (long long)n_pad, out, (long long)ldo, scratch, (int)H, vec, rpb)
-    switch (G) {
-      case 1: case 2: case 4: LAUNCH_RBC(4); break;
-      case 8: LAUNCH_RBC(8); break;
-      case 16: LAUNCH_RBC(16); break;
-      case 32: LAUNCH_RBC(32); break;
-      default: LAUNCH_RBC(64); break;
-    }
-#undef LAUNCH_RBC
+    with_groups<4, 64>(group_for(H), [&](auto gr) {   // (a narrow row still gets 4 lanes)
+      hipLaunchKernelGGL(k_relu_bwd_colsum<gr()>, dim3((unsigned)blocks), dim3(BLK), 0, st, g, (long long)ldg, y,
+                         (long long)ldy, (long long)n, (long long)n_pad, out, (long long)ldo, scratch, (int)H, vec, rpb);
+    });
   }
   // colsum == NULL: the per-block sums stay in scratch[blocks][H] for the caller's own second stage
   if (colsum) hipLaunchKernelGGL(k_colsum_finish, dim3((unsigned)((H + 63) / 64)), dim3(BLK), 0, st, scratch, blocks, (int)H, colsum);
@@ -1868,6 +1834,8 @@ int csl_gat_logits_bwd_acc_f32(const float* z, const float* attn_l, const float*
   return done();
 }
 
+// gradient of csl_sage_cat_f32's merged-sums form: gx [n_x, H] and gagg [n_agg, H] are zeroed here, then
+// gx[self_ids[r]] = gcat[r, 0:H) and gagg[owned[r]] = gcat[r, H:2H) / max(deg[r], 1) (both index lists are unique)
 int csl_sage_cat_rows_bwd_f32(const int32_t* self_ids, const int32_t* owned, const int32_t* deg, int64_t n,
                               const float* gcat, int64_t ldg, float* gx, int64_t n_x, float* gagg, int64_t n_agg,
                               int32_t H, void* stream) {
@@ -1879,8 +1847,10 @@ int csl_sage_cat_rows_bwd_f32(const int32_t* self_ids, const int32_t* owned, con
   if (!self_ids || !owned || !deg || !gcat || ldg < 2 * (int64_t)H || ldg % 4 != 0 || !aligned16(gcat) ||
       (gx && !aligned16(gx)) || (gagg && !aligned16(gagg)))
     return CSL_E_INVALID;
-  const int G = group_for(H);
-  DISPATCH_G(G, k_sage_cat_rows_bwd, n, self_ids, owned, deg, (long long)n, gcat, (long long)ldg, gx, gagg, (int)H);
+  with_groups<1, 64>(group_for(H), [&](auto g) {
+    hipLaunchKernelGGL(k_sage_cat_rows_bwd<g()>, row_grid<g()>(n), dim3(BLK), 0, st, self_ids, owned, deg, (long long)n, gcat,
+                       (long long)ldg, gx, gagg, (int)H);
+  });
   return done();
 }
 

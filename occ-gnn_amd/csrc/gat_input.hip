@@ -25,6 +25,7 @@
 
 #include "cslicer_aggr.h"
 #include "cslicer_hip.h"
+#include "dev_common.h"
 
 namespace {
 
@@ -33,9 +34,6 @@ constexpr int RPB = BLK / 32;   // destination rows per block and pass
 constexpr int GATIN_MAX_DEG = 32;
 
 __device__ __forceinline__ float dot4(const float4 a, const float4 b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
-__device__ __forceinline__ void fma4(float4& acc, const float s, const float4 v) {
-  acc.x += s * v.x, acc.y += s * v.y, acc.z += s * v.z, acc.w += s * v.w;
-}
 
 // Sum of V values (V = 2^k <= 32) over the 32 lanes of a row group.  While more than one value is left a step halves
 // them: a lane keeps the half its bit selects and receives the partner's share of it.  Returns in lane q the total of
@@ -79,7 +77,8 @@ __device__ __forceinline__ float leaky(const float x, const float slope) { retur
 
 // A kernel instance covers rows of at most ME edges (a multiple of the 32 / H edges of a reduction group) and keeps their
 // feature rows in registers between its two passes over the edges: ME = 12 (48 registers) covers config 5's fanout of 10,
-// ME = 32 anything the layer accepts.
+// ME = 32 the largest max_deg the host accepts.  The host bounds only the caller's max_deg, it does not read the rows: one
+// with more than ME edges is marked by RowIdx::over below.
 
 // The index chain of a row, ONE hop per level for all its edges: lane q takes edge q (indices, then rowmap), the row ids are
 // handed out with shuffles.  (An edge at a time it was three dependent memory round trips per group of edges and again per
@@ -653,9 +652,6 @@ int bd_blocks() {   // workgroups of k_bd_proj / k_bd_dagg (CSL_BD_BLOCKS: measu
 int bd_kt(int F) { return F <= 64 ? 4 : (F <= 112 ? 7 : 8); }
 bool bd_ok(int H, int F, int D) { return (H == 1 || H == 2 || H == 4 || H == 8) && F >= 4 && F % 4 == 0 && F <= 128 && (D == 16 || D == 32 || D == 64); }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-int done() { return hipGetLastError() == hipSuccess ? CSL_OK : CSL_E_HIP; }
-
 long long bwd_rows(long long n) {   // destination rows per workgroup of k_gatin_bwd / k_elu_bwd_colsum: <= ~1024 workgroups
   long long rpb = (n + 1023) / 1024;
   rpb = (rpb + RPB - 1) / RPB * RPB;
@@ -726,7 +722,29 @@ int reduce_or_defer(int count, const float* const* src, const int64_t* nblk, con
   }
   return CSL_OK;
 }
-long long up4(long long v) { return (v + 3) / 4 * 4; }
+
+// (heads, max_deg) to the <heads, edges> instance of k_gatin_fwd / k_gatin_bwd.  ONE table: the backward reads the alpha the
+// forward wrote, in the layout of the forward's instance
+template <typename F>
+void with_gatin_instance(int H, int max_deg, F&& f) {
+  switch (H) {
+    case 1: f(int_c<1>{}, int_c<32>{}); break;
+    case 2: if (max_deg <= 16) f(int_c<2>{}, int_c<16>{}); else f(int_c<2>{}, int_c<32>{}); break;
+    case 4: if (max_deg <= 16) f(int_c<4>{}, int_c<16>{}); else f(int_c<4>{}, int_c<32>{}); break;
+    default: if (max_deg <= 12) f(int_c<8>{}, int_c<12>{}); else f(int_c<8>{}, int_c<32>{}); break;
+  }
+}
+
+// (bd_kt(F), D / 16) to the <k-chunks, column tiles> pair of k_bd_proj / k_bd_dagg; k_bd_dw takes its row loads from the
+// same pair (bd_ok: D / 16 is 1, 2 or 4)
+template <typename F>
+void with_bd_tile(int kt, int nt, F&& f) {
+  with_groups<1, 4>(nt, [&](auto n) {
+    if (kt == 4) f(int_c<4>{}, n);
+    else if (kt == 7) f(int_c<7>{}, n);
+    else f(int_c<8>{}, n);
+  });
+}
 
 }  // namespace
 
@@ -748,16 +766,10 @@ int csl_gat_in_fwd_f32(const int32_t* indptr, const int32_t* indices, const int3
   if (!indices || !alpha) return CSL_E_INVALID;
   long long need = (n_out + RPB - 1) / RPB;
   const unsigned blocks = (unsigned)(need < 768 ? need : 768);   // three workgroups per CU (all resident) walk the rows
-#define LAUNCH_GIF(HH, MM)                                                                                             \
-  hipLaunchKernelGGL((k_gatin_fwd<HH, MM>), dim3(blocks), dim3(BLK), 0, st, indptr, indices, self_ids, rowmap, x,          \
-                     (long long)ldx, (int)F, vl, vr, slope, (long long)n_out, agg, alpha)
-  switch (H) {
-    case 1: LAUNCH_GIF(1, 32); break;
-    case 2: if (max_deg <= 16) LAUNCH_GIF(2, 16); else LAUNCH_GIF(2, 32); break;
-    case 4: if (max_deg <= 16) LAUNCH_GIF(4, 16); else LAUNCH_GIF(4, 32); break;
-    default: if (max_deg <= 12) LAUNCH_GIF(8, 12); else LAUNCH_GIF(8, 32); break;
-  }
-#undef LAUNCH_GIF
+  with_gatin_instance(H, max_deg, [&](auto h, auto me) {
+    hipLaunchKernelGGL((k_gatin_fwd<h(), me()>), dim3(blocks), dim3(BLK), 0, st, indptr, indices, self_ids, rowmap, x,
+                       (long long)ldx, (int)F, vl, vr, slope, (long long)n_out, agg, alpha);
+  });
   return done();
 }
 
@@ -787,17 +799,11 @@ int csl_gat_in_bwd_f32(const int32_t* indptr, const int32_t* indices, const int3
   const long long blocks = (n_out + rpb - 1) / rpb;
   float* part_l = scratch;
   float* part_r = scratch + blocks * H * F;
-#define LAUNCH_GIB(HH, MM)                                                                                             \
-  hipLaunchKernelGGL((k_gatin_bwd<HH, MM>), dim3((unsigned)blocks), dim3(BLK), 0, st, indptr, indices, self_ids, rowmap, x, \
-                     (long long)ldx, (int)F, alpha, dagg, (long long)ld_r, (long long)ld_h, slope, (long long)n_out, rpb, \
-                     part_l, part_r)
-  switch (H) {
-    case 1: LAUNCH_GIB(1, 32); break;
-    case 2: if (max_deg <= 16) LAUNCH_GIB(2, 16); else LAUNCH_GIB(2, 32); break;
-    case 4: if (max_deg <= 16) LAUNCH_GIB(4, 16); else LAUNCH_GIB(4, 32); break;
-    default: if (max_deg <= 12) LAUNCH_GIB(8, 12); else LAUNCH_GIB(8, 32); break;
-  }
-#undef LAUNCH_GIB
+  with_gatin_instance(H, max_deg, [&](auto h, auto me) {
+    hipLaunchKernelGGL((k_gatin_bwd<h(), me()>), dim3((unsigned)blocks), dim3(BLK), 0, st, indptr, indices, self_ids, rowmap, x,
+                       (long long)ldx, (int)F, alpha, dagg, (long long)ld_r, (long long)ld_h, slope, (long long)n_out, rpb,
+                       part_l, part_r);
+  });
   if (hipGetLastError() != hipSuccess) return CSL_E_HIP;
   const float* src[2] = {part_l, part_r};
   const int64_t nblk[2] = {blocks, blocks};
@@ -845,20 +851,6 @@ int csl_elu_bwd_colsum_f32(const float* g, int64_t ldg, const float* y, int64_t 
 int32_t csl_gat_in_proj_ok(int32_t H, int32_t F, int32_t D) { return bd_ok(H, F, D) ? 1 : 0; }
 int32_t csl_gat_in_proj_fpad(int32_t F) { return 16 * bd_kt(F); }
 
-#define BD_DISPATCH(KERNEL, ...)                                                                   \
-  do {                                                                                             \
-    const int kt = bd_kt(F), nt = D / 16;                                                          \
-    if (kt == 4 && nt == 1) hipLaunchKernelGGL((KERNEL<4, 1>), grid, block, 0, st, __VA_ARGS__);   \
-    else if (kt == 4 && nt == 2) hipLaunchKernelGGL((KERNEL<4, 2>), grid, block, 0, st, __VA_ARGS__); \
-    else if (kt == 4) hipLaunchKernelGGL((KERNEL<4, 4>), grid, block, 0, st, __VA_ARGS__);         \
-    else if (kt == 7 && nt == 1) hipLaunchKernelGGL((KERNEL<7, 1>), grid, block, 0, st, __VA_ARGS__); \
-    else if (kt == 7 && nt == 2) hipLaunchKernelGGL((KERNEL<7, 2>), grid, block, 0, st, __VA_ARGS__); \
-    else if (kt == 7) hipLaunchKernelGGL((KERNEL<7, 4>), grid, block, 0, st, __VA_ARGS__);         \
-    else if (nt == 1) hipLaunchKernelGGL((KERNEL<8, 1>), grid, block, 0, st, __VA_ARGS__);         \
-    else if (nt == 2) hipLaunchKernelGGL((KERNEL<8, 2>), grid, block, 0, st, __VA_ARGS__);         \
-    else hipLaunchKernelGGL((KERNEL<8, 4>), grid, block, 0, st, __VA_ARGS__);                      \
-  } while (0)
-
 int csl_gat_in_proj_f32(const float* agg, const float* W, const float* bias, int64_t n, int32_t H, int32_t F, int32_t D,
                         int32_t elu, float* out, int64_t ldo, void* stream) {
   if (n < 0 || !bd_ok(H, F, D) || ldo < (int64_t)H * D) return CSL_E_INVALID;
@@ -866,7 +858,10 @@ int csl_gat_in_proj_f32(const float* agg, const float* W, const float* bias, int
   if (!agg || !W || !bias || !out || !aligned16(agg) || !aligned16(W)) return CSL_E_INVALID;
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid(bd_blocks()), block(64 * BD_WAVES);
-  BD_DISPATCH(k_bd_proj, agg, W, bias, out, (long long)ldo, (long long)n, (int)H, (int)F, (int)elu);
+  with_bd_tile(bd_kt(F), D / 16, [&](auto kt, auto nt) {
+    hipLaunchKernelGGL((k_bd_proj<kt(), nt()>), grid, block, 0, st, agg, W, bias, out, (long long)ldo, (long long)n, (int)H,
+                       (int)F, (int)elu);
+  });
   return done();
 }
 
@@ -891,20 +886,16 @@ int csl_gat_in_proj_bwd_f32(const float* gg, int64_t ldg, const float* agg, cons
       !aligned16(gW))
     return CSL_E_INVALID;
   const dim3 grid(bd_blocks()), block(64 * BD_WAVES);
-  BD_DISPATCH(k_bd_dagg, gg, (long long)ldg, W, dagg, (long long)n, (int)H, (int)F);
   const long long ranges = (long long)bd_dw_blocks() * BD_WAVES / H;
   long long rows_per = (n + ranges - 1) / ranges;
   rows_per = (rows_per + 15) / 16 * 16;
   const dim3 grid_dw((unsigned)bd_dw_blocks());
-#define LAUNCH_DW(FF, NN)                                                                                          \
-  hipLaunchKernelGGL((k_bd_dw<FF, NN>), grid_dw, block, 0, st, gg, (long long)ldg, agg, scratch, (long long)n, (int)H, (int)F, \
-                     rows_per)
-  if (F <= 64) {
-    if (D == 16) LAUNCH_DW(1, 1); else if (D == 32) LAUNCH_DW(1, 2); else LAUNCH_DW(1, 4);
-  } else {
-    if (D == 16) LAUNCH_DW(2, 1); else if (D == 32) LAUNCH_DW(2, 2); else LAUNCH_DW(2, 4);
-  }
-#undef LAUNCH_DW
+  with_bd_tile(bd_kt(F), D / 16, [&](auto kt, auto nt) {
+    constexpr int FT = kt() == 4 ? 1 : 2;   // float4 loads per row: F <= 64 is bd_kt(F) == 4
+    hipLaunchKernelGGL((k_bd_dagg<kt(), nt()>), grid, block, 0, st, gg, (long long)ldg, W, dagg, (long long)n, (int)H, (int)F);
+    hipLaunchKernelGGL((k_bd_dw<FT, nt()>), grid_dw, block, 0, st, gg, (long long)ldg, agg, scratch, (long long)n, (int)H,
+                       (int)F, rows_per);
+  });
   if (hipGetLastError() != hipSuccess) return CSL_E_HIP;
   const float* src[1] = {scratch};
   const int64_t nblk[1] = {ranges};

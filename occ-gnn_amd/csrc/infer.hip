@@ -284,7 +284,7 @@ int sage_launch(const int32_t* indptr, const int32_t* indices, const int32_t* it
   const int G = groups_for(W / 4);
   const int rl = relu != 0, pj = proj != 0;
   if (n_items)
-    with_groups(G, [&](auto g) {
+    with_groups<1, 16>(G, [&](auto g) {
       hipLaunchKernelGGL((k_infer_sage<g(), E>), dim3(blocks_of(n_items)), dim3(BLK), 0, st, indptr, indices,
                          reinterpret_cast<const int4*>(items), (long long)n_items, (long long)pos0, (long long)part0, x,
                          (long long)ldx, (int)W, pj, bias, rl, partial, out, (long long)ldo);
@@ -318,7 +318,7 @@ int csl_infer_sage_f32(const int32_t* indptr, const int32_t* indices, const int3
   if (!sage_args_ok(indptr, indices, items, n_items, hubs, n_hubs, pos0, part0, ldx, W, proj, partial, ldo))
     return CSL_E_INVALID;
   if (n_items == 0 && n_hubs == 0) return CSL_OK;
-  if (!x || !out || !al16(x) || !al16(out) || (bias && !al16(bias))) return CSL_E_INVALID;
+  if (!x || !out || !aligned16(x) || !aligned16(out) || (bias && !aligned16(bias))) return CSL_E_INVALID;
   return sage_launch<float>(indptr, indices, items, n_items, hubs, n_hubs, pos0, part0, x, ldx, W, proj, bias, relu, partial,
                             out, ldo, stream);
 }
@@ -331,7 +331,7 @@ int csl_infer_sage_x16(const int32_t* indptr, const int32_t* indices, const int3
   if (!sage_args_ok(indptr, indices, items, n_items, hubs, n_hubs, pos0, part0, ldx, W, 0, partial, ldo))
     return CSL_E_INVALID;
   if (n_items == 0 && n_hubs == 0) return CSL_OK;
-  if (!out || !al16(out) || (bias && !al16(bias))) return CSL_E_INVALID;
+  if (!out || !aligned16(out) || (bias && !aligned16(bias))) return CSL_E_INVALID;
   return with_elem(kind, [&](auto e) {
     typedef typename decltype(e)::type E;
     return sage_launch(indptr, indices, items, n_items, hubs, n_hubs, pos0, part0, static_cast<const E*>(x), ldx, W, 0, bias,
@@ -345,7 +345,7 @@ int csl_upcast_rows_x16(const void* src, int32_t kind, int64_t lds, int64_t n, f
       n >= (1ll << 31))
     return CSL_E_INVALID;
   if (n == 0) return CSL_OK;
-  if (!dst || !al16(dst)) return CSL_E_INVALID;
+  if (!dst || !aligned16(dst)) return CSL_E_INVALID;
   with_elem(kind, [&](auto e) { upcast_launch<typename decltype(e)::type>(src, lds, n, dst, ldd, H, (hipStream_t)stream); });
   return done();
 }
@@ -363,7 +363,7 @@ int csl_infer_gat_f32(const int32_t* indptr, const int32_t* indices, const int32
   if (H < 1 || D < 4 || D % 4 != 0 || (int64_t)H * D > (last ? GAT_LAST_MAX_C : GAT_MAX_C)) return CSL_E_INVALID;
   if (last ? (n_cls < 1 || n_cls > D || ldo < n_cls) : (ldo % 4 != 0 || ldo < (int64_t)H * D)) return CSL_E_INVALID;
   if (n_items == 0 && n_hubs == 0) return CSL_OK;
-  if (!z || !el || !er || !out || !al16(z) || (!last && !al16(out)) || (bias && !al16(bias))) return CSL_E_INVALID;
+  if (!z || !el || !er || !out || !aligned16(z) || (!last && !aligned16(out)) || (bias && !aligned16(bias))) return CSL_E_INVALID;
   hipStream_t st = (hipStream_t)stream;
   const int C = H * D;
   const int G = groups_for(C / 4);
@@ -371,7 +371,7 @@ int csl_infer_gat_f32(const int32_t* indptr, const int32_t* indices, const int32
   const size_t shmem = last ? (size_t)WPB * C * sizeof(float) : 0;
   const int ls = last != 0;
   if (n_items)
-    with_groups(G, [&](auto g) {
+    with_groups<1, 16>(G, [&](auto g) {
       hipLaunchKernelGGL(k_infer_gat<g()>, dim3(blocks_of(n_items)), dim3(BLK), shmem, st, indptr, indices,
                          reinterpret_cast<const int4*>(items), (long long)n_items, (long long)pos0, (long long)part0, z, el,
                          er, (int)H, (int)D, slope, bias, ls, (int)n_cls, partial, pld, out, (long long)ldo);

@@ -1,5 +1,5 @@
-// infer_dev.h -- what csrc/infer.hip and csrc/infer_parts.hip share (private to csrc/): the launch constants, the float4
-// element helpers, the ROW ENDS of both models and the host helpers of their entry points.  A row is finished by the
+// infer_dev.h -- what csrc/infer.hip and csrc/infer_parts.hip share beyond csrc/dev_common.h (private to csrc/): the
+// launch constants, the float4 element helpers, the ROW ENDS of both models and the host helpers of their entry points.  A row is finished by the
 // same code whether one process summed it or the ranks' partials were merged, so with one part the rank path rounds as
 // the single-process path does: the bitwise promise of include/cslicer_infer_parts.h rests on this file being the only
 // home of these functions.
@@ -15,6 +15,7 @@
 #include "cslicer_hip.h"
 #include "cslicer_infer.h"
 #include "cslicer_infer16.h"
+#include "dev_common.h"
 #include "feat_elem.h"
 
 namespace {
@@ -29,11 +30,7 @@ constexpr long long GAT_MAX_C = 1ll << 24;  // H * D of a hidden layer (nothing 
 __device__ __forceinline__ float4 f4zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void st4(float* p, const float4 v) { *reinterpret_cast<float4*>(p) = v; }
-__device__ __forceinline__ void add4(float4& a, const float4 b) { a.x += b.x, a.y += b.y, a.z += b.z, a.w += b.w; }
 __device__ __forceinline__ void scale4(float4& a, const float s) { a.x *= s, a.y *= s, a.z *= s, a.w *= s; }
-__device__ __forceinline__ void fma4(float4& a, const float s, const float4 b) {
-  a.x += s * b.x, a.y += s * b.y, a.z += s * b.z, a.w += s * b.w;
-}
 __device__ __forceinline__ float4 shfl_xor4(const float4 v, const int d) {
   return make_float4(__shfl_xor(v.x, d), __shfl_xor(v.y, d), __shfl_xor(v.z, d), __shfl_xor(v.w, d));
 }
@@ -118,8 +115,6 @@ __device__ __forceinline__ void gat_head_mean(const float* stage, int H, int D, 
 
 // ---------------------------------------------------------------- host side
 
-bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-int done() { return hipGetLastError() == hipSuccess ? CSL_OK : CSL_E_HIP; }
 unsigned blocks_of(long long n, int per_wave = 1) {
   return (unsigned)((n + (long long)WPB * per_wave - 1) / ((long long)WPB * per_wave));
 }
@@ -137,54 +132,19 @@ bool plan_ok(const int32_t* indptr, const int32_t* indices, const int32_t* items
              int64_t n_hubs, int64_t pos0, int64_t part0, const void* partial, bool hubs_read_indptr) {
   if (n_items < 0 || n_hubs < 0 || pos0 < 0 || part0 < 0 || n_items >= (1ll << 31) * WPB || n_hubs >= (1ll << 31) * WPB)
     return false;
-  if (n_items && (!indptr || !indices || !items || !al16(items))) return false;
-  if (n_hubs && ((hubs_read_indptr && !indptr) || !hubs || !al16(hubs) || !partial || !al16(partial))) return false;
+  if (n_items && (!indptr || !indices || !items || !aligned16(items))) return false;
+  if (n_hubs && ((hubs_read_indptr && !indptr) || !hubs || !aligned16(hubs) || !partial || !aligned16(partial))) return false;
   return true;
 }
 
-// The launch dispatchers: a run-time group count G (and rows per wave R, element kind) to a compile-time one.  f is a
-// generic lambda that names its kernel with its own template arguments, e.g.
-//   with_groups(G, [&](auto g) { hipLaunchKernelGGL((k<g(), E>), ...); });
-template <int V>
-using int_c = std::integral_constant<int, V>;
-template <typename E>
-struct elem_c { typedef E type; };
-
-template <typename F>
-void with_groups(int G, F&& f) {
-  switch (G) {
-    case 1: f(int_c<1>{}); break;
-    case 2: f(int_c<2>{}); break;
-    case 4: f(int_c<4>{}); break;
-    case 8: f(int_c<8>{}); break;
-    default: f(int_c<16>{}); break;
-  }
-}
-
-// the (G, R) pairs in which a group keeps at least 4 lanes (pack_for)
+// a group count G and the rows per wave R to compile-time ones (int_c and with_groups for G alone: csrc/dev_common.h):
+// the (G, R) pairs in which a group keeps at least 4 lanes (pack_for): R <= 4, 2 and 1 for G <= 4, 8 and 16
 template <typename F>
 void with_groups_rows(int G, int R, F&& f) {
-  switch (G * 8 + R) {
-    case 1 * 8 + 1: f(int_c<1>{}, int_c<1>{}); break;
-    case 1 * 8 + 2: f(int_c<1>{}, int_c<2>{}); break;
-    case 1 * 8 + 4: f(int_c<1>{}, int_c<4>{}); break;
-    case 2 * 8 + 1: f(int_c<2>{}, int_c<1>{}); break;
-    case 2 * 8 + 2: f(int_c<2>{}, int_c<2>{}); break;
-    case 2 * 8 + 4: f(int_c<2>{}, int_c<4>{}); break;
-    case 4 * 8 + 1: f(int_c<4>{}, int_c<1>{}); break;
-    case 4 * 8 + 2: f(int_c<4>{}, int_c<2>{}); break;
-    case 4 * 8 + 4: f(int_c<4>{}, int_c<4>{}); break;
-    case 8 * 8 + 1: f(int_c<8>{}, int_c<1>{}); break;
-    case 8 * 8 + 2: f(int_c<8>{}, int_c<2>{}); break;
-    default: f(int_c<16>{}, int_c<1>{}); break;
-  }
-}
-
-// a 16-bit table's element kind (checked by the caller: feat::table_ok) to its element type
-template <typename F>
-auto with_elem(int32_t kind, F&& f) {
-  if (kind == CSL_FEAT_F16) return f(elem_c<feat::f16>{});
-  return f(elem_c<feat::bf16>{});
+  with_groups<1, 16>(G, [&](auto g) {
+    constexpr int RMAX = g() <= 4 ? 4 : 16 / g();
+    with_groups<1, RMAX>(R, [&](auto r) { f(g, r); });
+  });
 }
 
 }  // namespace

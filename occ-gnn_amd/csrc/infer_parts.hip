@@ -232,7 +232,7 @@ __global__ __launch_bounds__(BLK) void k_gat_merge(const int* __restrict__ lists
   if (last) gat_head_mean(stage, H, D, n_cls, out, ldo, i, lane);
 }
 
-// ---------------------------------------------------------------- host side (al16 .. plan_ok, with_*: csrc/infer_dev.h)
+// ---------------------------------------------------------------- host side (plan_ok, with_*: infer_dev.h, dev_common.h)
 
 // rows per wave: as asked, but a group keeps at least 4 lanes
 int pack_for(int G, int pack) {
@@ -243,7 +243,7 @@ int pack_for(int G, int pack) {
 
 bool merge_ok(const int32_t* lists, int64_t n, int32_t P, const float* recv) {
   if (n < 0 || P < 1 || n >= (1ll << 31) * WPB) return false;
-  if (n && (!lists || !recv || !al16(recv))) return false;
+  if (n && (!lists || !recv || !aligned16(recv))) return false;
   return true;
 }
 
@@ -286,7 +286,7 @@ int sage_merge_launch(const int32_t* dst, const int32_t* lists, int64_t n, int32
                       void* stream) {
   hipStream_t st = (hipStream_t)stream;
   const int G = groups_for(W / 4);
-  with_groups(G, [&](auto g) {
+  with_groups<1, 16>(G, [&](auto g) {
     hipLaunchKernelGGL((k_sage_merge<g(), E>), dim3(blocks_of(n, G)), dim3(BLK), 0, st,
                        reinterpret_cast<const int2*>(dst), lists, (long long)n, (int)P, recv, x, (long long)ldx, (int)W,
                        proj != 0, bias, relu != 0, out, (long long)ldo);
@@ -303,7 +303,7 @@ int csl_infer_sage_part_f32(const int32_t* indptr, const int32_t* indices, const
                             int32_t W, int32_t pack, float* partial, float* send, void* stream) {
   if (!sage_part_ok(indptr, indices, items, n_items, hubs, n_hubs, pos0, part0, ldy, W, pack, partial)) return CSL_E_INVALID;
   if (n_items == 0 && n_hubs == 0) return CSL_OK;
-  if (!y || !send || !al16(y) || !al16(send)) return CSL_E_INVALID;
+  if (!y || !send || !aligned16(y) || !aligned16(send)) return CSL_E_INVALID;
   return sage_part_launch<float>(indptr, indices, items, n_items, hubs, n_hubs, pos0, part0, y, ldy, W, pack, partial, send,
                                  stream);
 }
@@ -314,7 +314,7 @@ int csl_infer_sage_part_x16(const int32_t* indptr, const int32_t* indices, const
   if (!feat::table_ok(y, kind, ldy)) return CSL_E_INVALID;
   if (!sage_part_ok(indptr, indices, items, n_items, hubs, n_hubs, pos0, part0, ldy, W, pack, partial)) return CSL_E_INVALID;
   if (n_items == 0 && n_hubs == 0) return CSL_OK;
-  if (!send || !al16(send)) return CSL_E_INVALID;
+  if (!send || !aligned16(send)) return CSL_E_INVALID;
   return with_elem(kind, [&](auto e) {
     typedef typename decltype(e)::type E;
     return sage_part_launch(indptr, indices, items, n_items, hubs, n_hubs, pos0, part0, static_cast<const E*>(y), ldy, W,
@@ -327,7 +327,7 @@ int csl_infer_sage_merge_f32(const int32_t* dst, const int32_t* lists, int64_t n
                              float* out, int64_t ldo, void* stream) {
   if (!sage_merge_ok(lists, n, P, recv, ldx, W, proj, ldo)) return CSL_E_INVALID;
   if (n == 0) return CSL_OK;
-  if (!dst || (reinterpret_cast<uintptr_t>(dst) & 7u) || !x || !out || !al16(x) || !al16(out) || (bias && !al16(bias)))
+  if (!dst || (reinterpret_cast<uintptr_t>(dst) & 7u) || !x || !out || !aligned16(x) || !aligned16(out) || (bias && !aligned16(bias)))
     return CSL_E_INVALID;
   return sage_merge_launch<float>(dst, lists, n, P, recv, x, ldx, W, proj, bias, relu, out, ldo, stream);
 }
@@ -338,7 +338,7 @@ int csl_infer_sage_merge_x16(const int32_t* dst, const int32_t* lists, int64_t n
   if (!feat::table_ok(x, kind, ldx) || proj != 0) return CSL_E_INVALID;
   if (!sage_merge_ok(lists, n, P, recv, ldx, W, 0, ldo)) return CSL_E_INVALID;
   if (n == 0) return CSL_OK;
-  if (!dst || (reinterpret_cast<uintptr_t>(dst) & 7u) || !out || !al16(out) || (bias && !al16(bias))) return CSL_E_INVALID;
+  if (!dst || (reinterpret_cast<uintptr_t>(dst) & 7u) || !out || !aligned16(out) || (bias && !aligned16(bias))) return CSL_E_INVALID;
   return with_elem(kind, [&](auto e) {
     typedef typename decltype(e)::type E;
     return sage_merge_launch(dst, lists, n, P, recv, static_cast<const E*>(x), ldx, W, 0, bias, relu, out, ldo, stream);
@@ -352,7 +352,7 @@ int csl_infer_gat_part_f32(const int32_t* indptr, const int32_t* indices, const 
   if (!plan_ok(indptr, indices, items, n_items, hubs, n_hubs, pos0, part0, partial, false)) return CSL_E_INVALID;
   if (H < 1 || D < 4 || D % 4 != 0 || (int64_t)H * D > GAT_MAX_C || pack < 1) return CSL_E_INVALID;
   if (n_items == 0 && n_hubs == 0) return CSL_OK;
-  if (!z || !el || !er_rows || !send || !al16(z) || !al16(send)) return CSL_E_INVALID;
+  if (!z || !el || !er_rows || !send || !aligned16(z) || !aligned16(send)) return CSL_E_INVALID;
   hipStream_t st = (hipStream_t)stream;
   const int G = groups_for(H * D / 4), R = pack_for(G, pack);
   const long long pld = csl_infer_gat_partial_ld(H, D);
@@ -374,7 +374,7 @@ int csl_infer_gat_merge_f32(const int32_t* lists, int64_t n, int32_t P, const fl
   if (H < 1 || D < 4 || D % 4 != 0 || (int64_t)H * D > (last ? GAT_LAST_MAX_C : GAT_MAX_C)) return CSL_E_INVALID;
   if (last ? (n_cls < 1 || n_cls > D || ldo < n_cls) : (ldo % 4 != 0 || ldo < (int64_t)H * D)) return CSL_E_INVALID;
   if (n == 0) return CSL_OK;
-  if (!out || (!last && !al16(out)) || (bias && !al16(bias))) return CSL_E_INVALID;
+  if (!out || (!last && !aligned16(out)) || (bias && !aligned16(bias))) return CSL_E_INVALID;
   hipStream_t st = (hipStream_t)stream;
   const long long pld = csl_infer_gat_partial_ld(H, D);
   const size_t shmem = last ? (size_t)WPB * H * D * sizeof(float) : 0;

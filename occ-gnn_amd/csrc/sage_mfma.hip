@@ -43,7 +43,9 @@
 #include "cslicer_aggr.h"
 #include "cslicer_feat16.h"
 #include "cslicer_hip.h"
+#include "dev_common.h"
 #include "feat_elem.h"
+#include "table_readers.h"
 
 namespace {
 
@@ -589,17 +591,30 @@ int launch(const FwdArgs& a, unsigned grid, size_t lds, hipStream_t st) {
     attr_lds = lds;
   }
   hipLaunchKernelGGL((k_sage_fwd_mfma<KS, KL, STREAM, E>), dim3(grid), dim3(TBP), lds, st, a);
-  return hipGetLastError() == hipSuccess ? CSL_OK : CSL_E_HIP;
+  return done();
 }
 
-// the layer behind csl_sage_fwd_mfma_f32 (E = float) and csl_sage_fwd_mfma_x16: arguments checked by the caller
-template <typename E>
-int fwd_mfma(const int32_t* indptr, const int32_t* indices, const int32_t* self_ids, const int32_t* rowmap, const void* x,
-             int64_t ldx, const float* W, int64_t ldw, const float* bias, int64_t n, int64_t n_pad, int32_t H, int32_t out,
-             int32_t relu_in, int32_t relu_out, float* cat, int64_t ldc, float* y, int64_t ldy, float* wpack, void* stream) {
+}  // namespace
+
+// the layer behind csl_sage_fwd_mfma_f32 (kind 0) and csl_sage_fwd_mfma_x16 (table_readers.h)
+int rd::sage_fwd_mfma(const int32_t* indptr, const int32_t* indices, const int32_t* self_ids, const int32_t* rowmap,
+                      const void* x, int32_t kind, int64_t ldx, const float* W, int64_t ldw, const float* bias, int64_t n,
+                      int64_t n_pad, int32_t H, int32_t out, int32_t relu_in, int32_t relu_out, float* cat, int64_t ldc,
+                      float* y, int64_t ldy, float* wpack, void* stream) {
+  // (a 16-bit table is checked first, and whatever n is: a lane's 8-byte load needs an 8-byte aligned base and rows of
+  // whole quads)
+  if (rd::table16_bad(x, kind, ldx, H)) return CSL_E_INVALID;
+  if (n_pad == 0) return CSL_OK;
+  // what is refused whatever the table's kind (everything but the table itself)
+  if (n < 0 || n_pad < n || H < 4 || H % 4 != 0 || out < 1 || out > 256 || !W || ldw < 2 * (int64_t)H || ldw % 4 != 0 ||
+      !y || ldy < out || !wpack || !aligned16(W) || !aligned16(wpack))
+    return CSL_E_INVALID;
+  if (cat && (ldc < 2 * (int64_t)H || ldc % 4 != 0 || !aligned16(cat))) return CSL_E_INVALID;
   int KS, KL;
   split_for(2 * H / 8, KS, KL);
   const size_t lds = lds_for(H, out, KL);
+  if (lds > 160 * 1024 - 64 || (n_pad + BM - 1) / BM > 0x7fffffffLL / BM) return CSL_E_INVALID;
+  if (n > 0 && (!indptr || !self_ids || (kind == 0 && (!x || ldx < H || ldx % 4 != 0 || !aligned16(x))))) return CSL_E_INVALID;
   int dbg = 0;
   {
     const char* e = getenv("CSLICER_MFMA_DBG");
@@ -635,28 +650,15 @@ int fwd_mfma(const int32_t* indptr, const int32_t* indices, const int32_t* self_
   }
   a.dbg = dbg;
   const unsigned grid = (unsigned)(a.n_tiles < n_cu ? a.n_tiles : n_cu);
-  if (KQ == 25) return launch<19, 6, false, E>(a, grid, lds, st);
-  if (KQ == 24) return launch<18, 6, false, E>(a, grid, lds, st);
-  if (KQ == 16) return launch<16, 0, false, E>(a, grid, lds, st);
-  if (KQ > 16) return launch<16, 0, true, E>(a, grid, lds, st);
-  return launch<0, 0, true, E>(a, grid, lds, st);
+  return with_table(kind, [&](auto e) {
+    typedef typename decltype(e)::type E;
+    if (KQ == 25) return launch<19, 6, false, E>(a, grid, lds, st);
+    if (KQ == 24) return launch<18, 6, false, E>(a, grid, lds, st);
+    if (KQ == 16) return launch<16, 0, false, E>(a, grid, lds, st);
+    if (KQ > 16) return launch<16, 0, true, E>(a, grid, lds, st);
+    return launch<0, 0, true, E>(a, grid, lds, st);
+  });
 }
-
-// what csl_sage_fwd_mfma_f32 and its 16-bit twin refuse alike (everything but the table itself); no HIP call
-inline bool fwd_mfma_shape_ok(int64_t n, int64_t n_pad, int32_t H, int32_t out, const float* W, int64_t ldw, const float* y,
-                              int64_t ldy, const float* wpack, const float* cat, int64_t ldc) {
-  if (n < 0 || n_pad < n || H < 4 || H % 4 != 0 || out < 1 || out > 256 || !W || ldw < 2 * (int64_t)H || ldw % 4 != 0 ||
-      !y || ldy < out || !wpack || ((uintptr_t)W & 15) || ((uintptr_t)wpack & 15))
-    return false;
-  if (cat && (ldc < 2 * (int64_t)H || ldc % 4 != 0 || ((uintptr_t)cat & 15))) return false;
-  int KS, KL;
-  split_for(2 * H / 8, KS, KL);
-  if (lds_for(H, out, KL) > 160 * 1024 - 64) return false;
-  if ((n_pad + BM - 1) / BM > 0x7fffffffLL / BM) return false;
-  return true;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -671,27 +673,17 @@ int csl_sage_fwd_mfma_f32(const int32_t* indptr, const int32_t* indices, const i
                           const float* x, int64_t ldx, const float* W, int64_t ldw, const float* bias, int64_t n,
                           int64_t n_pad, int32_t H, int32_t out, int32_t relu_in, int32_t relu_out, float* cat,
                           int64_t ldc, float* y, int64_t ldy, float* wpack, void* stream) {
-  if (n_pad == 0) return CSL_OK;
-  if (!fwd_mfma_shape_ok(n, n_pad, H, out, W, ldw, y, ldy, wpack, cat, ldc)) return CSL_E_INVALID;
-  if (n > 0 && (!indptr || !self_ids || !x || ldx < H || ldx % 4 != 0 || ((uintptr_t)x & 15))) return CSL_E_INVALID;
-  return fwd_mfma<float>(indptr, indices, self_ids, rowmap, x, ldx, W, ldw, bias, n, n_pad, H, out, relu_in, relu_out, cat,
-                         ldc, y, ldy, wpack, stream);
+  return rd::sage_fwd_mfma(indptr, indices, self_ids, rowmap, x, 0, ldx, W, ldw, bias, n, n_pad, H, out, relu_in, relu_out, cat,
+                           ldc, y, ldy, wpack, stream);
 }
 
 int csl_sage_fwd_mfma_x16(const int32_t* indptr, const int32_t* indices, const int32_t* self_ids, const int32_t* rowmap,
                           const void* x, int32_t kind, int64_t ldx, const float* W, int64_t ldw, const float* bias,
                           int64_t n, int64_t n_pad, int32_t H, int32_t out, int32_t relu_in, int32_t relu_out, float* cat,
                           int64_t ldc, float* y, int64_t ldy, float* wpack, void* stream) {
-  // (the table is checked first, and whatever n is: a lane's 8-byte load needs an 8-byte aligned base and rows of whole quads)
-  if (!feat::table_ok(x, kind, ldx) || ldx < H) return CSL_E_INVALID;
-  if (n_pad == 0) return CSL_OK;
-  if (!fwd_mfma_shape_ok(n, n_pad, H, out, W, ldw, y, ldy, wpack, cat, ldc)) return CSL_E_INVALID;
-  if (n > 0 && (!indptr || !self_ids)) return CSL_E_INVALID;
-  if (kind == CSL_FEAT_F16)
-    return fwd_mfma<feat::f16>(indptr, indices, self_ids, rowmap, x, ldx, W, ldw, bias, n, n_pad, H, out, relu_in, relu_out,
-                               cat, ldc, y, ldy, wpack, stream);
-  return fwd_mfma<feat::bf16>(indptr, indices, self_ids, rowmap, x, ldx, W, ldw, bias, n, n_pad, H, out, relu_in, relu_out,
-                              cat, ldc, y, ldy, wpack, stream);
+  if (!feat::kind_ok(kind)) return CSL_E_INVALID;
+  return rd::sage_fwd_mfma(indptr, indices, self_ids, rowmap, x, kind, ldx, W, ldw, bias, n, n_pad, H, out, relu_in, relu_out,
+                           cat, ldc, y, ldy, wpack, stream);
 }
 
 }  // extern "C"

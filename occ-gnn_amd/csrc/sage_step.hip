@@ -28,7 +28,9 @@
 #include "cslicer_aggr.h"
 #include "cslicer_feat16.h"
 #include "cslicer_hip.h"
+#include "dev_common.h"
 #include "feat_elem.h"
+#include "table_readers.h"
 
 namespace {
 
@@ -44,7 +46,6 @@ inline int64_t pad_rows(int64_t m, int64_t row_pad) {
   const int64_t q = m >= row_pad ? row_pad : (row_pad < 256 ? row_pad : 256);
   return (m + q - 1) / q * q;
 }
-inline int64_t up4(int64_t x) { return (x + 3) & ~(int64_t)3; }  // every buffer starts 16-byte aligned
 
 struct Layout {
   int64_t cat[CSL_MAX_LAYERS], y[CSL_MAX_LAYERS], gy[CSL_MAX_LAYERS], gcat[CSL_MAX_LAYERS], mp[CSL_MAX_LAYERS];
@@ -138,7 +139,7 @@ struct SpanGuard {   // records e0 now and e1 when it goes out of scope
   hipStream_t st;
   TimedSpan sp;
   bool on;
-  SpanGuard(int group, void* stream) : st((hipStream_t)stream), on(g_timing) {
+  SpanGuard(int group, void* stream) : st((hipStream_t)stream), on(g_timing && group >= 0) {   // (group < 0: untimed)
     if (!on) return;
     std::lock_guard<std::mutex> lk(g_tmu);
     sp.group = group, sp.e0 = take_event(), sp.e1 = take_event();
@@ -166,36 +167,66 @@ struct SpanGuard {   // records e0 now and e1 when it goes out of scope
     }                                                                        \
   } while (0)
 
-// ---- the resident feature table: float32 (kind 0: csl_sage_fwd_bwd_f32, csl_sage_rank_fwd_bwd_f32) or 16-bit elements
-// (CSL_FEAT_F16 / CSL_FEAT_BF16: the _x16 twins, cslicer_feat16.h).  Only the deepest layer's forward reads it; each of
-// its three readers has both forms, and everything downstream of them is fp32 either way.
-inline int feat_fwd_mfma(int32_t kind, const int32_t* indptr, const int32_t* indices, const int32_t* self_ids,
-                         const int32_t* rowmap, const void* x, int64_t ldx, const float* W, int64_t ldw, const float* bias,
-                         int64_t n, int64_t n_pad, int32_t H, int32_t out, int32_t relu_in, int32_t relu_out, float* cat,
-                         int64_t ldc, float* y, int64_t ldy, float* wpack, void* stream) {
-  if (kind == 0)
-    return csl_sage_fwd_mfma_f32(indptr, indices, self_ids, rowmap, static_cast<const float*>(x), ldx, W, ldw, bias, n, n_pad,
-                                 H, out, relu_in, relu_out, cat, ldc, y, ldy, wpack, stream);
-  return csl_sage_fwd_mfma_x16(indptr, indices, self_ids, rowmap, x, kind, ldx, W, ldw, bias, n, n_pad, H, out, relu_in,
-                               relu_out, cat, ldc, y, ldy, wpack, stream);
+// ---- what the single-GPU step and the rank step share.  The resident feature table is float32 (kind 0: the _f32 entry
+// points) or 16-bit (CSL_FEAT_F16 / CSL_FEAT_BF16: the _x16 twins, cslicer_feat16.h); only the deepest layer's forward reads
+// it, through the readers of table_readers.h, and everything downstream of them is fp32 either way.
+
+// the _x16 entry points refuse a table no reader takes before anything else
+bool table16_refused(const void* feat, int32_t kind, int64_t ldf) {
+  if (feat::table_ok(feat, kind, ldf)) return false;
+  snprintf(s_err, sizeof(s_err), "16-bit feature table: kind %d (1 float16, 2 bfloat16), 8-byte aligned base, row stride a "
+           "multiple of 4 elements expected", (int)kind);
+  return true;
 }
-inline int feat_sage_cat(int32_t kind, const int32_t* indptr, const int32_t* indices, const int32_t* self_ids,
-                         const int32_t* owned, const int32_t* deg, const int32_t* rowmap, const void* x, int64_t ldx,
-                         const float* agg, int64_t lda, int64_t n, int64_t n_pad, float* cat, int64_t ldc, int32_t H,
-                         int32_t relu_in, void* stream) {
-  if (kind == 0)
-    return csl_sage_cat_f32(indptr, indices, self_ids, owned, deg, rowmap, static_cast<const float*>(x), ldx, agg, lda, n,
-                            n_pad, cat, ldc, H, relu_in, stream);
-  return csl_sage_cat_x16(indptr, indices, self_ids, owned, deg, rowmap, x, kind, ldx, agg, lda, n, n_pad, cat, ldc, H,
-                          relu_in, stream);
+
+bool workspace_fits(int64_t total, const float* workspace, int64_t workspace_floats) {
+  if (total <= workspace_floats && (total <= 0 || (workspace && aligned16(workspace)))) return true;
+  snprintf(s_err, sizeof(s_err), "workspace: %lld floats needed, %lld given", (long long)total, (long long)workspace_floats);
+  return false;
 }
-inline int feat_spmm_sum_map(int32_t kind, const int32_t* indptr, const int32_t* indices, const int32_t* rows,
-                             int64_t n_rows, const void* x, int64_t ldx, const int32_t* rowmap, float* out, int64_t ldo,
-                             int32_t H, int32_t compact, void* stream) {
-  if (kind == 0)
-    return csl_spmm_sum_map_f32(indptr, indices, rows, n_rows, static_cast<const float*>(x), ldx, rowmap, out, ldo, H,
-                                compact, stream);
-  return csl_spmm_sum_map_x16(indptr, indices, rows, n_rows, x, kind, ldx, rowmap, out, ldo, H, compact, stream);
+
+// where each parameter's gradient sits in the flat buffer: W_0, b_0, W_1, b_1, ...
+struct GradSlots {
+  float *gW[CSL_MAX_LAYERS], *gb[CSL_MAX_LAYERS];
+  GradSlots(float* grads, int L, const int32_t* dims) {
+    int64_t at = 0;
+    for (int j = 0; j < L; j++) {
+      gW[j] = grads + at, at += (int64_t)dims[j + 1] * 2 * dims[j];
+      gb[j] = grads + at, at += dims[j + 1];
+    }
+  }
+};
+
+// the second stages of a step's reductions, collected as (source, blocks, width, destination) and finished by ONE launch
+// (a step defers at most 2 L + 1 of them: see the static_assert above)
+struct Deferred {
+  const float* src[CSL_REDUCE_MULTI_MAX];
+  float* dst[CSL_REDUCE_MULTI_MAX];
+  int64_t nblk[CSL_REDUCE_MULTI_MAX];
+  int32_t h[CSL_REDUCE_MULTI_MAX];
+  int n = 0;
+  void add(const float* s, int64_t blocks, int32_t width, float* d) {
+    if (n >= CSL_REDUCE_MULTI_MAX) return;   // (cannot happen: asserted at compile time)
+    src[n] = s, nblk[n] = blocks, h[n] = width, dst[n] = d;
+    n++;
+  }
+  int finish(void* stream) { return csl_reduce_multi_f32(n, src, nblk, h, dst, stream); }
+};
+
+// gW_k = gy_k^T cat_k of either layout (Layout, RankLayout): nothing but a zero fill without rows, in row slabs whose sum
+// is deferred, or one plain GEMM.  group: the timing group of the GEMM (< 0: untimed)
+template <typename Lay>
+int weight_grad(int group, const Lay& o, int k, const int32_t* dims, int32_t n_slabs, float* ws, float* gW, Deferred& later,
+                void* stream) {
+  const int64_t in = dims[k], out = dims[k + 1], mp = o.mp[k], wn = out * 2 * in;
+  if (mp == 0) return hipMemsetAsync(gW, 0, sizeof(float) * wn, (hipStream_t)stream) == hipSuccess ? CSL_OK : CSL_E_HIP;
+  SpanGuard sg(group, stream);
+  if (!o.slabbed[k])
+    return csl_gemm_f32(1, 0, out, 2 * in, mp, ws + o.gy[k], out, 0, ws + o.cat[k], 2 * in, 0, gW, 2 * in, 0, 1, nullptr, 0, stream);
+  const int64_t rs = mp / n_slabs;
+  later.add(ws + o.slabs[k], n_slabs, (int32_t)wn, gW);
+  return csl_gemm_f32(1, 0, out, 2 * in, rs, ws + o.gy[k], out, rs * out, ws + o.cat[k], 2 * in, rs * 2 * in, ws + o.slabs[k],
+                      2 * in, wn, n_slabs, nullptr, 0, stream);
 }
 
 }  // namespace
@@ -245,21 +276,10 @@ static int sage_fwd_bwd(int32_t n_layers, const int32_t* dims, const csl_sage_sl
              "n_in of a layer = n_out of the layer below)", CSL_MAX_LAYERS);
     return CSL_E_INVALID;
   }
-  if (o.total > workspace_floats || (o.total > 0 && (!workspace || ((uintptr_t)workspace & 15)))) {
-    snprintf(s_err, sizeof(s_err), "workspace: %lld floats needed, %lld given", (long long)o.total, (long long)workspace_floats);
-    return CSL_E_INVALID;
-  }
+  if (!workspace_fits(o.total, workspace, workspace_floats)) return CSL_E_INVALID;
   const int L = n_layers;
   float* ws = workspace;
-  // where each parameter's gradient sits in the flat buffer: W_0, b_0, W_1, b_1, ...
-  float *gW[CSL_MAX_LAYERS], *gb[CSL_MAX_LAYERS];
-  {
-    int64_t at = 0;
-    for (int j = 0; j < L; j++) {
-      gW[j] = grads + at, at += (int64_t)dims[j + 1] * 2 * dims[j];
-      gb[j] = grads + at, at += dims[j + 1];
-    }
-  }
+  const GradSlots gs(grads, L, dims);
   // ---- forward
   for (k = 0; k < L; k++) {
     const int32_t in = dims[k], out = dims[k + 1];
@@ -269,28 +289,17 @@ static int sage_fwd_bwd(int32_t n_layers, const int32_t* dims, const csl_sage_sl
     if (k == 0 && o.wpack >= 0) {
       // gather [self | mean] into LDS, multiply on the fp32 matrix cores, bias + ReLU on the way out; the operand is
       // also written (the weight gradient reads it), but never read back by the forward
-      TSTEP(CSL_STEP_FUSED_FWD, feat_fwd_mfma(kind, sl[0].indptr, sl[0].indices, sl[0].self_ids_in, feat_rows, feat, ldf, weights[0],
-                                 2 * (int64_t)in, biases[0], m, mp, in, out, 0, L > 1 ? 1 : 0, ws + o.cat[0],
-                                 2 * (int64_t)in, ws + o.y[0], out, ws + o.wpack, stream));
+      TSTEP(CSL_STEP_FUSED_FWD, rd::sage_fwd_mfma(sl[0].indptr, sl[0].indices, sl[0].self_ids_in, feat_rows, feat, kind, ldf, weights[0],
+                                                  2 * (int64_t)in, biases[0], m, mp, in, out, 0, L > 1 ? 1 : 0, ws + o.cat[0],
+                                                  2 * (int64_t)in, ws + o.y[0], out, ws + o.wpack, stream));
       continue;
     }
-    TSTEP(CSL_STEP_AGGREGATION, feat_sage_cat(xk, sl[k].indptr, sl[k].indices, sl[k].self_ids_in, nullptr, nullptr, k == 0 ? feat_rows : nullptr, x,
-                          k == 0 ? ldf : (int64_t)in, nullptr, 0, m, mp, ws + o.cat[k], 2 * (int64_t)in, in, 0, stream));
+    TSTEP(CSL_STEP_AGGREGATION, rd::sage_cat(sl[k].indptr, sl[k].indices, sl[k].self_ids_in, nullptr, nullptr, k == 0 ? feat_rows : nullptr, x,
+                                             xk, k == 0 ? ldf : (int64_t)in, nullptr, 0, m, mp, ws + o.cat[k], 2 * (int64_t)in, in, 0, stream));
     TSTEP(CSL_STEP_GEMM, csl_gemm_f32(0, 1, mp, out, 2 * (int64_t)in, ws + o.cat[k], 2 * (int64_t)in, 0, weights[k], 2 * (int64_t)in, 0,
                       ws + o.y[k], out, 0, 1, biases[k], k + 1 < L ? 1 : 0, stream));
   }
-  // the second stages, collected: (source, blocks, width, destination)
-  // (a step defers at most 2 L + 1 second stages: see the static_assert next to CSL_MAX_LAYERS below)
-  const float* r_src[CSL_REDUCE_MULTI_MAX];
-  float* r_dst[CSL_REDUCE_MULTI_MAX];
-  int64_t r_nblk[CSL_REDUCE_MULTI_MAX];
-  int32_t r_h[CSL_REDUCE_MULTI_MAX];
-  int nr = 0;
-  auto defer = [&](const float* src, int64_t nblk, int32_t h, float* dst) {
-    if (nr >= CSL_REDUCE_MULTI_MAX) return;   // (cannot happen: asserted at compile time)
-    r_src[nr] = src, r_nblk[nr] = nblk, r_h[nr] = h, r_dst[nr] = dst;
-    nr++;
-  };
+  Deferred later;
   // ---- loss and its gradient w.r.t. the logits (written as the top layer's padded gy), bias column sums alongside
   k = L - 1;
   {
@@ -299,29 +308,19 @@ static int sage_fwd_bwd(int32_t n_layers, const int32_t* dims, const csl_sage_sl
     if (o.top_cols) {
       TSTEP(CSL_STEP_OTHER, csl_softmax_ce_partial_f32(ws + o.y[k], C, m, o.mp[k], C, seed_ids, nullptr, labels, scale, ws + o.gy[k], C,
                                       ws + o.lpart, ws + o.bpart[k], stream));
-      defer(ws + o.bpart[k], o.bblocks[k], C, gb[k]);
+      later.add(ws + o.bpart[k], o.bblocks[k], C, gs.gb[k]);
     } else {
       TSTEP(CSL_STEP_OTHER, csl_softmax_ce_partial_f32(ws + o.y[k], C, m, m, C, seed_ids, nullptr, labels, scale, ws + o.g, C, ws + o.lpart,
                                       nullptr, stream));
-      TSTEP(CSL_STEP_AGGREGATION, csl_relu_bwd_colsum_f32(ws + o.g, C, nullptr, 0, m, o.mp[k], ws + o.gy[k], C, gb[k], ws + o.scratch, C, stream));
+      TSTEP(CSL_STEP_AGGREGATION, csl_relu_bwd_colsum_f32(ws + o.g, C, nullptr, 0, m, o.mp[k], ws + o.gy[k], C, gs.gb[k], ws + o.scratch, C, stream));
     }
-    defer(ws + o.lpart, o.top_cols ? o.lblocks : (m + 3) / 4, 1, loss);  // (blocks of four rows the loss pass covered)
+    later.add(ws + o.lpart, o.top_cols ? o.lblocks : (m + 3) / 4, 1, loss);  // (blocks of four rows the loss pass covered)
   }
   // ---- backward
   for (k = L - 1; k >= 0; k--) {
     const int32_t in = dims[k], out = dims[k + 1];
-    const int64_t mp = o.mp[k], wn = (int64_t)out * 2 * in;
-    if (mp == 0) {
-      if (hipMemsetAsync(gW[k], 0, sizeof(float) * wn, (hipStream_t)stream) != hipSuccess) return CSL_E_HIP;
-    } else if (o.slabbed[k]) {
-      const int64_t rs = mp / n_slabs;
-      TSTEP(CSL_STEP_GEMM, csl_gemm_f32(1, 0, out, 2 * (int64_t)in, rs, ws + o.gy[k], out, rs * out, ws + o.cat[k], 2 * (int64_t)in,
-                        rs * 2 * in, ws + o.slabs[k], 2 * (int64_t)in, wn, n_slabs, nullptr, 0, stream));
-      defer(ws + o.slabs[k], n_slabs, (int32_t)wn, gW[k]);
-    } else {
-      TSTEP(CSL_STEP_GEMM, csl_gemm_f32(1, 0, out, 2 * (int64_t)in, mp, ws + o.gy[k], out, 0, ws + o.cat[k], 2 * (int64_t)in, 0, gW[k],
-                        2 * (int64_t)in, 0, 1, nullptr, 0, stream));
-    }
+    const int64_t mp = o.mp[k];
+    STEP(weight_grad(CSL_STEP_GEMM, o, k, dims, n_slabs, ws, gs.gW[k], later, stream));
     if (k == 0) break;
     if (!sl[k].t_indptr || !sl[k].t_indices) {
       snprintf(s_err, sizeof(s_err), "layer %d has no slice by source (engine flag CSL_FLAG_TRANSPOSE)", k);
@@ -342,12 +341,12 @@ static int sage_fwd_bwd(int32_t n_layers, const int32_t* dims, const csl_sage_sl
     TSTEP(CSL_STEP_AGGREGATION, csl_sage_cat_bwd_t_f32(sl[k].t_indptr, sl[k].t_indices, sl[k].indptr, ws + o.gcat[k], 2 * (int64_t)in,
                                 ws + o.y[k - 1], in, sl[k].n_in, o.mp[k - 1], ws + o.gy[k - 1], in, nullptr,
                                 ws + o.bpart[k - 1], in, stream));
-    if (o.bblocks[k - 1] > 0) defer(ws + o.bpart[k - 1], o.bblocks[k - 1], in, gb[k - 1]);
-    else if (hipMemsetAsync(gb[k - 1], 0, sizeof(float) * in, (hipStream_t)stream) != hipSuccess) return CSL_E_HIP;
+    if (o.bblocks[k - 1] > 0) later.add(ws + o.bpart[k - 1], o.bblocks[k - 1], in, gs.gb[k - 1]);
+    else if (hipMemsetAsync(gs.gb[k - 1], 0, sizeof(float) * in, (hipStream_t)stream) != hipSuccess) return CSL_E_HIP;
   }
   // ---- every deferred second stage (bias sums, weight-gradient slabs, the loss) in one launch
   k = -1;
-  TSTEP(CSL_STEP_OTHER, csl_reduce_multi_f32(nr, r_src, r_nblk, r_h, r_dst, stream));
+  TSTEP(CSL_STEP_OTHER, later.finish(stream));
   return CSL_OK;
 }
 
@@ -363,11 +362,7 @@ int csl_sage_fwd_bwd_x16(int32_t n_layers, const int32_t* dims, const csl_sage_s
                          const float* const* biases, const void* feat, int32_t kind, int64_t ldf, const int32_t* feat_rows,
                          const int32_t* seed_ids, const int64_t* labels, float scale, int64_t row_pad, int32_t n_slabs,
                          float* grads, float* loss, float* workspace, int64_t workspace_floats, void* stream) {
-  if (!feat::table_ok(feat, kind, ldf)) {
-    snprintf(s_err, sizeof(s_err), "16-bit feature table: kind %d (1 float16, 2 bfloat16), 8-byte aligned base, row stride a "
-             "multiple of 4 elements expected", (int)kind);
-    return CSL_E_INVALID;
-  }
+  if (table16_refused(feat, kind, ldf)) return CSL_E_INVALID;
   return sage_fwd_bwd(n_layers, dims, sl, weights, biases, feat, kind, ldf, feat_rows, seed_ids, labels, scale, row_pad,
                       n_slabs, grads, loss, workspace, workspace_floats, stream);
 }
@@ -471,20 +466,10 @@ static int sage_rank_fwd_bwd(int32_t n_layers, const int32_t* dims, const csl_sa
              "n_in of a layer = n_owned of the layer below)", CSL_MAX_LAYERS);
     return CSL_E_INVALID;
   }
-  if (o.total > workspace_floats || (o.total > 0 && (!workspace || ((uintptr_t)workspace & 15)))) {
-    snprintf(s_err, sizeof(s_err), "workspace: %lld floats needed, %lld given", (long long)o.total, (long long)workspace_floats);
-    return CSL_E_INVALID;
-  }
+  if (!workspace_fits(o.total, workspace, workspace_floats)) return CSL_E_INVALID;
   const int L = n_layers;
   float* ws = workspace;
-  float *gW[CSL_MAX_LAYERS], *gb[CSL_MAX_LAYERS];
-  {
-    int64_t at = 0;
-    for (int j = 0; j < L; j++) {
-      gW[j] = grads + at, at += (int64_t)dims[j + 1] * 2 * dims[j];
-      gb[j] = grads + at, at += dims[j + 1];
-    }
-  }
+  const GradSlots gs(grads, L, dims);
 #define XCHG(layer, backward, src, dst, width)                                                     \
   do {                                                                                             \
     const int rc_ = exchange(user, (layer), (backward), (src), (dst), (width), stream);            \
@@ -523,58 +508,38 @@ static int sage_rank_fwd_bwd(int32_t n_layers, const int32_t* dims, const csl_sa
       // too, with the empty buffers (whether a collective is entered depends only on L, which all ranks share)
       XCHG(0, 0, ws + o.send[0], ws + o.recv[0], in);
       XWAIT(0, 0);
-      STEP(feat_fwd_mfma(kind, s.indptr, s.indices, s.self_ids_in, feat_rows, feat, ldf, weights[0], 2 * (int64_t)in,
-                                 biases[0], s.n_owned, o.mp[0], in, out, 0, L > 1 ? 1 : 0, ws + o.cat[0], 2 * (int64_t)in,
-                                 ws + o.y[0], out, ws + o.wpack, stream));
+      STEP(rd::sage_fwd_mfma(s.indptr, s.indices, s.self_ids_in, feat_rows, feat, kind, ldf, weights[0], 2 * (int64_t)in,
+                             biases[0], s.n_owned, o.mp[0], in, out, 0, L > 1 ? 1 : 0, ws + o.cat[0], 2 * (int64_t)in,
+                             ws + o.y[0], out, ws + o.wpack, stream));
       continue;
     }
     // partial sums of the rows peers own, straight into the send buffer; then the rows this part owns
-    STEP(feat_spmm_sum_map(xk, s.indptr, s.indices, s.from_all, s.n_from, x, ldx, map, ws + o.send[k], in, in, 1, stream));
+    STEP(rd::spmm_sum_map(s.indptr, s.indices, s.from_all, s.n_from, x, xk, ldx, map, ws + o.send[k], in, in, 1, stream));
     XCHG(k, 0, ws + o.send[k], ws + o.recv[k], in);
-    STEP(feat_spmm_sum_map(xk, s.indptr, s.indices, s.owned_out_nodes, s.n_owned, x, ldx, map, ws + o.agg[k], in, in, 0, stream));
+    STEP(rd::spmm_sum_map(s.indptr, s.indices, s.owned_out_nodes, s.n_owned, x, xk, ldx, map, ws + o.agg[k], in, in, 0, stream));
     XWAIT(k, 0);
     STEP(csl_scatter_add_rows_atomic_f32(ws + o.agg[k], in, s.to_all, s.n_to, ws + o.recv[k], in, in, stream));
-    STEP(feat_sage_cat(xk, nullptr, nullptr, s.self_ids_in, s.owned_out_nodes, s.owned_degree, map, x, ldx, ws + o.agg[k],
-                          in, s.n_owned, o.mp[k], ws + o.cat[k], 2 * (int64_t)in, in, 0, stream));
+    STEP(rd::sage_cat(nullptr, nullptr, s.self_ids_in, s.owned_out_nodes, s.owned_degree, map, x, xk, ldx, ws + o.agg[k], in,
+                      s.n_owned, o.mp[k], ws + o.cat[k], 2 * (int64_t)in, in, 0, stream));
     STEP(csl_gemm_f32(0, 1, o.mp[k], out, 2 * (int64_t)in, ws + o.cat[k], 2 * (int64_t)in, 0, weights[k], 2 * (int64_t)in, 0,
                       ws + o.y[k], out, 0, 1, biases[k], k + 1 < L ? 1 : 0, stream));
   }
-  // (a step defers at most 2 L + 1 second stages: see the static_assert next to CSL_MAX_LAYERS below)
-  const float* r_src[CSL_REDUCE_MULTI_MAX];
-  float* r_dst[CSL_REDUCE_MULTI_MAX];
-  int64_t r_nblk[CSL_REDUCE_MULTI_MAX];
-  int32_t r_h[CSL_REDUCE_MULTI_MAX];
-  int nr = 0;
-  auto defer = [&](const float* src, int64_t nblk, int32_t h, float* dst) {
-    if (nr >= CSL_REDUCE_MULTI_MAX) return;   // (cannot happen: asserted at compile time)
-    r_src[nr] = src, r_nblk[nr] = nblk, r_h[nr] = h, r_dst[nr] = dst;
-    nr++;
-  };
+  Deferred later;
   // ---- loss over the seeds this part owns (the caller's `scale` = 1 / seeds of the WHOLE minibatch)
   k = L - 1;
   {
     const int32_t C = dims[L];
     STEP(csl_softmax_ce_partial_f32(ws + o.y[k], C, sl[k].n_owned, o.mp[k], C, seed_ids, label_rows, labels, scale,
                                     ws + o.gy[k], C, ws + o.lpart, ws + o.bpart[k], stream));
-    defer(ws + o.bpart[k], o.bblocks[k], C, gb[k]);
-    defer(ws + o.lpart, o.lblocks, 1, loss);
+    later.add(ws + o.bpart[k], o.bblocks[k], C, gs.gb[k]);
+    later.add(ws + o.lpart, o.lblocks, 1, loss);
   }
   // ---- backward
   for (k = L - 1; k >= 0; k--) {
     const int32_t in = dims[k], out = dims[k + 1];
     const csl_sage_rank_slice& s = sl[k];
-    const int64_t mp = o.mp[k], wn = (int64_t)out * 2 * in;
-    if (mp == 0) {
-      if (hipMemsetAsync(gW[k], 0, sizeof(float) * wn, (hipStream_t)stream) != hipSuccess) return CSL_E_HIP;
-    } else if (o.slabbed[k]) {
-      const int64_t rs = mp / n_slabs;
-      STEP(csl_gemm_f32(1, 0, out, 2 * (int64_t)in, rs, ws + o.gy[k], out, rs * out, ws + o.cat[k], 2 * (int64_t)in,
-                        rs * 2 * in, ws + o.slabs[k], 2 * (int64_t)in, wn, n_slabs, nullptr, 0, stream));
-      defer(ws + o.slabs[k], n_slabs, (int32_t)wn, gW[k]);
-    } else {
-      STEP(csl_gemm_f32(1, 0, out, 2 * (int64_t)in, mp, ws + o.gy[k], out, 0, ws + o.cat[k], 2 * (int64_t)in, 0, gW[k],
-                        2 * (int64_t)in, 0, 1, nullptr, 0, stream));
-    }
+    const int64_t mp = o.mp[k];
+    STEP(weight_grad(-1, o, k, dims, n_slabs, ws, gs.gW[k], later, stream));
     if (k == 0) break;   // (no gradient flows into the input features; the deepest layer's exchange has no backward)
     STEP(csl_gemm_f32(0, 0, mp, 2 * (int64_t)in, out, ws + o.gy[k], out, 0, weights[k], 2 * (int64_t)in, 0, ws + o.gcat[k],
                       2 * (int64_t)in, 0, 1, nullptr, 0, stream));
@@ -598,7 +563,7 @@ static int sage_rank_fwd_bwd(int32_t n_layers, const int32_t* dims, const csl_sa
           STEP(csl_sage_cat_bwd_t_f32(s.t_indptr, s.t_indices, nullptr, g2, 2 * (int64_t)in, ws + o.y[k - 1], in, s.n_in,
                                       o.mp[k - 1], ws + o.gy[k - 1], in, nullptr, ws + o.bpart[k - 1], in, stream));
       }
-      defer(ws + o.bpart[k - 1], o.mp[k - 1] > 0 ? o.bblocks[k - 1] : 0, in, gb[k - 1]);
+      later.add(ws + o.bpart[k - 1], o.mp[k - 1] > 0 ? o.bblocks[k - 1] : 0, in, gs.gb[k - 1]);
       continue;
     }
     // operand gradient -> self rows of gx and owned rows of the merged sums' gradient (both zeroed inside)
@@ -617,10 +582,10 @@ static int sage_rank_fwd_bwd(int32_t n_layers, const int32_t* dims, const csl_sa
     if (o.mp[k - 1] > 0)
       STEP(csl_relu_bwd_colsum_f32(ws + o.gx[k], in, ws + o.y[k - 1], in, s.n_in, o.mp[k - 1], ws + o.gy[k - 1], in,
                                    nullptr, ws + o.bpart[k - 1], in, stream));
-    defer(ws + o.bpart[k - 1], o.mp[k - 1] > 0 ? o.bblocks[k - 1] : 0, in, gb[k - 1]);
+    later.add(ws + o.bpart[k - 1], o.mp[k - 1] > 0 ? o.bblocks[k - 1] : 0, in, gs.gb[k - 1]);
   }
   k = -1;
-  STEP(csl_reduce_multi_f32(nr, r_src, r_nblk, r_h, r_dst, stream));
+  STEP(later.finish(stream));
 #undef XCHG
 #undef XWAIT
   return CSL_OK;
@@ -642,11 +607,7 @@ int csl_sage_rank_fwd_bwd_x16(int32_t n_layers, const int32_t* dims, const csl_s
                               const int64_t* labels, float scale, int64_t row_pad, int32_t n_slabs,
                               csl_exchange_fn exchange, csl_exchange_wait_fn wait, void* user, float* grads, float* loss,
                               float* workspace, int64_t workspace_floats, void* stream) {
-  if (!feat::table_ok(feat, kind, ldf)) {
-    snprintf(s_err, sizeof(s_err), "16-bit feature table: kind %d (1 float16, 2 bfloat16), 8-byte aligned base, row stride a "
-             "multiple of 4 elements expected", (int)kind);
-    return CSL_E_INVALID;
-  }
+  if (table16_refused(feat, kind, ldf)) return CSL_E_INVALID;
   return sage_rank_fwd_bwd(n_layers, dims, sl, weights, biases, feat, kind, ldf, feat_rows, seed_ids, label_rows, labels,
                            scale, row_pad, n_slabs, exchange, wait, user, grads, loss, workspace, workspace_floats, stream);
 }

@@ -148,6 +148,65 @@ def test_feat16_host_side_argument_checks():
         assert mfma(tab, kind, 100, n=0) == 0 and cat(tab, kind, 100, n=0) == 0
         assert spmm(tab, kind, 100, n=0) == 0 and gather(tab, kind, 100, n=0) == 0
 
+    # ---- parity: each _f32 entry point and its _x16 twin (both kinds) get the same arguments and give the same stated
+    # code.  Every case is refused or has nothing to do, so no HIP call is reached.  Defaults: the aligned dummy table,
+    # H = 100, out = 256, n = n_pad = 10, the natural leading dimensions, null index lists.
+    def mfma2(kind, indptr=null, self_ids=null, x=tab, ldx=None, W=tab, ldw=None, n=10, n_pad=10, H=100, out=256,
+              cat=null, ldc=None, y=tab, ldy=None, wpack=tab):
+        ldx, ldw = H if ldx is None else ldx, 2 * H if ldw is None else ldw
+        ldc, ldy = 2 * H if ldc is None else ldc, out if ldy is None else ldy
+        table = (x, ldx) if kind is None else (x, kind, ldx)
+        fn = L.csl_sage_fwd_mfma_f32 if kind is None else L.csl_sage_fwd_mfma_x16
+        return fn(indptr, indptr, self_ids, null, *table, W, ldw, null, n, n_pad, H, out, 0, 1, cat, ldc, y, ldy, wpack, st)
+
+    def cat2(kind, indptr=null, self_ids=null, owned=null, deg=null, x=tab, ldx=None, agg=null, lda=None, n=10, n_pad=10,
+             cat=tab, ldc=None, H=100):
+        ldx, lda, ldc = H if ldx is None else ldx, H if lda is None else lda, 2 * H if ldc is None else ldc
+        table = (x, ldx) if kind is None else (x, kind, ldx)
+        fn = L.csl_sage_cat_f32 if kind is None else L.csl_sage_cat_x16
+        return fn(indptr, indptr, self_ids, owned, deg, null, *table, agg, lda, n, n_pad, cat, ldc, H, 0, st)
+
+    def spmm2(kind, indptr=null, rows=null, n=10, x=tab, ldx=None, out=tab, ldo=None, H=100, compact=0):
+        ldx, ldo = H if ldx is None else ldx, H if ldo is None else ldo
+        table = (x, ldx) if kind is None else (x, kind, ldx)
+        fn = L.csl_spmm_sum_map_f32 if kind is None else L.csl_spmm_sum_map_x16
+        return fn(indptr, indptr, rows, n, *table, null, out, ldo, H, compact, st)
+
+    def gather2(kind, x=tab, lds=None, idx=null, n=10, dst=tab, ldd=None, H=100):
+        lds, ldd = H if lds is None else lds, H if ldd is None else ldd
+        table = (x, lds) if kind is None else (x, kind, lds)
+        fn = L.csl_gather_rows_f32 if kind is None else L.csl_gather_rows_x16
+        return fn(*table, idx, n, dst, ldd, H, st)
+
+    merged = dict(self_ids=tab, owned=tab, deg=tab, agg=tab)      # sage_cat's merged-sums form: no indptr
+    without = lambda d, *keys: {k: v for k, v in d.items() if k not in keys}
+    matrix = {
+        mfma2: ([dict(n=0, n_pad=0)],
+                [dict(), dict(indptr=tab), dict(self_ids=tab), dict(H=102), dict(out=257), dict(out=0), dict(ldx=96),
+                 dict(H=300), dict(W=null), dict(W=odd), dict(ldw=196), dict(ldw=202), dict(n_pad=8), dict(n=-1),
+                 dict(y=null), dict(ldy=252), dict(wpack=null), dict(wpack=odd), dict(cat=tab, ldc=196), dict(cat=odd),
+                 dict(indptr=tab, self_ids=tab, cat=tab, ldc=202)]),
+        cat2: ([dict(n=0, n_pad=0)],
+               [dict(), dict(H=6), dict(H=2), dict(ldx=96), dict(n_pad=8), dict(n=-1), dict(cat=null), dict(cat=odd),
+                dict(ldc=196), dict(ldc=202), without(merged, "owned"), without(merged, "deg"), without(merged, "agg"),
+                without(merged, "owned", "deg", "agg"), dict(merged, lda=96), dict(merged, lda=102), dict(merged, agg=odd),
+                dict(indptr=tab)]),
+        spmm2: ([dict(n=0)],
+                [dict(), dict(n=-1), dict(ldx=96), dict(out=null), dict(ldo=96), dict(indptr=tab, compact=1), dict(H=0)]),
+        gather2: ([dict(n=0)], [dict(), dict(n=-1), dict(lds=96), dict(dst=null), dict(ldd=96), dict(H=0)]),
+    }
+    assert [len(ok) + len(bad) for ok, bad in matrix.values()] == [22, 19, 8, 7]
+    for fn, (ok, bad) in matrix.items():
+        for want, cases in ((0, ok), (-1, bad)):
+            for kw in cases:
+                got = [fn(kind, **kw) for kind in (None, F16, BF16)]
+                assert got == [want] * 3, (fn.__name__, kw, got)
+    # the one difference that is meant: with nothing to do, a 16-bit table is still checked (here rows narrower than H), a
+    # float32 table is not looked at
+    for fn, kw in ((mfma2, dict(n=0, n_pad=0, ldx=96)), (cat2, dict(n=0, n_pad=0, ldx=96)), (spmm2, dict(n=0, ldx=96)),
+                   (gather2, dict(n=0, lds=96))):
+        assert [fn(kind, **kw) for kind in (None, F16, BF16)] == [0, -1, -1], fn.__name__
+
 
 def test_trainer_refuses_an_unknown_feature_dtype():
     """raised before anything touches a device"""

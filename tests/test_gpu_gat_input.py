@@ -27,7 +27,13 @@ def _scale(t):
 @pytest.mark.parametrize("heads,D,F0,fan,B,elu", [(8, 32, 100, 10, 256, True), (4, 12, 20, 7, 64, False),
                                                   (1, 8, 128, 32, 50, True), (2, 16, 4, 3, 300, True),
                                                   (8, 4, 36, 17, 128, False), (4, 64, 128, 12, 100, True),
-                                                  (2, 32, 64, 20, 77, False), (1, 16, 112, 5, 33, True)])
+                                                  (2, 32, 64, 20, 77, False), (1, 16, 112, 5, 33, True),
+                                                  # the smallest shapes that reach the instances nothing above launches:
+                                                  (4, 64, 36, 20, 64, True),     # heads 4 with 32 edges; projection tile
+                                                                                 # <4, 4>; k_bd_dw<1, 4>
+                                                  (2, 64, 100, 5, 64, False),    # projection tile <7, 4>
+                                                  (1, 16, 128, 9, 64, True),     # projection tile <8, 1>
+                                                  (8, 32, 128, 10, 64, False)])  # projection tile <8, 2>
 def test_input_layer_matches_the_projecting_layer(mods, heads, D, F0, fan, B, elu, libgemm, monkeypatch):
     """one layer, same slice, same parameters: output, weight / attention / bias gradients.  The block-diagonal projection
     runs on the MFMA kernels where they cover the shape (D in {16, 32, 64}) and as batched library GEMMs otherwise
