@@ -1,7 +1,8 @@
 /* cslicer_feat16.h -- C ABI of the readers of a 16-bit feature table (float16 or bfloat16 rows resident in HBM).
  * Part of libcslicer_hip.so; kernels in csrc/sage_mfma.hip, csrc/aggregate.hip, sequencers in csrc/sage_step.hip.
  *
- * The input layer takes no gradient, so only the FORWARD readers of the table have a 16-bit form: each entry point here
+ * The input layer takes no gradient, so of the GraphSAGE readers only the FORWARD ones have a 16-bit form (the attention
+ * input layer reads the table in its backward too: its twins are in cslicer_gat_in16.h): each entry point here
  * is the twin of an fp32 entry point of cslicer_aggr.h whose table argument `x` / `feat` / `src` holds 16-bit elements
  * of kind `kind` instead of floats.  A row is upcast in registers (both conversions to float32 are exact) and everything
  * after the load -- the order of the sums, the operand kept for the weight gradient, the GEMMs, the backward -- is the

@@ -16,6 +16,7 @@ from . import _abi, l0
 # prototypes are bound from the headers' text when the library is loaded (_abi.bind_header)
 _abi.load()
 SYMBOLS, FEAT16_SYMBOLS = _abi.BOUND["cslicer_aggr.h"], _abi.BOUND["cslicer_feat16.h"]
+GAT_IN16_SYMBOLS = _abi.BOUND["cslicer_gat_in16.h"]   # the attention input layer over a 16-bit table (forward AND backward)
 EXCHANGE_FN, EXCHANGE_WAIT_FN = _abi.EXCHANGE_FN, _abi.EXCHANGE_WAIT_FN
 # element kinds of a 16-bit feature table (CSL_FEAT_F16 / CSL_FEAT_BF16); a float32 table has the fp32 entry points
 FEAT_KINDS = {torch.float16: 1, torch.bfloat16: 2}
@@ -867,11 +868,16 @@ class FeatureRows(object):
 GAT_IN_MAX_WIDTH = 256   # H * D: the rows csl_elu_bwd_colsum_f32 (the layer's backward epilogue) covers
 
 
+def gat_in_max_degree():
+    """the longest row (edges) the input layer's edge kernels take"""
+    return int(_lib().csl_gat_in_max_degree())
+
+
 def gat_input_ok(H, F, fanout, D=None):
     """whether GatInputLayer covers a layer of H heads x D outputs on F input features whose rows have <= fanout edges
     (D = None: the edge kernels' limits alone; a caller that is about to build the layer passes its D)"""
     return (H in (1, 2, 4, 8) and F % 4 == 0 and 4 <= F <= 128 and (D is None or 0 < H * D <= GAT_IN_MAX_WIDTH)
-            and 0 < fanout <= int(_lib().csl_gat_in_max_degree()))
+            and 0 < fanout <= gat_in_max_degree())
 
 
 def _gemm_batched(transa, transb, m, n, k, a, lda, sa, b, ldb, sb, c, ldc, sc, batch):
@@ -890,6 +896,9 @@ class GatInputLayer(torch.autograd.Function):
     equals GatLayerLocal on the gathered rows up to fp32 rounding, with a tenth of its flops and without the projected
     source matrix, the gathered input matrix or the layer's slice by source.  Backward: dW_h = g_h^T agg_h, dagg_h = g_h W_h,
     one pass over the edges for the gradients of v_l / v_r (csl_gat_in_bwd_f32), then the chain rule through v = W^T a.
+    The table is float32, float16 or bfloat16 and is read IN PLACE by both edge passes (a 16-bit one through the _x16 twins
+    of include/cslicer_gat_in16.h, upcast in registers): it is saved for the backward as it is, no float32 copy of it is
+    made, and the layer on a 16-bit table is bitwise the layer on table.float().
     Where the fp32-MFMA projection kernels cover the shape (csl_gat_in_proj_ok: D in {16, 32, 64}) each direction is ONE
     native call (csl_gat_in_layer_fwd_f32 / _bwd_f32); otherwise the products are strided-batched csl_gemm_f32 calls and
     the small pieces torch ops."""
@@ -903,7 +912,7 @@ class GatInputLayer(torch.autograd.Function):
         F, Cw = table.shape[1], H * D
         if Cw > GAT_IN_MAX_WIDTH:
             raise ValueError("GatInputLayer: H * D = %d > %d has no backward kernel (gat_input_ok)" % (Cw, GAT_IN_MAX_WIDTH))
-        table, weight = _f32(table), _f32(weight).contiguous()
+        kind, weight = _table(table), _f32(weight).contiguous()
         al, ar, b = _f32(attn_l).contiguous(), _f32(attn_r).contiguous(), _f32(bias).contiguous()
         indptr, indices, self_ids_in = _i32(indptr), _i32(indices), _i32(self_ids_in)
         rows = _i32(rows) if rows is not None else None
@@ -918,17 +927,15 @@ class GatInputLayer(torch.autograd.Function):
         if mfma:
             # the whole forward as one native call: v_l / v_r, the edge pass, the projection on the fp32 matrix cores
             buf = torch.empty((max(int(L.csl_gat_in_layer_fwd_scratch(H, F)), 4),), dtype=torch.float32, device=dev)
-            _chk(L.csl_gat_in_layer_fwd_f32(_p(indptr), _p(indices), _p(self_ids_in), _p(rows), _p(table), table.stride(0), F,
-                                            _p(weight), _p(al), _p(ar), _p(b), H, D, slope, 1 if elu else 0, n_out, n_edges,
-                                            max_deg, _p(agg), _p(alpha), _p(out), Cw, _p(buf), _stream()),
-                 "csl_gat_in_layer_fwd_f32")
+            _table_call(_twins("gat_in_layer_fwd"), kind, (_p(indptr), _p(indices), _p(self_ids_in), _p(rows), _p(table)),
+                        (table.stride(0), F, _p(weight), _p(al), _p(ar), _p(b), H, D, slope, 1 if elu else 0, n_out, n_edges,
+                         max_deg, _p(agg), _p(alpha), _p(out), Cw, _p(buf), _stream()))
         else:
             Wv = weight.view(H, D, F)
             vl = torch.einsum("hdf,hd->hf", Wv, al).contiguous()
             vr = torch.einsum("hdf,hd->hf", Wv, ar).contiguous()
-            _chk(L.csl_gat_in_fwd_f32(_p(indptr), _p(indices), _p(self_ids_in), _p(rows), _p(table), table.stride(0), F,
-                                      _p(vl), _p(vr), H, slope, n_out, n_edges, max_deg, _p(agg), _p(alpha), _stream()),
-                 "csl_gat_in_fwd_f32")
+            _table_call(_twins("gat_in_fwd"), kind, (_p(indptr), _p(indices), _p(self_ids_in), _p(rows), _p(table)),
+                        (table.stride(0), F, _p(vl), _p(vr), H, slope, n_out, n_edges, max_deg, _p(agg), _p(alpha), _stream()))
             if n_out:
                 _gemm_batched(0, 1, n_out, D, F, agg, H * F, F, weight, F, D * F, out, Cw, D, H)
                 _chk(L.csl_bias_elu_f32(_p(out), Cw, _p(b), n_out, Cw, 1 if elu else 0, _stream()), "csl_bias_elu_f32")
@@ -940,7 +947,7 @@ class GatInputLayer(torch.autograd.Function):
     def backward(ctx, g):
         table, rows, weight, al, ar, agg, alpha, out, indptr, indices, self_ids_in = ctx.saved_tensors
         n_out, n_edges, max_deg, H, D, F, slope, elu, mfma = ctx.cfg
-        Cw, dev = H * D, table.device
+        Cw, dev, kind = H * D, table.device, _table(table)
         L = _lib()
         g = _f32(g)
         if g.stride(-1) != 1 or g.stride(0) % 4:
@@ -954,12 +961,10 @@ class GatInputLayer(torch.autograd.Function):
             # the whole backward as one native call (five kernels, one second-stage launch, the chain rule through v = W^T a)
             g_a = torch.empty((2, H, D), dtype=torch.float32, device=dev)
             buf = torch.empty((max(int(L.csl_gat_in_layer_bwd_scratch(n_out, H, F, D)), 4),), dtype=torch.float32, device=dev)
-            _chk(L.csl_gat_in_layer_bwd_f32(_p(indptr), _p(indices), _p(self_ids_in), _p(rows), _p(table), table.stride(0), F,
-                                            _p(weight), _p(al), _p(ar), H, D, slope, 1 if elu else 0, n_out, n_edges, max_deg,
-                                            _p(agg), _p(alpha), _p(out), Cw, _p(g), g.stride(0), _p(gg), _p(dagg),
-                                            C.c_void_p(gW.data_ptr()), C.c_void_p(g_a[0].data_ptr()),
-                                            C.c_void_p(g_a[1].data_ptr()), _p(g_bias), _p(buf), _stream()),
-                 "csl_gat_in_layer_bwd_f32")
+            _table_call(_twins("gat_in_layer_bwd"), kind, (_p(indptr), _p(indices), _p(self_ids_in), _p(rows), _p(table)),
+                        (table.stride(0), F, _p(weight), _p(al), _p(ar), H, D, slope, 1 if elu else 0, n_out, n_edges, max_deg,
+                         _p(agg), _p(alpha), _p(out), Cw, _p(g), g.stride(0), _p(gg), _p(dagg), C.c_void_p(gW.data_ptr()),
+                         C.c_void_p(g_a[0].data_ptr()), C.c_void_p(g_a[1].data_ptr()), _p(g_bias), _p(buf), _stream()))
             return (None, None, gW.view(Cw, F), g_a[0], g_a[1], g_bias) + (None,) * 10
         buf = torch.empty((max(int(L.csl_elu_bwd_colsum_scratch(n_out, Cw)), int(L.csl_gat_in_bwd_scratch(n_out, H, F)), 4),),
                           dtype=torch.float32, device=dev)
@@ -972,9 +977,9 @@ class GatInputLayer(torch.autograd.Function):
             _gemm_batched(0, 0, n_out, F, D, gg, Cw, D, weight, F, D * F, dagg, H * F, F, H)
         else:
             gW.zero_()
-        _chk(L.csl_gat_in_bwd_f32(_p(indptr), _p(indices), _p(self_ids_in), _p(rows), _p(table), table.stride(0), F, _p(alpha),
-                                  _p(dagg), H * FP, FP, H, slope, n_out, n_edges, max_deg, C.c_void_p(g_v[0].data_ptr()),
-                                  C.c_void_p(g_v[1].data_ptr()), _p(buf), _stream()), "csl_gat_in_bwd_f32")
+        _table_call(_twins("gat_in_bwd"), kind, (_p(indptr), _p(indices), _p(self_ids_in), _p(rows), _p(table)),
+                    (table.stride(0), F, _p(alpha), _p(dagg), H * FP, FP, H, slope, n_out, n_edges, max_deg,
+                     C.c_void_p(g_v[0].data_ptr()), C.c_void_p(g_v[1].data_ptr()), _p(buf), _stream()))
         # chain rule through v_l[h] = W_h^T a_l[h] (and v_r)
         Wv = weight.view(H, D, F)
         gW = gW + al.unsqueeze(2) * g_v[0].unsqueeze(1) + ar.unsqueeze(2) * g_v[1].unsqueeze(1)

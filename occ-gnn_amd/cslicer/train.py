@@ -31,7 +31,7 @@ class Trainer(object):
     def __init__(self, indptr, indices, features, labels, n_classes, rank=0, world=1, fanouts=(15, 10, 5),
                  batch=1024, streams=8, hidden=256, lr=1e-3, device=0, dist=None, seed=0, overlap=False,
                  model="sage", heads=8, rank_path=None, workload=None, feat_dim=None, rng_seed=5489,
-                 feature_dtype="float32"):
+                 feature_dtype="float32", gat_input=None):
         """Part `rank` of `world`.  Ownership = the engine's workload table (`workload` int32 [N], the METIS map of
         python/utils/sampler.py:64-134 / partition_map_opt.bin; None = v % world like pyfrontend.cpp:57): the rank
         keeps the feature and label rows of the nodes it owns, in ascending node order.
@@ -46,10 +46,46 @@ class Trainer(object):
         is ever made on the device, and the deepest layer's forward -- and the first layer of evaluate() / predict() --
         reads it in place and upcasts in registers (exact), so the model is bitwise the one trained on the stored table
         upcast to float32.  A 16-bit table whose width
-        is no multiple of 4 is stored with zero-padded rows; `self.feat` is then the [n_own, F] view of it."""
+        is no multiple of 4 is stored with zero-padded rows; `self.feat` is then the [n_own, F] view of it.
+
+        gat_input: whether the attention model's deepest layer runs aggregate-then-project on the raw feature rows
+        (aggr.GatInputLayer, which reads a table of any of the three types in place).  None (default): on for a float32
+        table where the layer covers the shape (aggr.gat_input_ok), off for a 16-bit table, whose runs keep the numbers
+        they had (the two forms of the layer agree up to fp32 rounding only).  False: off.  True: on, for any table
+        type; a ValueError names the reason where the layer cannot run (another model, more than one part or the rank
+        path, a shape outside gat_input_ok, one of the A/B switches that take its prerequisites away).  `self.gat_input`
+        is the outcome."""
         if feature_dtype not in aggr.FEATURE_DTYPES:
             raise ValueError("feature_dtype must be one of %s, not %r" % (", ".join(aggr.FEATURE_DTYPES), feature_dtype))
         fdt = aggr.FEATURE_DTYPES[feature_dtype]
+        if not any(gat_input is v for v in (None, True, False)):
+            raise ValueError("gat_input must be None, True or False, not %r" % (gat_input,))
+        import os
+        F_in = None
+        if model == "gat":   # (the attention model's input width, known before the rows are loaded)
+            F_in = features.shape[1] if feat_dim is None and not callable(features) else feat_dim
+        gat_D = hidden if len(fanouts) > 1 else (n_classes + 3) // 4 * 4
+        if gat_input is True:
+            # (before any device call: a request the layer cannot serve is an error, never a quiet fall-back)
+            why = None
+            if model != "gat":
+                why = "model is %r, the input layer belongs to model='gat'" % (model,)
+            elif world > 1 or rank_path:
+                why = "more than one part or rank_path: the rank path's attention layer has no aggregate-then-project form"
+            elif F_in is None:
+                why = "the feature width is unknown (pass feat_dim with callable features)"
+            elif not aggr.gat_input_ok(heads, F_in, fanouts[-1], gat_D):
+                why = ("aggr.gat_input_ok(heads=%d, F=%d, fanout=%d, D=%d) is false: heads in (1, 2, 4, 8), F %% 4 == 0, "
+                       "4 <= F <= 128, heads * D <= %d, fanout <= %d" % (heads, F_in, fanouts[-1], gat_D, aggr.GAT_IN_MAX_WIDTH,
+                                                                         aggr.gat_in_max_degree()))
+            elif os.environ.get("CSLICER_NO_TRANSPOSE"):
+                why = "CSLICER_NO_TRANSPOSE is set: the upper layers' slices by source are off"
+            elif splitgnn._NO_LOCAL_FUSE:
+                why = "CSLICER_NO_LOCAL_FUSE is set: the fused single-part layers are off"
+            elif splitgnn._NO_GAT_INPUT:
+                why = "CSLICER_GAT_NO_INPUT_LAYER is set: the input layer is switched off"
+            if why is not None:
+                raise ValueError("gat_input=True: " + why)
         self.rank, self.world, self.dist = rank, world, dist
         self.P = world
         self.dev = torch.device("cuda", device)
@@ -66,7 +102,6 @@ class Trainer(object):
         # one process per part: only this rank's slices are materialised (the sampling itself is replicated).
         # One GPU holding every node (the fused GraphSAGE path): the engine also emits the slices by source, over
         # which the backward gathers its input gradients (CSLICER_NO_TRANSPOSE=1: atomic scatter instead, A/B switch).
-        import os
         by_source = (not self.rank_path and self.P == 1 and model == "sage" and len(fanouts) > 1
                      and not os.environ.get("CSLICER_NO_TRANSPOSE"))
         eng_flags = _abi.FLAG_TRANSPOSE if by_source else 0
@@ -78,12 +113,11 @@ class Trainer(object):
         if (not self.rank_path and self.P == 1 and model == "gat" and not os.environ.get("CSLICER_NO_TRANSPOSE")):
             # GAT aggregates PROJECTED features: every layer's sources take a gradient -- the deepest layer's too, unless
             # it runs aggregate-then-project on the raw feature rows (aggr.GatInputLayer: no source gradient at all)
-            F_in = features.shape[1] if feat_dim is None and not callable(features) else feat_dim
-            # (the input layer's kernels read float32 rows: a 16-bit table takes the project-then-aggregate path)
+            # (gat_input=None: a 16-bit table keeps the project-then-aggregate path its runs have had; True asks for the
+            # input layer, which reads the table in either form)
             self.gat_input = (not splitgnn._NO_GAT_INPUT and not splitgnn._NO_LOCAL_FUSE and F_in is not None
-                              and fdt == torch.float32
-                              and aggr.gat_input_ok(heads, F_in, fanouts[-1],
-                                                    hidden if len(fanouts) > 1 else (n_classes + 3) // 4 * 4))
+                              and (fdt == torch.float32 if gat_input is None else gat_input)
+                              and aggr.gat_input_ok(heads, F_in, fanouts[-1], gat_D))
             eng_flags = _abi.FLAG_TRANSPOSE | (0 if self.gat_input else _abi.FLAG_TRANSPOSE_ALL)
         self.eng = _abi.Engine(indptr, indices, n_parts=self.P, fanouts=fanouts, max_batch=batch,
                                n_streams=streams, n_slots=self.SLOTS, device=device, mode=_abi.MODE_GRAPH,
@@ -564,6 +598,10 @@ def _parser():
                     help="(extra) element type of the feature table resident in HBM (default: float32, or what an L0 "
                          "directory's meta.txt says); a 16-bit table is half the memory and trains bitwise the model of "
                          "the same table upcast to float32")
+    ap.add_argument("--gat-input", choices=("auto", "on", "off"), default="auto",
+                    help="(extra) --model-name gat: the deepest layer as aggregate-then-project on the raw feature rows "
+                         "(`Trainer(gat_input=...)`).  auto: on for a float32 table, off for a 16-bit one; on: for any "
+                         "table type, an error where the layer cannot run; off: never")
     return ap
 
 
@@ -604,8 +642,11 @@ def main(argv=None):
     (`Trainer(feature_dtype=...)`).  Default: float32, or with an L0 directory what its meta.txt records
     (feature_dtype=, cslicer.l0.write_l0); features.bin is memory-mapped in its stored type and, where the two differ,
     the rank's rows are converted on load.
+    --gat-input (extra): auto (default), on or off, `Trainer(gat_input=...)`: whether the attention model's deepest layer
+    aggregates the raw feature rows before it projects.  auto keeps a 16-bit table on the project-then-aggregate path.
 
-        python -m cslicer.train --graph <L0 dir> --feature-dtype bfloat16 --eval-split holdout"""
+        python -m cslicer.train --graph <L0 dir> --feature-dtype bfloat16 --eval-split holdout
+        python -m cslicer.train --graph products-like --model-name gat --feature-dtype bfloat16 --gat-input on"""
     import os
     a = _parser().parse_args(argv)
     from . import l0
@@ -652,7 +693,8 @@ def main(argv=None):
     hidden = a.num_hidden // a.num_heads if kind == "gat" else a.num_hidden
     tr = Trainer(indptr, indices, feats, labels, n_classes, rank=rank, world=world, fanouts=fan, batch=a.batch_size,
                  streams=8, hidden=max(4, hidden // 4 * 4), lr=a.lr, device=local, dist=dist, model=kind, heads=a.num_heads,
-                 workload=workload, feat_dim=fdim, feature_dtype=fdtype)
+                 workload=workload, feat_dim=fdim, feature_dtype=fdtype,
+                 gat_input={"auto": None, "on": True, "off": False}[a.gat_input])
     if rank == 0 and fdtype != "float32":
         print("feature table: %s, %d bytes on this rank" % (fdtype, tr.feat.numel() * tr.feat.element_size()))
     n = indptr.shape[0] - 1

@@ -24,8 +24,11 @@
 #include <cstdlib>
 
 #include "cslicer_aggr.h"
+#include "cslicer_gat_in16.h"
 #include "cslicer_hip.h"
 #include "dev_common.h"
+#include "feat_elem.h"
+#include "table_readers.h"
 
 namespace {
 
@@ -110,17 +113,30 @@ __device__ __forceinline__ RowIdx load_row_idx(const int* __restrict__ indptr, c
   return ri;
 }
 
+// E is the element type of the feature table x (feat_elem.h: float, feat::f16, feat::bf16).  A lane loads its quad of a
+// row as Elem<E>::Raw -- 16 bytes of a float32 table, 8 of a 16-bit one; ldx and the row arithmetic count ELEMENTS -- and
+// the rows stay in registers AS LOADED (two registers a quad instead of four), upcast where a pass consumes them (the
+// compiler converts a quad at its first use and keeps the result for the second pass where registers allow).  Upcast once
+// right after the masks instead, the 16-bit <8, 12> forward spilled (20 bytes of scratch) and no instance gained the wave
+// per SIMD that five float16 instances gain this way (DESIGN 4.5 has the figures).  Both upcasts are exact and everything
+// behind them is the float32 code, so a 16-bit table gives bitwise what its float32 copy gives.
+// A masked-out row is Elem<E>::zero(): all-zero bits, 0.0 in the three formats.  (For E = float that is spelled zero4, the
+// kernel's one zero object: with a second constant of the same value the compiler orders the forward's registers
+// differently, and the float32 instances are kept instruction-identical to the kernels before the template.)
+
 // forward: agg[r, h, :] = sum_e alpha[e, h] x[src_e];  alpha[e, h] (its sign bit: the logit was <= 0) is kept for the
 // backward.  A row with more than ME edges (a max_deg below the true one) gets agg[r] = NaN: no host-side check, no sync.
-template <int H, int ME>
+template <int H, int ME, typename E>
 __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(ME <= 16 ? 3 : 1, 8))) void k_gatin_fwd(const int* __restrict__ indptr, const int* __restrict__ indices,
                                                    const int* __restrict__ self_ids, const int* __restrict__ rowmap,
-                                                   const float* __restrict__ x, long long ldx, int F,
+                                                   const E* __restrict__ x, long long ldx, int F,
                                                    const float* __restrict__ vl, const float* __restrict__ vr, float slope,
                                                    long long n_out, float* __restrict__ agg, float* __restrict__ alpha) {
   constexpr int EPG = 32 / H;              // edges per reduction group
   constexpr int NG = ME / EPG;             // groups of a row
   static_assert(ME % EPG == 0 && ME <= GATIN_MAX_DEG, "whole groups");
+  typedef feat::Elem<E> El;
+  typedef typename El::Raw Raw;
   __shared__ __attribute__((aligned(16))) float s_al[RPB][ME * H];
   const int q = threadIdx.x & 31, g = threadIdx.x >> 5, half = threadIdx.x & 32;
   const bool on = 4 * q < F;
@@ -155,18 +171,21 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(ME <= 16 ? 
   const int e0 = ri.e0, deg = ri.deg;
   const int degmax = max(deg, __shfl_xor(deg, 32));          // wave-uniform
   // every feature row the first pass needs is requested before any is used
-  float4 xe[ME];
+  Raw xe[ME];
 #pragma unroll
   for (int j = 0; j < ME; j++) {
     const long long row = __shfl(ri.xrow_q, half | j);
-    xe[j] = *reinterpret_cast<const float4*>(x + row * ldx + col);
+    xe[j] = El::ld(x + row * ldx + col);
   }
-  float4 xs = *reinterpret_cast<const float4*>(x + ri.srow * ldx + col);
+  float4 xs = El::up(El::ld(x + ri.srow * ldx + col));
   nx = load_row_idx(indptr, indices, self_ids, rowmap, r + stride, r + stride < n_out, q, ME);
   if (!on || ri.sid < 0) xs = zero4;
 #pragma unroll
   for (int j = 0; j < ME; j++)
-    if (!on || j >= deg) xe[j] = zero4;
+    if (!on || j >= deg) {
+      if constexpr (std::is_same<E, float>::value) xe[j] = zero4;
+      else xe[j] = El::zero();
+    }
   float er_mine;
   {
     float pv[H];
@@ -185,7 +204,7 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(ME <= 16 ? 
 #pragma unroll
       for (int j = 0; j < EPG; j++)
 #pragma unroll
-        for (int h = 0; h < H; h++) v[j * H + h] = dot4(xe[c * EPG + j], wl[h]);
+        for (int h = 0; h < H; h++) v[j * H + h] = dot4(El::up(xe[c * EPG + j]), wl[h]);
       const float t = treduce32<32>(v, q);                   // lane q: edge q / H of the group, head q % H
       __builtin_amdgcn_sched_barrier(0);                     // (groups interleaved by the scheduler: 32 more registers each)
       const float raw = t + er_mine;
@@ -226,7 +245,7 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(ME <= 16 ? 
     if (j < degmax) {                                        // wave-uniform
       asm volatile("" ::: "memory");   // (all 12 x 8 weights read ahead would cost 96 registers)
 #pragma unroll
-      for (int h = 0; h < H; h++) fma4(acc[h], s_al[g][j * H + h], xe[j]);   // (zero weights and rows for j >= deg)
+      for (int h = 0; h < H; h++) fma4(acc[h], s_al[g][j * H + h], El::up(xe[j]));   // (zero weights and rows for j >= deg)
     }
   }
   if (rowok && on) {
@@ -247,10 +266,10 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(ME <= 16 ? 
 // edges poisons its block's partial sums with NaN (and with them g_vl / g_vr), as the forward poisons its output row.
 //   dalpha[e, h] = <dagg[r, h], x[src_e]>      dlogit = alpha (dalpha - sum_e alpha dalpha)      draw = dlogit * leaky'
 //   dv_l[h] += draw[e, h] x[src_e]             dv_r[h] += (sum_e draw[e, h]) x[self(r)]
-template <int H, int ME>
+template <int H, int ME, typename E>
 __global__ __launch_bounds__(BLK) void k_gatin_bwd(const int* __restrict__ indptr, const int* __restrict__ indices,
                                                    const int* __restrict__ self_ids, const int* __restrict__ rowmap,
-                                                   const float* __restrict__ x, long long ldx, int F,
+                                                   const E* __restrict__ x, long long ldx, int F,
                                                    const float* __restrict__ alpha, const float* __restrict__ dagg,
                                                    long long ld_r, long long ld_h, float slope, long long n_out,
                                                    long long rows_per_block, float* __restrict__ part_l,
@@ -258,6 +277,8 @@ __global__ __launch_bounds__(BLK) void k_gatin_bwd(const int* __restrict__ indpt
   constexpr int EPG = 32 / H;
   constexpr int NG = ME / EPG;
   static_assert(ME % EPG == 0 && ME <= GATIN_MAX_DEG, "whole groups");
+  typedef feat::Elem<E> El;
+  typedef typename El::Raw Raw;
   __shared__ __attribute__((aligned(16))) float s_dr[RPB][ME * H];
   __shared__ __attribute__((aligned(16))) float s_der[RPB][8];
   __shared__ float4 s_red[RPB][32];
@@ -282,13 +303,13 @@ __global__ __launch_bounds__(BLK) void k_gatin_bwd(const int* __restrict__ indpt
     const RowIdx ri = nx;
     const int e0 = ri.e0, deg = ri.deg;
     const int degmax = max(deg, __shfl_xor(deg, 32));
-    float4 xe[ME];
+    Raw xe[ME];
 #pragma unroll
     for (int j = 0; j < ME; j++) {
       const long long row = __shfl(ri.xrow_q, half | j);
-      xe[j] = *reinterpret_cast<const float4*>(x + row * ldx + col);
+      xe[j] = El::ld(x + row * ldx + col);
     }
-    float4 xs = *reinterpret_cast<const float4*>(x + ri.srow * ldx + col);
+    float4 xs = El::up(El::ld(x + ri.srow * ldx + col));
     const long long rr = rowok ? r : 0;
     float4 da[H];
 #pragma unroll
@@ -304,8 +325,11 @@ __global__ __launch_bounds__(BLK) void k_gatin_bwd(const int* __restrict__ indpt
     if (!on || ri.sid < 0) xs = zero4;
 #pragma unroll
     for (int j = 0; j < ME; j++)
-      if (!on || j >= deg) xe[j] = zero4;
-#pragma unroll
+      if (!on || j >= deg) {
+        if constexpr (std::is_same<E, float>::value) xe[j] = zero4;
+        else xe[j] = El::zero();
+      }
+    #pragma unroll
     for (int h = 0; h < H; h++)
       if (!on || !rowok) da[h] = zero4;
     float dal[NG];
@@ -318,7 +342,7 @@ __global__ __launch_bounds__(BLK) void k_gatin_bwd(const int* __restrict__ indpt
 #pragma unroll
         for (int j = 0; j < EPG; j++)
 #pragma unroll
-          for (int h = 0; h < H; h++) v[j * H + h] = dot4(xe[c * EPG + j], da[h]);
+          for (int h = 0; h < H; h++) v[j * H + h] = dot4(El::up(xe[c * EPG + j]), da[h]);
         dal[c] = treduce32<32>(v, q);
         __builtin_amdgcn_sched_barrier(0);                   // (groups interleaved by the scheduler: 32 more registers each)
         tsum += fabsf(av[c]) * dal[c];
@@ -344,7 +368,7 @@ __global__ __launch_bounds__(BLK) void k_gatin_bwd(const int* __restrict__ indpt
       if (j < degmax) {
         asm volatile("" ::: "memory");
 #pragma unroll
-        for (int h = 0; h < H; h++) fma4(accl[h], s_dr[g][j * H + h], xe[j]);
+        for (int h = 0; h < H; h++) fma4(accl[h], s_dr[g][j * H + h], El::up(xe[j]));
       }
     }
 #pragma unroll
@@ -748,6 +772,150 @@ void with_bd_tile(int kt, int nt, F&& f) {
 
 }  // namespace
 
+// ---- the two edge passes' host paths (table_readers.h): one for a float32 and a 16-bit table each
+
+namespace {
+
+bool edge_shape_bad(int64_t n_out, int64_t n_edges, int32_t max_deg, int32_t H, int32_t F, int64_t ldx) {
+  return n_out < 0 || n_edges < 0 || max_deg < 0 || max_deg > GATIN_MAX_DEG || !heads_ok(H) || F < 4 || F % 4 != 0 || F > 128 ||
+         ldx % 4 != 0 || ldx < F;
+}
+// a float32 table the kernels cannot load from (a 16-bit one: rd::table16_bad, whatever the row count)
+bool table32_bad(const void* x, int32_t kind) { return kind == 0 && (!x || !aligned16(x)); }
+
+// What the edge passes refuse, from their arguments alone: no HIP call.  The layer sequencers ask before their first
+// launch, so that a refused layer call has issued nothing.
+bool fwd_bad(const int32_t* indptr, const int32_t* indices, const int32_t* self_ids, const void* x, int32_t kind, int64_t ldx,
+             int32_t F, const float* vl, const float* vr, int32_t H, int64_t n_out, int64_t n_edges, int32_t max_deg,
+             const float* agg, const float* alpha) {
+  if (rd::table16_bad(x, kind, ldx, F) || edge_shape_bad(n_out, n_edges, max_deg, H, F, ldx)) return true;
+  if (n_out == 0) return false;
+  if (!indptr || !self_ids || table32_bad(x, kind) || !vl || !vr || !agg || !aligned16(vl) || !aligned16(vr) || !aligned16(agg))
+    return true;
+  return n_edges > 0 && (!indices || !alpha);
+}
+bool bwd_bad(const int32_t* indptr, const int32_t* indices, const int32_t* self_ids, const void* x, int32_t kind, int64_t ldx,
+             int32_t F, const float* alpha, const float* dagg, int64_t ld_r, int64_t ld_h, int32_t H, int64_t n_out,
+             int64_t n_edges, int32_t max_deg, const float* g_vl, const float* g_vr, const float* scratch) {
+  if (rd::table16_bad(x, kind, ldx, F) || edge_shape_bad(n_out, n_edges, max_deg, H, F, ldx) || ld_r % 4 != 0 || ld_h % 4 != 0)
+    return true;
+  if (!g_vl || !g_vr || !aligned16(g_vl) || !aligned16(g_vr)) return true;
+  if (n_out == 0 || n_edges == 0) return false;
+  return !indptr || !indices || !self_ids || table32_bad(x, kind) || !alpha || !dagg || !scratch || !aligned16(dagg) ||
+         !aligned16(scratch);
+}
+
+}  // namespace
+
+int rd::gat_in_fwd(const int32_t* indptr, const int32_t* indices, const int32_t* self_ids, const int32_t* rowmap, const void* x,
+                   int32_t kind, int64_t ldx, int32_t F, const float* vl, const float* vr, int32_t H, float slope,
+                   int64_t n_out, int64_t n_edges, int32_t max_deg, float* agg, float* alpha, void* stream) {
+  if (fwd_bad(indptr, indices, self_ids, x, kind, ldx, F, vl, vr, H, n_out, n_edges, max_deg, agg, alpha)) return CSL_E_INVALID;
+  if (n_out == 0) return CSL_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if (n_edges == 0) {   // (no index to read: every row is empty)
+    return hipMemsetAsync(agg, 0, sizeof(float) * (size_t)n_out * H * F, st) == hipSuccess ? CSL_OK : CSL_E_HIP;
+  }
+  long long need = (n_out + RPB - 1) / RPB;
+  const unsigned blocks = (unsigned)(need < 768 ? need : 768);   // three workgroups per CU (all resident) walk the rows
+  with_table(kind, [&](auto e) {
+    typedef typename decltype(e)::type E;
+    with_gatin_instance(H, max_deg, [&](auto h, auto me) {
+      hipLaunchKernelGGL((k_gatin_fwd<h(), me(), E>), dim3(blocks), dim3(BLK), 0, st, indptr, indices, self_ids, rowmap,
+                         static_cast<const E*>(x), (long long)ldx, (int)F, vl, vr, slope, (long long)n_out, agg, alpha);
+    });
+  });
+  return done();
+}
+
+int rd::gat_in_bwd(const int32_t* indptr, const int32_t* indices, const int32_t* self_ids, const int32_t* rowmap, const void* x,
+                   int32_t kind, int64_t ldx, int32_t F, const float* alpha, const float* dagg, int64_t ld_r, int64_t ld_h,
+                   int32_t H, float slope, int64_t n_out, int64_t n_edges, int32_t max_deg, float* g_vl, float* g_vr,
+                   float* scratch, void* stream) {
+  if (bwd_bad(indptr, indices, self_ids, x, kind, ldx, F, alpha, dagg, ld_r, ld_h, H, n_out, n_edges, max_deg, g_vl, g_vr, scratch))
+    return CSL_E_INVALID;
+  hipStream_t st = (hipStream_t)stream;
+  if (n_out == 0 || n_edges == 0) {   // no edge: no attention, no gradient through the logits
+    if (hipMemsetAsync(g_vl, 0, sizeof(float) * (size_t)H * F, st) != hipSuccess) return CSL_E_HIP;
+    return hipMemsetAsync(g_vr, 0, sizeof(float) * (size_t)H * F, st) == hipSuccess ? CSL_OK : CSL_E_HIP;
+  }
+  const long long rpb = bwd_rows(n_out);
+  const long long blocks = (n_out + rpb - 1) / rpb;
+  float* part_l = scratch;
+  float* part_r = scratch + blocks * H * F;
+  with_table(kind, [&](auto e) {
+    typedef typename decltype(e)::type E;
+    with_gatin_instance(H, max_deg, [&](auto h, auto me) {
+      hipLaunchKernelGGL((k_gatin_bwd<h(), me(), E>), dim3((unsigned)blocks), dim3(BLK), 0, st, indptr, indices, self_ids, rowmap,
+                         static_cast<const E*>(x), (long long)ldx, (int)F, alpha, dagg, (long long)ld_r, (long long)ld_h, slope,
+                         (long long)n_out, rpb, part_l, part_r);
+    });
+  });
+  if (hipGetLastError() != hipSuccess) return CSL_E_HIP;
+  const float* src[2] = {part_l, part_r};
+  const int64_t nblk[2] = {blocks, blocks};
+  const int32_t Hs[2] = {H * F, H * F};
+  float* dst[2] = {g_vl, g_vr};
+  return reduce_or_defer(2, src, nblk, Hs, dst, stream);
+}
+
+// ---- the whole layer as one call per direction: one body for the float32 entry point and its 16-bit twin.  `kind` goes
+// to the edge pass (its argument check, asked before the first launch, and its call) and nowhere else.
+
+namespace {
+
+int layer_fwd(const int32_t* indptr, const int32_t* indices, const int32_t* self_ids, const int32_t* rowmap, const void* x,
+              int32_t kind, int64_t ldx, int32_t F, const float* W, const float* attn_l, const float* attn_r, const float* bias,
+              int32_t H, int32_t D, float slope, int32_t elu, int64_t n_out, int64_t n_edges, int32_t max_deg, float* agg,
+              float* alpha, float* out, int64_t ldo, float* scratch, void* stream) {
+  if (!bd_ok(H, F, D) || !W || !attn_l || !attn_r || !scratch || !aligned16(scratch)) return CSL_E_INVALID;
+  float* vl = scratch;
+  float* vr = scratch + (size_t)H * F;
+  if (fwd_bad(indptr, indices, self_ids, x, kind, ldx, F, vl, vr, H, n_out, n_edges, max_deg, agg, alpha)) return CSL_E_INVALID;
+  hipLaunchKernelGGL(k_gatin_vlr, dim3((unsigned)((H * F + BLK - 1) / BLK)), dim3(BLK), 0, (hipStream_t)stream, W, attn_l, attn_r,
+                     (int)H, (int)D, (int)F, scratch);
+  int rc = rd::gat_in_fwd(indptr, indices, self_ids, rowmap, x, kind, ldx, F, vl, vr, H, slope, n_out, n_edges, max_deg, agg,
+                          alpha, stream);
+  if (rc != CSL_OK) return rc;
+  return csl_gat_in_proj_f32(agg, W, bias, n_out, H, F, D, elu, out, ldo, stream);
+}
+
+int layer_bwd(const int32_t* indptr, const int32_t* indices, const int32_t* self_ids, const int32_t* rowmap, const void* x,
+              int32_t kind, int64_t ldx, int32_t F, const float* W, const float* attn_l, const float* attn_r, int32_t H, int32_t D,
+              float slope, int32_t elu, int64_t n_out, int64_t n_edges, int32_t max_deg, const float* agg, const float* alpha,
+              const float* out, int64_t ldo, const float* g, int64_t ldg, float* gg, float* dagg, float* gW, float* g_al,
+              float* g_ar, float* g_bias, float* scratch, void* stream) {
+  if (!bd_ok(H, F, D) || !W || !attn_l || !attn_r || !gW || !g_al || !g_ar || !g_bias || !scratch || !aligned16(scratch) || n_out < 0)
+    return CSL_E_INVALID;
+  const int C = H * D, FP = 16 * bd_kt(F);
+  float* s_elu = scratch;
+  float* s_dw = s_elu + up4(csl_elu_bwd_colsum_scratch(n_out, C));
+  float* s_in = s_dw + up4(csl_gat_in_proj_bwd_scratch(H, F, D));
+  float* g_v = s_in + up4(csl_gat_in_bwd_scratch(n_out, H, F));
+  if (bwd_bad(indptr, indices, self_ids, x, kind, ldx, F, alpha, dagg, (int64_t)H * FP, FP, H, n_out, n_edges, max_deg, g_v,
+              g_v + (size_t)H * F, s_in))
+    return CSL_E_INVALID;
+  DeferredSums jobs;
+  jobs.count = 0;
+  g_defer = &jobs;
+  int rc = csl_elu_bwd_colsum_f32(g, ldg, out, ldo, n_out, C, elu, gg, C, g_bias, s_elu, stream);
+  if (rc == CSL_OK) rc = csl_gat_in_proj_bwd_f32(gg, C, agg, W, n_out, H, F, D, dagg, gW, s_dw, stream);
+  if (rc == CSL_OK)
+    rc = rd::gat_in_bwd(indptr, indices, self_ids, rowmap, x, kind, ldx, F, alpha, dagg, (int64_t)H * FP, FP, H, slope, n_out,
+                        n_edges, max_deg, g_v, g_v + (size_t)H * F, s_in, stream);
+  g_defer = nullptr;
+  if (rc != CSL_OK) return rc;
+  if (jobs.count) {
+    rc = csl_reduce_multi_f32(jobs.count, jobs.src, jobs.nblk, jobs.H, jobs.dst, stream);
+    if (rc != CSL_OK) return rc;
+  }
+  hipLaunchKernelGGL(k_gatin_chain, dim3((unsigned)((C + BLK / 64 - 1) / (BLK / 64))), dim3(BLK), 0, (hipStream_t)stream, W, attn_l,
+                     attn_r, g_v, (int)H, (int)D, (int)F, gW, g_al, g_ar);
+  return done();
+}
+
+}  // namespace
+
 extern "C" {
 
 int32_t csl_gat_in_max_degree(void) { return GATIN_MAX_DEG; }
@@ -755,22 +923,16 @@ int32_t csl_gat_in_max_degree(void) { return GATIN_MAX_DEG; }
 int csl_gat_in_fwd_f32(const int32_t* indptr, const int32_t* indices, const int32_t* self_ids, const int32_t* rowmap,
                        const float* x, int64_t ldx, int32_t F, const float* vl, const float* vr, int32_t H, float slope,
                        int64_t n_out, int64_t n_edges, int32_t max_deg, float* agg, float* alpha, void* stream) {
-  if (n_out < 0 || n_edges < 0 || max_deg < 0 || max_deg > GATIN_MAX_DEG || !heads_ok(H) || F < 4 || F % 4 != 0 || F > 128 || ldx % 4 != 0 || ldx < F) return CSL_E_INVALID;
-  if (n_out == 0) return CSL_OK;
-  if (!indptr || !self_ids || !x || !vl || !vr || !agg || !aligned16(x) || !aligned16(vl) || !aligned16(vr) || !aligned16(agg))
-    return CSL_E_INVALID;
-  hipStream_t st = (hipStream_t)stream;
-  if (n_edges == 0) {   // (no index to read: every row is empty)
-    return hipMemsetAsync(agg, 0, sizeof(float) * (size_t)n_out * H * F, st) == hipSuccess ? CSL_OK : CSL_E_HIP;
-  }
-  if (!indices || !alpha) return CSL_E_INVALID;
-  long long need = (n_out + RPB - 1) / RPB;
-  const unsigned blocks = (unsigned)(need < 768 ? need : 768);   // three workgroups per CU (all resident) walk the rows
-  with_gatin_instance(H, max_deg, [&](auto h, auto me) {
-    hipLaunchKernelGGL((k_gatin_fwd<h(), me()>), dim3(blocks), dim3(BLK), 0, st, indptr, indices, self_ids, rowmap, x,
-                       (long long)ldx, (int)F, vl, vr, slope, (long long)n_out, agg, alpha);
-  });
-  return done();
+  return rd::gat_in_fwd(indptr, indices, self_ids, rowmap, x, 0, ldx, F, vl, vr, H, slope, n_out, n_edges, max_deg, agg, alpha,
+                        stream);
+}
+
+int csl_gat_in_fwd_x16(const int32_t* indptr, const int32_t* indices, const int32_t* self_ids, const int32_t* rowmap,
+                       const void* x, int32_t kind, int64_t ldx, int32_t F, const float* vl, const float* vr, int32_t H,
+                       float slope, int64_t n_out, int64_t n_edges, int32_t max_deg, float* agg, float* alpha, void* stream) {
+  if (!feat::kind_ok(kind)) return CSL_E_INVALID;
+  return rd::gat_in_fwd(indptr, indices, self_ids, rowmap, x, kind, ldx, F, vl, vr, H, slope, n_out, n_edges, max_deg, agg,
+                        alpha, stream);
 }
 
 int64_t csl_gat_in_bwd_scratch(int64_t n_out, int32_t H, int32_t F) {
@@ -783,33 +945,17 @@ int csl_gat_in_bwd_f32(const int32_t* indptr, const int32_t* indices, const int3
                        const float* x, int64_t ldx, int32_t F, const float* alpha, const float* dagg, int64_t ld_r,
                        int64_t ld_h, int32_t H, float slope, int64_t n_out, int64_t n_edges, int32_t max_deg, float* g_vl,
                        float* g_vr, float* scratch, void* stream) {
-  if (n_out < 0 || n_edges < 0 || max_deg < 0 || max_deg > GATIN_MAX_DEG || !heads_ok(H) || F < 4 || F % 4 != 0 || F > 128 || ldx % 4 != 0 || ldx < F || ld_r % 4 != 0 ||
-      ld_h % 4 != 0)
-    return CSL_E_INVALID;
-  if (!g_vl || !g_vr || !aligned16(g_vl) || !aligned16(g_vr)) return CSL_E_INVALID;
-  hipStream_t st = (hipStream_t)stream;
-  if (n_out == 0 || n_edges == 0) {   // no edge: no attention, no gradient through the logits
-    if (hipMemsetAsync(g_vl, 0, sizeof(float) * (size_t)H * F, st) != hipSuccess) return CSL_E_HIP;
-    return hipMemsetAsync(g_vr, 0, sizeof(float) * (size_t)H * F, st) == hipSuccess ? CSL_OK : CSL_E_HIP;
-  }
-  if (!indptr || !indices || !self_ids || !x || !alpha || !dagg || !scratch || !aligned16(x) || !aligned16(dagg) ||
-      !aligned16(scratch))
-    return CSL_E_INVALID;
-  const long long rpb = bwd_rows(n_out);
-  const long long blocks = (n_out + rpb - 1) / rpb;
-  float* part_l = scratch;
-  float* part_r = scratch + blocks * H * F;
-  with_gatin_instance(H, max_deg, [&](auto h, auto me) {
-    hipLaunchKernelGGL((k_gatin_bwd<h(), me()>), dim3((unsigned)blocks), dim3(BLK), 0, st, indptr, indices, self_ids, rowmap, x,
-                       (long long)ldx, (int)F, alpha, dagg, (long long)ld_r, (long long)ld_h, slope, (long long)n_out, rpb,
-                       part_l, part_r);
-  });
-  if (hipGetLastError() != hipSuccess) return CSL_E_HIP;
-  const float* src[2] = {part_l, part_r};
-  const int64_t nblk[2] = {blocks, blocks};
-  const int32_t Hs[2] = {H * F, H * F};
-  float* dst[2] = {g_vl, g_vr};
-  return reduce_or_defer(2, src, nblk, Hs, dst, stream);
+  return rd::gat_in_bwd(indptr, indices, self_ids, rowmap, x, 0, ldx, F, alpha, dagg, ld_r, ld_h, H, slope, n_out, n_edges,
+                        max_deg, g_vl, g_vr, scratch, stream);
+}
+
+int csl_gat_in_bwd_x16(const int32_t* indptr, const int32_t* indices, const int32_t* self_ids, const int32_t* rowmap,
+                       const void* x, int32_t kind, int64_t ldx, int32_t F, const float* alpha, const float* dagg,
+                       int64_t ld_r, int64_t ld_h, int32_t H, float slope, int64_t n_out, int64_t n_edges, int32_t max_deg,
+                       float* g_vl, float* g_vr, float* scratch, void* stream) {
+  if (!feat::kind_ok(kind)) return CSL_E_INVALID;
+  return rd::gat_in_bwd(indptr, indices, self_ids, rowmap, x, kind, ldx, F, alpha, dagg, ld_r, ld_h, H, slope, n_out, n_edges,
+                        max_deg, g_vl, g_vr, scratch, stream);
 }
 
 int csl_bias_elu_f32(float* y, int64_t ldy, const float* bias, int64_t n, int32_t C, int32_t elu, void* stream) {
@@ -911,13 +1057,18 @@ int csl_gat_in_layer_fwd_f32(const int32_t* indptr, const int32_t* indices, cons
                              const float* x, int64_t ldx, int32_t F, const float* W, const float* attn_l, const float* attn_r,
                              const float* bias, int32_t H, int32_t D, float slope, int32_t elu, int64_t n_out, int64_t n_edges,
                              int32_t max_deg, float* agg, float* alpha, float* out, int64_t ldo, float* scratch, void* stream) {
-  if (!bd_ok(H, F, D) || !W || !attn_l || !attn_r || !scratch || !aligned16(scratch)) return CSL_E_INVALID;
-  hipLaunchKernelGGL(k_gatin_vlr, dim3((unsigned)((H * F + BLK - 1) / BLK)), dim3(BLK), 0, (hipStream_t)stream, W, attn_l, attn_r,
-                     (int)H, (int)D, (int)F, scratch);
-  int rc = csl_gat_in_fwd_f32(indptr, indices, self_ids, rowmap, x, ldx, F, scratch, scratch + (size_t)H * F, H, slope, n_out,
-                              n_edges, max_deg, agg, alpha, stream);
-  if (rc != CSL_OK) return rc;
-  return csl_gat_in_proj_f32(agg, W, bias, n_out, H, F, D, elu, out, ldo, stream);
+  return layer_fwd(indptr, indices, self_ids, rowmap, x, 0, ldx, F, W, attn_l, attn_r, bias, H, D, slope, elu, n_out, n_edges,
+                   max_deg, agg, alpha, out, ldo, scratch, stream);
+}
+
+int csl_gat_in_layer_fwd_x16(const int32_t* indptr, const int32_t* indices, const int32_t* self_ids, const int32_t* rowmap,
+                             const void* x, int32_t kind, int64_t ldx, int32_t F, const float* W, const float* attn_l,
+                             const float* attn_r, const float* bias, int32_t H, int32_t D, float slope, int32_t elu,
+                             int64_t n_out, int64_t n_edges, int32_t max_deg, float* agg, float* alpha, float* out, int64_t ldo,
+                             float* scratch, void* stream) {
+  if (!feat::kind_ok(kind)) return CSL_E_INVALID;
+  return layer_fwd(indptr, indices, self_ids, rowmap, x, kind, ldx, F, W, attn_l, attn_r, bias, H, D, slope, elu, n_out,
+                   n_edges, max_deg, agg, alpha, out, ldo, scratch, stream);
 }
 
 int64_t csl_gat_in_layer_bwd_scratch(int64_t n_out, int32_t H, int32_t F, int32_t D) {
@@ -931,30 +1082,19 @@ int csl_gat_in_layer_bwd_f32(const int32_t* indptr, const int32_t* indices, cons
                              const float* agg, const float* alpha, const float* out, int64_t ldo, const float* g, int64_t ldg,
                              float* gg, float* dagg, float* gW, float* g_al, float* g_ar, float* g_bias, float* scratch,
                              void* stream) {
-  if (!bd_ok(H, F, D) || !W || !attn_l || !attn_r || !gW || !g_al || !g_ar || !g_bias || !scratch || !aligned16(scratch) || n_out < 0)
-    return CSL_E_INVALID;
-  const int C = H * D, FP = 16 * bd_kt(F);
-  float* s_elu = scratch;
-  float* s_dw = s_elu + up4(csl_elu_bwd_colsum_scratch(n_out, C));
-  float* s_in = s_dw + up4(csl_gat_in_proj_bwd_scratch(H, F, D));
-  float* g_v = s_in + up4(csl_gat_in_bwd_scratch(n_out, H, F));
-  DeferredSums jobs;
-  jobs.count = 0;
-  g_defer = &jobs;
-  int rc = csl_elu_bwd_colsum_f32(g, ldg, out, ldo, n_out, C, elu, gg, C, g_bias, s_elu, stream);
-  if (rc == CSL_OK) rc = csl_gat_in_proj_bwd_f32(gg, C, agg, W, n_out, H, F, D, dagg, gW, s_dw, stream);
-  if (rc == CSL_OK)
-    rc = csl_gat_in_bwd_f32(indptr, indices, self_ids, rowmap, x, ldx, F, alpha, dagg, (int64_t)H * FP, FP, H, slope, n_out,
-                            n_edges, max_deg, g_v, g_v + (size_t)H * F, s_in, stream);
-  g_defer = nullptr;
-  if (rc != CSL_OK) return rc;
-  if (jobs.count) {
-    rc = csl_reduce_multi_f32(jobs.count, jobs.src, jobs.nblk, jobs.H, jobs.dst, stream);
-    if (rc != CSL_OK) return rc;
-  }
-  hipLaunchKernelGGL(k_gatin_chain, dim3((unsigned)((C + BLK / 64 - 1) / (BLK / 64))), dim3(BLK), 0, (hipStream_t)stream, W, attn_l,
-                     attn_r, g_v, (int)H, (int)D, (int)F, gW, g_al, g_ar);
-  return done();
+  return layer_bwd(indptr, indices, self_ids, rowmap, x, 0, ldx, F, W, attn_l, attn_r, H, D, slope, elu, n_out, n_edges, max_deg,
+                   agg, alpha, out, ldo, g, ldg, gg, dagg, gW, g_al, g_ar, g_bias, scratch, stream);
+}
+
+int csl_gat_in_layer_bwd_x16(const int32_t* indptr, const int32_t* indices, const int32_t* self_ids, const int32_t* rowmap,
+                             const void* x, int32_t kind, int64_t ldx, int32_t F, const float* W, const float* attn_l,
+                             const float* attn_r, int32_t H, int32_t D, float slope, int32_t elu, int64_t n_out,
+                             int64_t n_edges, int32_t max_deg, const float* agg, const float* alpha, const float* out,
+                             int64_t ldo, const float* g, int64_t ldg, float* gg, float* dagg, float* gW, float* g_al,
+                             float* g_ar, float* g_bias, float* scratch, void* stream) {
+  if (!feat::kind_ok(kind)) return CSL_E_INVALID;
+  return layer_bwd(indptr, indices, self_ids, rowmap, x, kind, ldx, F, W, attn_l, attn_r, H, D, slope, elu, n_out, n_edges,
+                   max_deg, agg, alpha, out, ldo, g, ldg, gg, dagg, gW, g_al, g_ar, g_bias, scratch, stream);
 }
 
 }  // extern "C"
