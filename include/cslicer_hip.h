@@ -154,7 +154,16 @@ enum {
   CSL_FLAG_TRANSPOSE = 4,
   /* with CSL_FLAG_TRANSPOSE: the deepest layer too (a consumer whose aggregation acts on projected features -- GAT --
    * needs the gradient of every layer's sources) */
-  CSL_FLAG_TRANSPOSE_ALL = 8
+  CSL_FLAG_TRANSPOSE_ALL = 8,
+  /* CSL_MODE_GRAPH only: a row with deg >= fanout yields `fanout` DISTINCT edge positions (the default of
+   * dgl.sampling.sample_neighbors, which the reference's Python trainers sample with) instead of `fanout` independent
+   * draws.  The row consumes the same `fanout` mt19937 words r_0..r_{f-1} at the same positions; only the map from
+   * draws to positions is Floyd's subset algorithm: for j = 0..f-1, J = deg - f + j, t = r_j % (J + 1),
+   * pick_j = (t among pick_0..pick_{j-1}) ? J : t, and candidate slot j+1 is indices[off + pick_j].  Rows with
+   * deg < fanout keep all their edges in order; draws, rng positions and everything behind the candidate stream are
+   * unchanged.  Picks are edge positions: parallel edges can still give one neighbour twice.  Every fanout must be
+   * <= csl_noreplace_max_fanout(); refused with CSL_MODE_STRICT. */
+  CSL_FLAG_NO_REPLACE = 16
 };
 
 typedef struct {
@@ -187,6 +196,8 @@ typedef struct csl_engine csl_engine;
 
 const char* csl_last_error(void);
 int csl_abi_version(void);
+/* largest fanout CSL_FLAG_NO_REPLACE accepts (64) */
+int csl_noreplace_max_fanout(void);
 
 /* CSlicer::CSlicer + WorkerPool::WorkerPool + Slicer::Slicer (pyfrontend.cpp:41-70,
  * WorkerPool.cpp:4-35, slicer.h:41-70): uploads the CSR, allocates the per-stream

@@ -26,6 +26,7 @@ FLAG_SERIAL_ROUNDS = 1
 FLAG_KEEP_CANDIDATES = 2
 FLAG_TRANSPOSE = 4   # graph mode: also the slices by source (T_INDPTR / T_INDICES), every layer but the deepest
 FLAG_TRANSPOSE_ALL = 8   # ... the deepest too (with FLAG_TRANSPOSE)
+FLAG_NO_REPLACE = 16     # graph mode: rows with deg >= fanout pick distinct edge positions (Floyd), same draws
 T_SORTED_MAX = 128       # lists of a slice by source up to this length are sorted; longer ones (hubs) are not
 LIST_KINDS = {
     "in_nodes": IN_NODES, "out_nodes": OUT_NODES, "owned_out_nodes": OWNED_OUT_NODES,
@@ -41,6 +42,7 @@ SYMBOLS = [
     "csl_timing_enable", "csl_timing_read", "csl_kernel_name", "csl_rng_peek", "csl_device_bytes",
     "csl_debug_wave_duplicates",
     "csl_fetch_sample", "csl_fetch_sample32", "csl_totals", "csl_arena_info", "csl_copy_candidates",
+    "csl_noreplace_max_fanout",
 ]
 
 
@@ -158,6 +160,7 @@ def load():
     vp = C.c_void_p
     L.csl_last_error.restype = C.c_char_p
     L.csl_abi_version.restype = C.c_int
+    L.csl_noreplace_max_fanout.restype = C.c_int
     L.csl_create.argtypes = [C.POINTER(Config), C.POINTER(vp)]
     L.csl_destroy.argtypes = [vp]
     L.csl_destroy.restype = None
@@ -198,6 +201,11 @@ def _check(rc):
     if rc < 0:
         raise CslError(rc, load().csl_last_error().decode())
     return rc
+
+
+def noreplace_max_fanout():
+    """largest fanout FLAG_NO_REPLACE accepts (csl_noreplace_max_fanout)"""
+    return int(load().csl_noreplace_max_fanout())
 
 
 ERR_FRONTIER_CAP = 8

@@ -31,7 +31,7 @@ class Trainer(object):
     def __init__(self, indptr, indices, features, labels, n_classes, rank=0, world=1, fanouts=(15, 10, 5),
                  batch=1024, streams=8, hidden=256, lr=1e-3, device=0, dist=None, seed=0, overlap=False,
                  model="sage", heads=8, rank_path=None, workload=None, feat_dim=None, rng_seed=5489,
-                 feature_dtype="float32", gat_input=None):
+                 feature_dtype="float32", gat_input=None, replace=True):
         """Part `rank` of `world`.  Ownership = the engine's workload table (`workload` int32 [N], the METIS map of
         python/utils/sampler.py:64-134 / partition_map_opt.bin; None = v % world like pyfrontend.cpp:57): the rank
         keeps the feature and label rows of the nodes it owns, in ascending node order.
@@ -54,7 +54,15 @@ class Trainer(object):
         they had (the two forms of the layer agree up to fp32 rounding only).  False: off.  True: on, for any table
         type; a ValueError names the reason where the layer cannot run (another model, more than one part or the rank
         path, a shape outside gat_input_ok, one of the A/B switches that take its prerequisites away).  `self.gat_input`
-        is the outcome."""
+        is the outcome.
+
+        replace: True (default): a row with at least `fanout` edges is sampled with replacement, the reference slicer's
+        draw (slicer.cpp:10-21).  False: such a row yields `fanout` distinct edges (_abi.FLAG_NO_REPLACE: the same
+        mt19937 words, mapped by Floyd's subset algorithm), the default of dgl.sampling.sample_neighbors that the
+        reference's Python trainers sample with; every fanout must then be <= _abi.noreplace_max_fanout()."""
+        if not replace and max(fanouts) > _abi.noreplace_max_fanout():
+            raise ValueError("replace=False: fanouts %r exceed the limit of %d neighbours per row"
+                             % (tuple(fanouts), _abi.noreplace_max_fanout()))
         if feature_dtype not in aggr.FEATURE_DTYPES:
             raise ValueError("feature_dtype must be one of %s, not %r" % (", ".join(aggr.FEATURE_DTYPES), feature_dtype))
         fdt = aggr.FEATURE_DTYPES[feature_dtype]
@@ -119,6 +127,9 @@ class Trainer(object):
                               and (fdt == torch.float32 if gat_input is None else gat_input)
                               and aggr.gat_input_ok(heads, F_in, fanouts[-1], gat_D))
             eng_flags = _abi.FLAG_TRANSPOSE | (0 if self.gat_input else _abi.FLAG_TRANSPOSE_ALL)
+        if not replace:
+            eng_flags |= _abi.FLAG_NO_REPLACE
+        self.replace = bool(replace)
         self.eng = _abi.Engine(indptr, indices, n_parts=self.P, fanouts=fanouts, max_batch=batch,
                                n_streams=streams, n_slots=self.SLOTS, device=device, mode=_abi.MODE_GRAPH,
                                workload=workload, part_mask=(1 << rank) if self.rank_path else 0,
@@ -602,6 +613,9 @@ def _parser():
                     help="(extra) --model-name gat: the deepest layer as aggregate-then-project on the raw feature rows "
                          "(`Trainer(gat_input=...)`).  auto: on for a float32 table, off for a 16-bit one; on: for any "
                          "table type, an error where the layer cannot run; off: never")
+    ap.add_argument("--no-replace", action="store_true",
+                    help="(extra) sample rows with at least fan-out edges WITHOUT replacement (`Trainer(replace=False)`), "
+                         "as dgl.sampling.sample_neighbors does by default; every fan-out must be <= 64")
     return ap
 
 
@@ -644,12 +658,19 @@ def main(argv=None):
     the rank's rows are converted on load.
     --gat-input (extra): auto (default), on or off, `Trainer(gat_input=...)`: whether the attention model's deepest layer
     aggregates the raw feature rows before it projects.  auto keeps a 16-bit table on the project-then-aggregate path.
+    --no-replace (extra): `Trainer(replace=False)`: a row with at least fan-out edges yields that many DISTINCT edges
+    (the default of dgl.sampling.sample_neighbors) instead of independent draws.  Every --fan-out number must then be
+    <= 64 (_abi.noreplace_max_fanout()).
 
         python -m cslicer.train --graph <L0 dir> --feature-dtype bfloat16 --eval-split holdout
         python -m cslicer.train --graph products-like --model-name gat --feature-dtype bfloat16 --gat-input on"""
     import os
     a = _parser().parse_args(argv)
     from . import l0
+    if a.no_replace:     # (before the graph is loaded)
+        lim = _abi.noreplace_max_fanout()
+        if any(int(x) > lim for x in a.fan_out.split(",")):
+            raise SystemExit("--no-replace: --fan-out %s exceeds the limit of %d neighbours per row" % (a.fan_out, lim))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -694,7 +715,7 @@ def main(argv=None):
     tr = Trainer(indptr, indices, feats, labels, n_classes, rank=rank, world=world, fanouts=fan, batch=a.batch_size,
                  streams=8, hidden=max(4, hidden // 4 * 4), lr=a.lr, device=local, dist=dist, model=kind, heads=a.num_heads,
                  workload=workload, feat_dim=fdim, feature_dtype=fdtype,
-                 gat_input={"auto": None, "on": True, "off": False}[a.gat_input])
+                 gat_input={"auto": None, "on": True, "off": False}[a.gat_input], replace=not a.no_replace)
     if rank == 0 and fdtype != "float32":
         print("feature table: %s, %d bytes on this rank" % (fdtype, tr.feat.numel() * tr.feat.element_size()))
     n = indptr.shape[0] - 1

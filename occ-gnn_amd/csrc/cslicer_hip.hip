@@ -173,6 +173,8 @@ struct LArgs {
 };
 
 constexpr uint32_t SELF_BIT = 0x80000000u;
+// CSL_FLAG_NO_REPLACE: largest fanout (floyd_pick walks O(fanout^2) words per slot at worst; 64 is one wave)
+constexpr int kNoReplaceMaxFanout = 64;
 
 // v % P for the runtime constant P (pyfrontend.cpp:57 workload_map[j] = j % 4) without the ~25-instruction
 // software division: q = floor(v * floor(2^32 / P) / 2^32) is the quotient or one short of it.
@@ -545,222 +547,49 @@ __device__ __forceinline__ uint32_t mt_temper(uint32_t y) {
 // node's part mask, counts the per-node list memberships and the size of each
 // dedup bucket.  A block walks TPB consecutive tiles so its bucket histogram
 // (LDS) is flushed once per 1024 nodes.
+//
+// k_sample_norep (CSL_FLAG_NO_REPLACE) is the same body with NOREP set (k_sample_body.inc): the row's fanout draws
+// r_0..r_{f-1} sit at the same ring
+// positions, only the map from draws to edge positions is Floyd's subset algorithm (floyd_pick below) instead of
+// r_j % deg.  k_sample holds no trace of it.
+//
+// pick_j of a row with D = deg - fanout:  t_j = r_j % (D + j + 1),  pick_j = t_j unless t_j is among pick_0..pick_{j-1},
+// then D + j.  The slot's thread needs no list of the earlier picks: x is among pick_0..pick_{m-1} iff some t_i == x
+// (i < m) -- then pick_i == x, or t_i was taken already -- or x == D + i for an i < m whose t_i was itself taken at step
+// i, which is the same question for (t_i, i).  The index falls with every such step, so the walk ends; it reads the
+// row's consecutive ring words again (the same lines its neighbour slots read) and keeps nothing in LDS or in scratch.
+// Cost: j remainders in the common case, O(f^2) at worst -- hence csl_noreplace_max_fanout().
+// A word outside the generated window reads as 0 and raises CSL_ERR_RNG_WINDOW, as the word's own slot does.
+__device__ __forceinline__ uint32_t ring_word(const LArgs& a, uint32_t s, unsigned long long pos) {
+  if (pos >= a.gen_lo && pos < a.gen_hi) return a.ring[pos & a.ring_mask];
+  atomicOr(&a.meta[s].error, (uint32_t)CSL_ERR_RNG_WINDOW);
+  return 0;
+}
+__device__ __forceinline__ uint32_t floyd_pick(const LArgs& a, uint32_t s, unsigned long long row_pos, uint32_t j,
+                                               uint32_t D, uint32_t rj) {
+  uint32_t x = rj % (D + j + 1u);
+  const uint32_t own = x;
+  uint32_t m = j;
+  bool taken = false;
+  for (;;) {
+    for (uint32_t i = 0; i < m; i++) {
+      if (ring_word(a, s, row_pos + i) % (D + i + 1u) == x) taken = true;
+    }
+    if (taken || x < D || x - D >= m) break;
+    // x == D + i for an earlier step i whose own t_i differs from x: taken iff step i fell back to D + i
+    m = x - D;
+    x = ring_word(a, s, row_pos + m) % (D + m + 1u);
+  }
+  return taken ? D + j : own;
+}
+
 __global__ CSL_LB256 void k_sample(LArgs a) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t s_bh[];  // [nb] bucket histogram
-  uint32_t bx, s;
-  if (!xcd_block(a, bx, s)) return;
-  const uint32_t F = a.fsize[s * (CSL_MAX_LAYERS + 1) + a.layer];
-  if (bx * a.tpb * TN >= F) return;
-  __shared__ uint32_t s_v[TN];
-  __shared__ unsigned long long s_ri[TN];
-  __shared__ uint32_t s_rng[TN];
-  __shared__ uint32_t s_hb[TN];
-  __shared__ uint8_t s_to[TN];  // owner part of the tile's nodes
-  __shared__ uint32_t s_wn[NW];
-  __shared__ uint32_t s_cnt[5 * CSL_MAX_PARTS];
-  __shared__ uint32_t s_ec[TN * CSL_MAX_PARTS];                                 // graph: edges per (node, source part)
-  __shared__ uint32_t s_gcnt[CSL_MAX_PARTS + CSL_MAX_PARTS * CSL_MAX_PARTS];    // graph: ECNT[g], PAIR[g][p]
-  const uint32_t n = threadIdx.x;
-  const uint32_t f = a.fanout, W = a.W;
-  const uint32_t P = a.P;
-  const uint32_t nb = a.nbk[s];
-  for (uint32_t b = n; b < nb; b += TN) s_bh[b] = 0;
-  const unsigned long long rbase = a.rngbase[s];
-  for (uint32_t sub = 0; sub < a.tpb; sub++) {
-    const uint32_t tile = bx * a.tpb + sub;
-    if (tile * TN >= F) break;
-    const uint32_t i = tile * TN + n;
-    // phase 1: stage the tile's nodes, rank the rng consumers
-    uint32_t v = 0, need = 0;
-    unsigned long long ri = 0;
-    if (i < F) {
-      v = a.fr_in[s * a.fr_in_stride + i];
-      ri = a.ninfo[s * a.fcap + i];
-      need = (uint32_t)(ri & DEG_MASK) >= f;
-    }
-    const unsigned long long bm = __ballot(need);
-    __syncthreads();  // previous sub-tile done with the LDS arrays
-    if (lane_id() == 0) s_wn[n >> 6] = __popcll(bm);
-    if (n < 5 * CSL_MAX_PARTS) s_cnt[n] = 0;
-    s_v[n] = v;
-    s_ri[n] = ri;
-    s_hb[n] = 0;
-    s_to[n] = i < F ? (uint8_t)owner(a, v) : 0;
-    if (a.graph) {
-      for (uint32_t k = n; k < TN * P; k += TN) s_ec[k] = 0;
-      if (n < CSL_MAX_PARTS + CSL_MAX_PARTS * CSL_MAX_PARTS) s_gcnt[n] = 0;
-    }
-    __syncthreads();
-    {
-      uint32_t r = __popcll(bm & lt_mask());
-      for (uint32_t w = 0; w < (n >> 6); w++) r += s_wn[w];
-      const uint32_t tb = a.tcnt[((size_t)s * a.nk + K_NEED) * a.tmax + tile];
-      s_rng[n] = need ? (tb + r) * f : UNSET;
-    }
-    __syncthreads();
-    // phase 2: candidates, coalesced over c.  Each thread keeps SU candidates in
-    // flight: all their rng words are requested, then all their neighbour ids,
-    // before any is consumed (the loads are dependent pairs of HBM round trips).
-    const uint32_t nodes_here = (F - tile * TN) < (uint32_t)TN ? (F - tile * TN) : (uint32_t)TN;
-    const uint32_t ncand = nodes_here * W;
-    const size_t cbase = (size_t)s * a.ccap + (size_t)tile * TN * W;
-    constexpr int SU = CSL_SU;
-    const uint32_t dq = TN / W, dr = TN - dq * W;  // k += TN  =>  node += dq, slot += dr (+carry)
-    uint32_t nn = n / W, slot = n - nn * W;
-    for (uint32_t k0 = n; k0 < ncand; k0 += TN * SU) {
-      uint32_t nnu[SU], slu[SU], vvu[SU], degu[SU], val[SU], rnd[SU];
-      unsigned long long addr[SU], rpos[SU];
-      bool live[SU], gat[SU], rq[SU];
-#pragma unroll
-      for (int u = 0; u < SU; u++) {
-        live[u] = k0 + u * TN < ncand;
-        nnu[u] = nn;
-        slu[u] = slot;
-        nn += dq;
-        slot += dr;
-        if (slot >= W) {
-          slot -= W;
-          nn++;
-        }
-        val[u] = UNSET;
-        gat[u] = false;
-        rq[u] = false;
-        addr[u] = 0;
-        rpos[u] = 0;
-        vvu[u] = 0;
-        degu[u] = 1;
-        rnd[u] = 0;
-        if (live[u]) {
-          vvu[u] = s_v[nnu[u]];
-          if (slu[u] == 0) {
-            val[u] = vvu[u];
-          } else {
-            const unsigned long long r2 = s_ri[nnu[u]];
-            const uint32_t deg = (uint32_t)(r2 & DEG_MASK);
-            const uint32_t j = slu[u] - 1;
-            degu[u] = deg;
-            addr[u] = r2 >> DEG_BITS;
-            if (deg < f) {
-              gat[u] = j < deg;
-              addr[u] += j;
-            } else {
-              gat[u] = true;
-              rq[u] = true;
-              rpos[u] = rbase + s_rng[nnu[u]] + j;
-            }
-          }
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < SU; u++) {
-        if (rq[u]) {
-          if (rpos[u] >= a.gen_lo && rpos[u] < a.gen_hi) {
-            rnd[u] = a.ring[rpos[u] & a.ring_mask];
-          } else {
-            atomicOr(&a.meta[s].error, (uint32_t)CSL_ERR_RNG_WINDOW);
-          }
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < SU; u++) {
-        // (non-temporal loads here were measured 5 % slower: picks of one row share lines)
-        if (gat[u]) val[u] = a.indices[addr[u] + (rq[u] ? rnd[u] % degu[u] : 0u)];
-      }
-#pragma unroll
-      for (int u = 0; u < SU; u++) {
-        if (live[u]) {
-          // The flag byte every candidate gets here is what k_bucket would find in the common case: a self entry
-          // new to the frontier, an edge candidate the first occurrence of its node (in the frontier and among its
-          // slice's in-nodes) and not a frontier node itself.  k_bucket then only stores the exceptions (a fifth of
-          // the entries) instead of one scattered byte per first occurrence (most entries): its evaluate phase was
-          // bound by exactly those stores.  bit0 new-frontier, bit1 first-in-node, bits 2-4 owner part.
-          uint32_t fl = 0;
-          if (slu[u] == 0) {
-            atomicAdd(&s_bh[bucket_of(val[u], nb)], 1u);
-            fl = (a.graph ? 3u : 1u) | ((uint32_t)s_to[nnu[u]] << 2);
-          } else if (val[u] != UNSET) {
-            if (val[u] == vvu[u]) {
-              // a sampled self loop only re-adds the self edge (slicer.cpp:33-35,
-              // bipartite.h:34): it is neither an edge nor new to the frontier
-              if (a.candk) a.candk[cbase + k0 + u * TN] = val[u];  // (the raw stream keeps it)
-              val[u] = UNSET;
-            } else {
-              const uint32_t og = owner(a, val[u]);
-              atomicOr(&s_hb[nnu[u]], 1u << og);
-              if (a.graph) atomicAdd(&s_ec[nnu[u] * P + og], 1u);
-              atomicAdd(&s_bh[bucket_of(val[u], nb)], 1u);
-              fl = 3u | (og << 2);
-              // graph mode: an edge's source position is its own position unless k_bucket finds an earlier one
-              if (a.graph) a.srcpos[cbase + k0 + u * TN] = tile * TN * W + k0 + u * TN;
-            }
-          }
-          a.cand[cbase + k0 + u * TN] = val[u];
-          a.cflag[cbase + k0 + u * TN] = (uint8_t)fl;  // k_bucket corrects the exceptions
-          if (a.candk && (val[u] != UNSET || slu[u] == 0 || !gat[u])) a.candk[cbase + k0 + u * TN] = val[u];
-        }
-      }
-    }
-    __syncthreads();
-    // phase 3: per-node list memberships (bipartite.h:33-66 push conditions)
-    uint32_t hb = 0, to = 0;
-    const bool act = i < F;
-    if (act) {
-      hb = s_hb[n];
-      to = s_to[n];
-      if (!a.graph) a.firstpos[s * a.fcap + i] = UNSET;  // k_bucket stores it for nodes that are sampled as a neighbour too
-      // graph mode: a node is always an out node of its own slice
-      if (a.graph) hb |= 1u << to;
-      a.hasedge[s * a.fcap + i] = hb;
-    }
-    if (a.graph) {
-      for (uint32_t g = 0; g < P; g++) {
-        const uint32_t ec = act ? s_ec[n * P + g] : 0u;  // <= fanout <= 255
-        if (act) a.ecnt[(s * a.fcap + i) * P + g] = (uint8_t)ec;
-        uint32_t x = ec;
-        for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o);
-        if (lane_id() == 0 && x) atomicAdd(&s_gcnt[g], x);
-        const bool hasg = act && ((hb >> g) & 1u) && to != g;
-        for (uint32_t p = 0; p < P; p++) {
-          const uint32_t c_pair = __popcll(__ballot(hasg && to == p));
-          if (lane_id() == 0 && c_pair) atomicAdd(&s_gcnt[CSL_MAX_PARTS + g * CSL_MAX_PARTS + p], c_pair);
-        }
-      }
-    }
-    for (uint32_t g = 0; g < P; g++) {
-      const bool own = act && to == g;
-      const bool has = act && ((hb >> g) & 1u);
-      const uint32_t c_out = __popcll(__ballot(has));
-      const uint32_t c_owned = __popcll(__ballot(own && has));
-      const uint32_t c_self = __popcll(__ballot(own));
-      const uint32_t c_to = __popcll(__ballot(own && (hb & ~(1u << g)) != 0));
-      const uint32_t c_from = __popcll(__ballot(has && !own));
-      if (lane_id() == 0) {
-        if (c_out) atomicAdd(&s_cnt[0 * CSL_MAX_PARTS + g], c_out);
-        if (c_owned) atomicAdd(&s_cnt[1 * CSL_MAX_PARTS + g], c_owned);
-        if (c_self) atomicAdd(&s_cnt[2 * CSL_MAX_PARTS + g], c_self);
-        if (c_to) atomicAdd(&s_cnt[3 * CSL_MAX_PARTS + g], c_to);
-        if (c_from) atomicAdd(&s_cnt[4 * CSL_MAX_PARTS + g], c_from);
-      }
-    }
-    __syncthreads();
-    if (n < 5 * P) {
-      const uint32_t kind5 = n / P, g = n - kind5 * P;
-      a.tcnt[((size_t)s * a.nk + (K_OUT(P, 0) + kind5 * P + g)) * a.tmax + tile] = s_cnt[kind5 * CSL_MAX_PARTS + g];
-    }
-    if (a.graph) {
-      if (n < P) a.tcnt[((size_t)s * a.nk + K_ECNT(P, n)) * a.tmax + tile] = s_gcnt[n];
-      if (n < P * P) {
-        const uint32_t g = n / P, p = n - g * P;
-        a.tcnt[((size_t)s * a.nk + K_PAIR(P, g, p)) * a.tmax + tile] = s_gcnt[CSL_MAX_PARTS + g * CSL_MAX_PARTS + p];
-      }
-    }
-  }
-  __syncthreads();
-  uint32_t* gcnt = a.bcnt + (size_t)s * (a.nbmax + 1);
-  for (uint32_t b = n; b < nb; b += TN) {
-    const uint32_t c = s_bh[b];
-    if (c) atomicAdd(&gcnt[b], c);
-  }
+  constexpr bool NOREP = false;
+#include "k_sample_body.inc"
+}
+__global__ CSL_LB256 void k_sample_norep(LArgs a) {
+  constexpr bool NOREP = true;
+#include "k_sample_body.inc"
 }
 
 // ---- k_scatter: partitions the candidate stream into the dedup buckets.
@@ -2493,7 +2322,10 @@ int run_round(csl_engine* e, const long long* nodes_dev, int32_t n_batches, int3
       // CSL_SAMPLE_LDS_PAD=<bytes>: measurement knob (profiles/r3_sample_occupancy): what k_sample costs at the occupancy
       // an LDS-staged counting sort inside it (k_scatter folded in: 32 KB per workgroup) would leave it
       static const size_t lds_pad = getenv("CSL_SAMPLE_LDS_PAD") ? (size_t)atol(getenv("CSL_SAMPLE_LDS_PAD")) : 0;
-      hipLaunchKernelGGL(k_sample, grid_sample, blk, lds_hist + lds_pad, st, a);
+      if (e->cfg.flags & CSL_FLAG_NO_REPLACE)
+        hipLaunchKernelGGL(k_sample_norep, grid_sample, blk, lds_hist + lds_pad, st, a);
+      else
+        hipLaunchKernelGGL(k_sample, grid_sample, blk, lds_hist + lds_pad, st, a);
     }
     if (l == L - 1) {
       // Snapshot of the streams' positions AFTER this round (tightens the host's bounds without a sync).
@@ -2576,6 +2408,7 @@ extern "C" {
 
 const char* csl_last_error(void) { return g_err; }
 int csl_abi_version(void) { return CSL_ABI_VERSION; }
+int csl_noreplace_max_fanout(void) { return kNoReplaceMaxFanout; }
 const char* csl_kernel_name(int32_t k) { return (k >= 0 && k < CSL_NUM_KERNELS) ? kKernelNames[k] : ""; }
 
 int csl_debug_wave_duplicates(uint64_t* out3) {
@@ -2841,6 +2674,13 @@ int csl_create(const csl_config* cfg, csl_engine** out) {
     return fail(CSL_E_INVALID, "CSL_FLAG_TRANSPOSE needs CSL_MODE_GRAPH (strict mode has no edges to transpose)");
   if ((cfg->flags & CSL_FLAG_TRANSPOSE_ALL) && !(cfg->flags & CSL_FLAG_TRANSPOSE))
     return fail(CSL_E_INVALID, "CSL_FLAG_TRANSPOSE_ALL only widens CSL_FLAG_TRANSPOSE");
+  if ((cfg->flags & CSL_FLAG_NO_REPLACE) && cfg->mode != CSL_MODE_GRAPH)
+    return fail(CSL_E_INVALID, "CSL_FLAG_NO_REPLACE needs CSL_MODE_GRAPH (strict mode is the reference's sampling, with replacement)");
+  if (cfg->flags & CSL_FLAG_NO_REPLACE)
+    for (int l = 0; l < cfg->n_layers; l++)
+      if (cfg->fanout[l] > kNoReplaceMaxFanout)
+        return fail(CSL_E_INVALID, "fanout[%d]=%d: CSL_FLAG_NO_REPLACE samples at most %d neighbours per row", l, cfg->fanout[l],
+                    kNoReplaceMaxFanout);
   if (cfg->part_mask >> cfg->n_parts) return fail(CSL_E_INVALID, "part_mask 0x%x names parts beyond n_parts", cfg->part_mask);
   if (!cfg->indptr || (!cfg->indices && cfg->num_edges > 0)) return fail(CSL_E_INVALID, "graph arrays missing");
   // the reference keeps ids in `int` (bipartite.h:55): node ids are only defined below 2^31.  Row offsets:
