@@ -13,6 +13,7 @@ The print keys of train.py:101-103 are kept (`avg forward time`, `batch slice ti
 `cache refresh time`; there is no feature cache here: features are resident in HBM, so the last
 one is reported as 0).
 """
+import collections
 import os
 import time
 
@@ -20,6 +21,98 @@ import numpy as np
 import torch
 
 from . import _abi, _roctx, aggr, shard, splitgnn
+
+
+# The A/B switches a trainer is built under.  They are read when the constructor runs (read_switches), never at import:
+# the tests set them per trainer.
+Switches = collections.namedtuple("Switches", "no_transpose py_step no_local_fuse no_gat_input",
+                                  defaults=(False, False, False, False))
+
+# How a trainer trains a minibatch and what it asks of its engine (step_plan):
+#   engine_flags  the _abi.FLAG_* of the engine
+#   path          "native" (aggr.SageStep), "native_rank" (aggr.SageRankStep), "local" (autograd, model.forward_local on
+#                 the single part) or "parts" (autograd, model.forward_parts / forward_rank on a gathered input)
+#   gat_input     whether the attention model's deepest layer is aggr.GatInputLayer
+#   input_form    the "parts" path's input matrix: "table" (aggr.FeatureRows: the table read in place), "padded"
+#                 (aggr.padded_rows and a gather into it) or "rows" (aggr.gather_rows); None on the other paths
+StepPlan = collections.namedtuple("StepPlan", "engine_flags path gat_input input_form")
+
+
+def read_switches():
+    return Switches(no_transpose=bool(os.environ.get("CSLICER_NO_TRANSPOSE")), py_step=bool(os.environ.get("CSLICER_PY_STEP")),
+                    no_local_fuse=bool(splitgnn._NO_LOCAL_FUSE), no_gat_input=bool(splitgnn._NO_GAT_INPUT))
+
+
+def gat_input_obstacle(kind, world, rank_path, n_layers, F, hidden, n_classes, heads, fanout, sw):
+    """Why the attention model's deepest layer cannot run aggregate-then-project on the raw feature rows
+    (aggr.GatInputLayer), or None where it can.  F: the feature width as known BEFORE the rank's rows are loaded (None:
+    callable features without feat_dim); fanout: the deepest layer's.  The one statement of the layer's prerequisites:
+    the constructor's gat_input=True refusal raises the text, step_plan turns the layer on where there is none."""
+    D = hidden if n_layers > 1 else (n_classes + 3) // 4 * 4
+    if kind != "gat":
+        return "model is %r, the input layer belongs to model='gat'" % (kind,)
+    if world > 1 or rank_path:
+        return "more than one part or rank_path: the rank path's attention layer has no aggregate-then-project form"
+    if F is None:
+        return "the feature width is unknown (pass feat_dim with callable features)"
+    if not aggr.gat_input_ok(heads, F, fanout, D):
+        return ("aggr.gat_input_ok(heads=%d, F=%d, fanout=%d, D=%d) is false: heads in (1, 2, 4, 8), F %% 4 == 0, "
+                "4 <= F <= 128, heads * D <= %d, fanout <= %d" % (heads, F, fanout, D, aggr.GAT_IN_MAX_WIDTH,
+                                                                  aggr.gat_in_max_degree()))
+    if sw.no_transpose:
+        return "CSLICER_NO_TRANSPOSE is set: the upper layers' slices by source are off"
+    if sw.no_local_fuse:
+        return "CSLICER_NO_LOCAL_FUSE is set: the fused single-part layers are off"
+    if sw.no_gat_input:
+        return "CSLICER_GAT_NO_INPUT_LAYER is set: the input layer is switched off"
+    return None
+
+
+def step_plan(kind, world, rank_path, n_layers, F, hidden, n_classes, heads, fanout, table_f32, gat_input, replace,
+              sw=Switches(), width_known=True):
+    """The StepPlan of a configuration, from plain values only (no device, no engine): every rule is written here once.
+    ONE function, called when the rank's host rows are in hand -- F is the loaded table's width (feat_dim where given),
+    which the path depends on -- so the constructor creates its engine after the host-side loading.
+    rank_path: as resolved (None -> world > 1); fanout: the deepest layer's; table_f32: whether the feature table is
+    float32; gat_input: the constructor's None / True / False; width_known: whether F was known before the rows were
+    loaded (feat_dim, or the shape of a feature matrix; False: callable features without feat_dim)."""
+    sage, gat = kind == "sage", kind == "gat"
+    single = not rank_path and world == 1      # one part in one process, no collective
+    want = table_f32 if gat_input is None else gat_input     # (None: a 16-bit table keeps the numbers its runs have had)
+    gat_in = bool(want) and gat_input_obstacle(kind, world, rank_path, n_layers, F if width_known else None, hidden,
+                                               n_classes, heads, fanout, sw) is None
+    # GraphSAGE's backward gathers its input gradients over the upper layers' slices by source (CSLICER_NO_TRANSPOSE:
+    # atomic scatter instead)
+    by_source = sage and n_layers > 1 and not sw.no_transpose
+    # the single part with every layer as one fused node, the deepest reading the resident table through in_nodes
+    local = single and sage and F % 4 == 0 and not sw.no_local_fuse
+
+    flags = 0
+    if by_source and (single or (rank_path and not sw.py_step)):
+        # Neither the widths nor n_classes are looked at: a rank-path model with more than 256 classes, whose autograd
+        # step never reads them, still gets the slices by source.  Kept as it is (behaviour, not a rule of this table).
+        flags = _abi.FLAG_TRANSPOSE
+    elif gat and single and not sw.no_transpose:
+        # GAT aggregates PROJECTED features: every layer's sources take a gradient -- the deepest layer's too, unless it
+        # is the input layer (no source gradient at all)
+        flags = _abi.FLAG_TRANSPOSE | (0 if gat_in else _abi.FLAG_TRANSPOSE_ALL)
+    if not replace:
+        flags |= _abi.FLAG_NO_REPLACE
+
+    if rank_path and sage and F % 4 == 0 and hidden % 4 == 0 and n_classes <= 256 and not sw.py_step:
+        path = "native_rank"
+    elif local and by_source and hidden % 4 == 0 and not sw.py_step:
+        path = "native"
+    elif local:
+        path = "local"
+    else:
+        path = "parts"
+
+    form = None
+    if path == "parts":
+        # "padded": straight into the row-padded buffer the fused GAT layer multiplies (no second copy of 0.3 GB)
+        form = "table" if gat_in else "padded" if gat and single and not sw.no_local_fuse else "rows"
+    return StepPlan(flags, path, gat_in, form)
 
 
 class Trainer(object):
@@ -59,7 +152,11 @@ class Trainer(object):
         replace: True (default): a row with at least `fanout` edges is sampled with replacement, the reference slicer's
         draw (slicer.cpp:10-21).  False: such a row yields `fanout` distinct edges (_abi.FLAG_NO_REPLACE: the same
         mt19937 words, mapped by Floyd's subset algorithm), the default of dgl.sampling.sample_neighbors that the
-        reference's Python trainers sample with; every fanout must then be <= _abi.noreplace_max_fanout()."""
+        reference's Python trainers sample with; every fanout must then be <= _abi.noreplace_max_fanout().
+
+        `self.plan` is the StepPlan of the configuration (step_plan above): which step the trainer runs, decided here
+        once; `self.native` / `self.native_rank` are the native stepper of that path, None on every other path."""
+        # -- 1. the arguments (before any device call: a request that cannot be served is an error, never a quiet fall-back)
         if not replace and max(fanouts) > _abi.noreplace_max_fanout():
             raise ValueError("replace=False: fanouts %r exceed the limit of %d neighbours per row"
                              % (tuple(fanouts), _abi.noreplace_max_fanout()))
@@ -68,30 +165,16 @@ class Trainer(object):
         fdt = aggr.FEATURE_DTYPES[feature_dtype]
         if not any(gat_input is v for v in (None, True, False)):
             raise ValueError("gat_input must be None, True or False, not %r" % (gat_input,))
-        import os
-        F_in = None
+        # rank_path=True forces the one-process-per-part code (collectives included) even for a single part:
+        # a way to run the RCCL calls on a one-GPU box
+        self.rank_path = (world > 1) if rank_path is None else bool(rank_path)
+        sw = read_switches()
+        F_early = None
         if model == "gat":   # (the attention model's input width, known before the rows are loaded)
-            F_in = features.shape[1] if feat_dim is None and not callable(features) else feat_dim
-        gat_D = hidden if len(fanouts) > 1 else (n_classes + 3) // 4 * 4
+            F_early = features.shape[1] if feat_dim is None and not callable(features) else feat_dim
         if gat_input is True:
-            # (before any device call: a request the layer cannot serve is an error, never a quiet fall-back)
-            why = None
-            if model != "gat":
-                why = "model is %r, the input layer belongs to model='gat'" % (model,)
-            elif world > 1 or rank_path:
-                why = "more than one part or rank_path: the rank path's attention layer has no aggregate-then-project form"
-            elif F_in is None:
-                why = "the feature width is unknown (pass feat_dim with callable features)"
-            elif not aggr.gat_input_ok(heads, F_in, fanouts[-1], gat_D):
-                why = ("aggr.gat_input_ok(heads=%d, F=%d, fanout=%d, D=%d) is false: heads in (1, 2, 4, 8), F %% 4 == 0, "
-                       "4 <= F <= 128, heads * D <= %d, fanout <= %d" % (heads, F_in, fanouts[-1], gat_D, aggr.GAT_IN_MAX_WIDTH,
-                                                                         aggr.gat_in_max_degree()))
-            elif os.environ.get("CSLICER_NO_TRANSPOSE"):
-                why = "CSLICER_NO_TRANSPOSE is set: the upper layers' slices by source are off"
-            elif splitgnn._NO_LOCAL_FUSE:
-                why = "CSLICER_NO_LOCAL_FUSE is set: the fused single-part layers are off"
-            elif splitgnn._NO_GAT_INPUT:
-                why = "CSLICER_GAT_NO_INPUT_LAYER is set: the input layer is switched off"
+            why = gat_input_obstacle(model, world, self.rank_path, len(fanouts), F_early, hidden, n_classes, heads,
+                                     fanouts[-1], sw)
             if why is not None:
                 raise ValueError("gat_input=True: " + why)
         self.rank, self.world, self.dist = rank, world, dist
@@ -100,40 +183,11 @@ class Trainer(object):
         torch.cuda.set_device(self.dev)
         N = indptr.shape[0] - 1
         self.N, self.B, self.S, self.L = N, batch, streams, len(fanouts)
-        # rank_path=True forces the one-process-per-part code (collectives included) even for a single part:
-        # a way to run the RCCL calls on a one-GPU box
-        self.rank_path = (world > 1) if rank_path is None else bool(rank_path)
         if workload is not None:
             workload = np.ascontiguousarray(workload, dtype=np.int32)
             if workload.shape != (N,) or workload.min() < 0 or workload.max() >= world:
                 raise ValueError("workload must be int32 [num_nodes] with values in [0, world)")
-        # one process per part: only this rank's slices are materialised (the sampling itself is replicated).
-        # One GPU holding every node (the fused GraphSAGE path): the engine also emits the slices by source, over
-        # which the backward gathers its input gradients (CSLICER_NO_TRANSPOSE=1: atomic scatter instead, A/B switch).
-        by_source = (not self.rank_path and self.P == 1 and model == "sage" and len(fanouts) > 1
-                     and not os.environ.get("CSLICER_NO_TRANSPOSE"))
-        eng_flags = _abi.FLAG_TRANSPOSE if by_source else 0
-        # one process per part, GraphSAGE, native rank step: the part's slices by source too (the backward gathers its input
-        # gradients over them instead of scattering them with atomics; CSLICER_NO_TRANSPOSE=1: A/B switch)
-        if (self.rank_path and model == "sage" and len(fanouts) > 1 and not os.environ.get("CSLICER_NO_TRANSPOSE")
-                and not os.environ.get("CSLICER_PY_STEP")):
-            eng_flags = _abi.FLAG_TRANSPOSE
-        if (not self.rank_path and self.P == 1 and model == "gat" and not os.environ.get("CSLICER_NO_TRANSPOSE")):
-            # GAT aggregates PROJECTED features: every layer's sources take a gradient -- the deepest layer's too, unless
-            # it runs aggregate-then-project on the raw feature rows (aggr.GatInputLayer: no source gradient at all)
-            # (gat_input=None: a 16-bit table keeps the project-then-aggregate path its runs have had; True asks for the
-            # input layer, which reads the table in either form)
-            self.gat_input = (not splitgnn._NO_GAT_INPUT and not splitgnn._NO_LOCAL_FUSE and F_in is not None
-                              and (fdt == torch.float32 if gat_input is None else gat_input)
-                              and aggr.gat_input_ok(heads, F_in, fanouts[-1], gat_D))
-            eng_flags = _abi.FLAG_TRANSPOSE | (0 if self.gat_input else _abi.FLAG_TRANSPOSE_ALL)
-        if not replace:
-            eng_flags |= _abi.FLAG_NO_REPLACE
-        self.replace = bool(replace)
-        self.eng = _abi.Engine(indptr, indices, n_parts=self.P, fanouts=fanouts, max_batch=batch,
-                               n_streams=streams, n_slots=self.SLOTS, device=device, mode=_abi.MODE_GRAPH,
-                               workload=workload, part_mask=(1 << rank) if self.rank_path else 0,
-                               flags=eng_flags, rng_seed=rng_seed)
+        # -- 2. the rank's nodes and their rows, on the host
         if workload is None:
             own = np.arange(rank, N, self.P, dtype=np.int64)           # owner v % P holds v at local row v // P
         else:
@@ -157,6 +211,16 @@ class Trainer(object):
         if f_own.shape[0] != self.n_own or l_own.shape[0] != self.n_own:
             raise ValueError("features / labels do not cover the rank's %d nodes" % self.n_own)
         F = f_own.shape[1] if feat_dim is None else feat_dim
+        # -- 3. how this configuration trains, 4. the engine it needs.  One process per part: only this rank's slices are
+        # materialised (the sampling itself is replicated)
+        self.plan = step_plan(model, world, self.rank_path, self.L, F, hidden, n_classes, heads, fanouts[-1],
+                              fdt == torch.float32, gat_input, replace, sw, width_known=F_early is not None)
+        self.gat_input, self.replace = self.plan.gat_input, bool(replace)
+        self.eng = _abi.Engine(indptr, indices, n_parts=self.P, fanouts=fanouts, max_batch=batch,
+                               n_streams=streams, n_slots=self.SLOTS, device=device, mode=_abi.MODE_GRAPH,
+                               workload=workload, part_mask=(1 << rank) if self.rank_path else 0,
+                               flags=self.plan.engine_flags, rng_seed=rng_seed)
+        # -- 5. the resident table and the model
         # whether self.feat is a view of rows stored zero-padded to a multiple of 4 (what lets inference read it in place)
         self._feat_padded = bool(fdt != torch.float32 and f_own.shape[1] % 4)
         if self._feat_padded:
@@ -184,29 +248,31 @@ class Trainer(object):
             self.model = splitgnn.DistGATModel(F, hidden, n_classes, heads=heads, n_layers=self.L).to(self.dev)
         else:
             raise ValueError("model must be 'sage' or 'gat'")
-        # torch.optim.Adam's update in one HIP launch per step (the library's for-each form is eight small
+        # -- 6. torch.optim.Adam's update in one HIP launch per step (the library's for-each form is eight small
         # launches, ~0.1 ms of GPU time per step; its fused form one of 42 us for these six small tensors)
         self.opt = aggr.Adam(list(self.model.parameters()), lr=lr)
-        # the fused single-GPU GraphSAGE step as one native call per minibatch (CSLICER_PY_STEP=1: the same kernels
-        # issued from Python through an autograd node, A/B switch and what the tests compare it with)
-        self.native, self.grad_sync = None, None
+        # data-parallel replicas: called with the flat gradient, sums it over the ranks' shares of the minibatch
+        self.grad_sync = None
         # rank path, autograd step: called with the flat gradient right after its all-reduce (what the optimizer applies)
         self.on_reduced_grads = None
-        if (by_source and F % 4 == 0 and hidden % 4 == 0 and not os.environ.get("CSLICER_PY_STEP")
-                and not splitgnn._NO_LOCAL_FUSE):
-            self.native = aggr.SageStep(self.model, splitgnn.ROW_PAD, splitgnn.SPLIT_K)
-            self._loss_ring, self._ring_at = torch.zeros((4096,), dtype=torch.float32, device=self.dev), 0
         self.comm = splitgnn.DistComm(device=self.dev) if self.rank_path else None
         self.overlap = overlap
-        # one process per part: the same idea -- everything between two boundary exchanges is issued by one native call,
-        # the exchanges come back as callbacks into self.comm, on its side stream with overlap=True (CSLICER_PY_STEP=1: the
-        # autograd path)
-        self.native_rank = None
-        if (self.rank_path and model == "sage" and F % 4 == 0 and hidden % 4 == 0 and n_classes <= 256
-                and not os.environ.get("CSLICER_PY_STEP")):
+        # -- 7. the native stepper the plan names.  "native": the fused single-GPU GraphSAGE step as one native call per
+        # minibatch.  "native_rank": the same idea with one process per part -- everything between two boundary exchanges
+        # is issued by one native call, the exchanges come back as callbacks into self.comm, on its side stream with
+        # overlap=True.  (CSLICER_PY_STEP=1: the same kernels issued from Python through autograd nodes, A/B switch and
+        # what the tests compare the native steps with)
+        self.native = self.native_rank = None
+        if self.plan.path == "native":
+            self.native = aggr.SageStep(self.model, splitgnn.ROW_PAD, splitgnn.SPLIT_K)
+        elif self.plan.path == "native_rank":
             self.native_rank = aggr.SageRankStep(self.model, splitgnn.ROW_PAD, splitgnn.SPLIT_K, self.comm,
                                                  overlap=overlap)
-            self._loss_ring, self._ring_at = torch.zeros((4096,), dtype=torch.float32, device=self.dev), 0
+        self._path_step = getattr(self, "_step_" + self.plan.path)
+        # -- 8. the native steps write each loss into the next element of a ring (run() sizes it for its steps)
+        self._loss_ring, self._ring_at = None, 0
+        if self.native is not None or self.native_rank is not None:
+            self._loss_ring = torch.zeros((4096,), dtype=torch.float32, device=self.dev)
         self.t_forward = self.t_slice = 0.0
         self.steps_done = 0
         self._round_base, self._slot_done, self._ahead = 0, [None] * self.SLOTS, None
@@ -225,115 +291,119 @@ class Trainer(object):
         slices = splitgnn.slices_of(self.eng, stream, slot, parts=[self.rank], device=self.dev, meta=meta)
         _roctx.pop()
         self.t_slice += time.perf_counter() - t0
-        deep = slices[self.L - 1][self.rank]
-        top = slices[0][self.rank]
-        for k in range(self.L):
-            sl = slices[self.L - 1 - k][self.rank]
-            u = self.units[k]
+        layers = [slices[self.L - 1 - k][self.rank] for k in range(self.L)]    # the rank's slices in MODEL order
+        for u, sl in zip(self.units, layers):
             u["rows"] += sl.n_owned
             u["src"] += sl.n_in
             u["edges"] += sl.n_edges
-        n_seeds = int(meta.n_seeds)
-        fused = (not self.rank_path and self.kind == "sage" and self.P == 1 and self.feat.shape[1] % 4 == 0
-                 and not splitgnn._NO_LOCAL_FUSE)
-        if self.native_rank is not None:
-            _roctx.push("step_native_rank")
-            loss = self._loss_ring[self._ring_at:self._ring_at + 1]
-            self._ring_at += 1
-            rows = deep.in_nodes if self.local_row is None else self.local_row[deep.in_nodes.long()]
-            seeds = top.out_nodes[top.owned_out_nodes.long()]          # the seeds this rank owns, frontier order
-            self.native_rank([slices[self.L - 1 - k][self.rank] for k in range(self.L)], self.feat, rows, seeds,
-                             self.local_row, self.labels, 1.0 / max(n_seeds, 1), loss)
-            self.dist.all_reduce(self.native_rank.grads)               # replicated weights: sum of the ranks' shares
-            self.opt.step(flat_grads=self.native_rank.grads)
-            _roctx.pop()
-            self.steps_done += 1
-            return loss
-        if self.native is not None:
-            # forward, loss, backward: one native call; the optimizer: a second one on the flat gradient buffer
-            _roctx.push("step_native")
-            loss = self._loss_ring[self._ring_at:self._ring_at + 1]    # (run() sized the ring for its steps)
-            self._ring_at += 1
-            self.native([slices[self.L - 1 - k][self.rank] for k in range(self.L)], self.feat, self.labels,
-                        1.0 / self._loss_den(stream, slot, n_seeds), loss)
-            if self.grad_sync is not None:
-                self.grad_sync(self.native.grads)         # (data-parallel: sum over the ranks' shares of the minibatch)
-            self.opt.step(flat_grads=self.native.grads)
-            _roctx.pop()
-            self.steps_done += 1
-            return loss
-        if fused:
-            # one GPU holding every node: the deepest layer reads the resident feature table through the slice's
-            # in_nodes (no gathered input matrix), every layer is one fused node, the loss is one HIP pass
-            t1 = time.perf_counter()
-            _roctx.push("forward")
-            logits = self.model.forward_local(slices, self.feat)
-            loss = aggr.SoftmaxCE.apply(logits, top.out_nodes, self.labels, 1.0 / max(n_seeds, 1))
-            _roctx.pop()
-        else:
-            # gather of owned input features (row v // P of the owner v % P), int32 indices, float4 row kernel
-            _roctx.push("gather")
-            rows = deep.in_nodes if self.P == 1 else self.local_row[deep.in_nodes.long()]
-            if self.kind == "gat" and getattr(self, "gat_input", False):
-                x = aggr.FeatureRows(self.feat, rows)       # the deepest layer reads the table through in_nodes
-            elif self.kind == "gat" and not self.rank_path and self.P == 1 and not splitgnn._NO_LOCAL_FUSE:
-                # straight into the row-padded buffer the fused GAT layer multiplies (no second copy of 0.3 GB)
-                x = aggr.padded_rows(rows.numel(), self.feat.shape[1], splitgnn.ROW_PAD, self.dev)
-                aggr.gather_rows(self.feat, rows, out=x.t[:x.n])
-            else:
-                x = aggr.gather_rows(self.feat, rows)
-            _roctx.pop()
-            t1 = time.perf_counter()
-            _roctx.push("forward")
-            if self.rank_path:
-                if self.kind == "gat":
-                    logits = self.model.forward_rank(slices, x, self.rank, self.comm)
-                else:
-                    logits = self.model.forward_rank(slices, x, self.rank, self.comm, overlap=self.overlap)
-            else:
-                logits = self.model.forward_parts(slices, {0: x})[0]
-            seeds = top.out_nodes[top.owned_out_nodes.long()]  # the seeds this rank owns, frontier order
-            # mean over the WHOLE minibatch: sum of local losses / global seed count
-            if self.kind == "sage" and logits.shape[0] > 0:
-                loss = aggr.SoftmaxCE.apply(logits, seeds, self.labels, 1.0 / max(n_seeds, 1), self.local_row)
-            else:
-                seeds = seeds.long()
-                y = self.labels[seeds if self.P == 1 else self.local_row[seeds].long()]
-                den = max(n_seeds, 1) if self.rank_path else self._loss_den(stream, slot, n_seeds)   # (data-parallel: global)
-                loss = torch.nn.functional.cross_entropy(logits, y, reduction="sum") / den
-            _roctx.pop()
+        loss = self._path_step(slices, layers, int(meta.n_seeds), stream, slot)    # (_step_<plan.path>)
+        self.steps_done += 1
+        return loss
+
+    def _next_loss(self):
+        """the loss ring's next element (run() sized the ring for its steps)"""
+        loss = self._loss_ring[self._ring_at:self._ring_at + 1]
+        self._ring_at += 1
+        return loss
+
+    def _input_rows(self, deep):
+        """rows of self.feat that hold the deepest slice's input nodes (row v // P of the owner v % P, or the table's)"""
+        return deep.in_nodes if self.local_row is None else self.local_row[deep.in_nodes.long()]
+
+    def _step_native(self, slices, layers, n_seeds, stream, slot):
+        # forward, loss, backward: one native call; the optimizer: a second one on the flat gradient buffer
+        _roctx.push("step_native")
+        loss = self._next_loss()
+        self.native(layers, self.feat, self.labels, 1.0 / self._loss_den(stream, slot, n_seeds), loss)
+        if self.grad_sync is not None:
+            self.grad_sync(self.native.grads)             # (data-parallel: sum over the ranks' shares of the minibatch)
+        self.opt.step(flat_grads=self.native.grads)
+        _roctx.pop()
+        return loss
+
+    def _step_native_rank(self, slices, layers, n_seeds, stream, slot):
+        _roctx.push("step_native_rank")
+        loss = self._next_loss()
+        top = layers[-1]
+        seeds = top.out_nodes[top.owned_out_nodes.long()]              # the seeds this rank owns, frontier order
+        self.native_rank(layers, self.feat, self._input_rows(layers[0]), seeds, self.local_row, self.labels,
+                         1.0 / max(n_seeds, 1), loss)
+        self.dist.all_reduce(self.native_rank.grads)                   # replicated weights: sum of the ranks' shares
+        self.opt.step(flat_grads=self.native_rank.grads)
+        _roctx.pop()
+        return loss
+
+    def _step_local(self, slices, layers, n_seeds, stream, slot):
+        # one GPU holding every node: the deepest layer reads the resident feature table through the slice's
+        # in_nodes (no gathered input matrix), every layer is one fused node, the loss is one HIP pass
+        t1 = time.perf_counter()
+        _roctx.push("forward")
+        logits = self.model.forward_local(slices, self.feat)
+        loss = aggr.SoftmaxCE.apply(logits, layers[-1].out_nodes, self.labels, 1.0 / max(n_seeds, 1))
+        _roctx.pop()
         self.t_forward += time.perf_counter() - t1
+        return self._backward_and_update(loss)
+
+    def _step_parts(self, slices, layers, n_seeds, stream, slot):
+        # gather of owned input features, int32 indices, float4 row kernel
+        _roctx.push("gather")
+        rows = self._input_rows(layers[0])
+        if self.plan.input_form == "table":
+            x = aggr.FeatureRows(self.feat, rows)       # the deepest layer reads the table through in_nodes
+        elif self.plan.input_form == "padded":
+            x = aggr.padded_rows(rows.numel(), self.feat.shape[1], splitgnn.ROW_PAD, self.dev)
+            aggr.gather_rows(self.feat, rows, out=x.t[:x.n])
+        else:
+            x = aggr.gather_rows(self.feat, rows)
+        _roctx.pop()
+        t1 = time.perf_counter()
+        _roctx.push("forward")
+        if not self.rank_path:
+            logits = self.model.forward_parts(slices, {0: x})[0]
+        elif self.kind == "gat":
+            logits = self.model.forward_rank(slices, x, self.rank, self.comm)
+        else:
+            logits = self.model.forward_rank(slices, x, self.rank, self.comm, overlap=self.overlap)
+        top = layers[-1]
+        seeds = top.out_nodes[top.owned_out_nodes.long()]  # the seeds this rank owns, frontier order
+        # mean over the WHOLE minibatch: sum of local losses / global seed count
+        if self.kind == "sage" and logits.shape[0] > 0:
+            loss = aggr.SoftmaxCE.apply(logits, seeds, self.labels, 1.0 / max(n_seeds, 1), self.local_row)
+        else:
+            seeds = seeds.long()
+            y = self.labels[seeds if self.P == 1 else self.local_row[seeds].long()]
+            den = max(n_seeds, 1) if self.rank_path else self._loss_den(stream, slot, n_seeds)   # (data-parallel: global)
+            loss = torch.nn.functional.cross_entropy(logits, y, reduction="sum") / den
+        _roctx.pop()
+        self.t_forward += time.perf_counter() - t1
+        return self._backward_and_update(loss)
+
+    def _flat_grads(self):
+        """the parameters' gradients back to back (a rank whose share of the minibatch produced no gradient for a
+        parameter still takes part: zeros)"""
+        return torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1)
+                          for p in self.model.parameters()])
+
+    def _backward_and_update(self, loss):
+        """the autograd paths' second half: backward, the gradients' reduction where there is one, the optimizer"""
         _roctx.push("backward")
         self.opt.zero_grad(set_to_none=True)
         loss.backward()
         _roctx.pop()
-        if self.rank_path:
+        # rank path: replicated weights, sum of the per-rank gradients.  Data-parallel replicas on the autograd path (GAT):
+        # one all-reduce of the flat gradient, as the native step's
+        reduce = self.dist.all_reduce if self.rank_path else self.grad_sync
+        flat = None
+        if reduce is not None:
             _roctx.push("grad_allreduce")
-            # (a rank whose share of the minibatch produced no gradient for a parameter still takes part)
-            flat = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1)
-                              for p in self.model.parameters()])
-            self.dist.all_reduce(flat)                    # replicated weights: sum of per-rank gradients
-            if self.on_reduced_grads is not None:
+            flat = self._flat_grads()
+            reduce(flat)
+            if self.rank_path and self.on_reduced_grads is not None:
                 self.on_reduced_grads(flat)
             _roctx.pop()
-            _roctx.push("optimizer")
-            self.opt.step(flat_grads=flat)                # the reduced buffer is used in place
-            _roctx.pop()
-        elif self.grad_sync is not None:
-            # data-parallel replicas on the autograd path (GAT): one all-reduce of the flat gradient, as the native step's
-            _roctx.push("grad_allreduce")
-            flat = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1)
-                              for p in self.model.parameters()])
-            self.grad_sync(flat)
-            _roctx.pop()
-            _roctx.push("optimizer")
-            self.opt.step(flat_grads=flat)
-            _roctx.pop()
-        else:
-            _roctx.push("optimizer")
-            self.opt.step()
-            _roctx.pop()
-        self.steps_done += 1
+        _roctx.push("optimizer")
+        self.opt.step(flat_grads=flat)                    # (the reduced buffer is used in place)
+        _roctx.pop()
         return loss.detach()
 
     def run(self, n_steps, first_batch=0, then=None):
@@ -350,7 +420,7 @@ class Trainer(object):
         if not plan:
             return losses
 
-        if self.native is not None or self.native_rank is not None:
+        if self._loss_ring is not None:
             if self._loss_ring.numel() < n_steps:
                 self._loss_ring = torch.zeros((n_steps,), dtype=torch.float32, device=self.dev)
             self._ring_at = 0
@@ -400,7 +470,7 @@ class Trainer(object):
 
     def fused_deepest_layer(self):
         """whether the native step runs the deepest layer as the one fused gather -> fp32-MFMA kernel"""
-        if self.native is None or os.environ.get("CSLICER_NO_MFMA_FWD"):
+        if self.plan.path != "native" or os.environ.get("CSLICER_NO_MFMA_FWD"):
             return False
         fout, fin2 = self.model.convs[0].fc.weight.shape
         return aggr._lib().csl_sage_fwd_mfma_scratch(fin2 // 2, fout) > 0
@@ -513,7 +583,7 @@ class DataParallelTrainer(Trainer):
         kw.setdefault("rng_seed", 5489 + 7919 * self.dp_rank)
         super().__init__(indptr, indices, features, labels, n_classes, rank=0, world=1, batch=self.chunk, dist=None,
                          rank_path=False, **kw)
-        if self.native is None and self.kind != "gat":
+        if self.plan.path != "native" and self.kind != "gat":
             raise ValueError("the data-parallel trainer runs the native GraphSAGE step (feature and hidden widths "
                              "multiples of 4, at least two layers) or the single-GPU GAT step")
         if self.dp_world > 1:
@@ -664,7 +734,6 @@ def main(argv=None):
 
         python -m cslicer.train --graph <L0 dir> --feature-dtype bfloat16 --eval-split holdout
         python -m cslicer.train --graph products-like --model-name gat --feature-dtype bfloat16 --gat-input on"""
-    import os
     a = _parser().parse_args(argv)
     from . import l0
     if a.no_replace:     # (before the graph is loaded)

@@ -56,6 +56,45 @@ def test_native_step_trains_like_the_python_step(monkeypatch):
     np.testing.assert_allclose(curves[0], curves[1], rtol=2e-3)
 
 
+# (row of tests/test_step_plan_cpu.py, Trainer arguments / width of the table, switch, engine flags, native, gat_input)
+PLAN_ROWS = [
+    (1, {}, None, 4, True, False),
+    (2, {}, "CSLICER_PY_STEP", 4, False, False),
+    (3, {}, "CSLICER_NO_TRANSPOSE", 0, False, False),
+    (4, dict(fanouts=(10,)), None, 0, False, False),
+    (6, dict(F0=22), None, 4, False, False),
+    (15, dict(model="gat"), None, 4, False, True),
+    (16, dict(model="gat", feature_dtype="float16"), None, 4 | 8, False, False),
+    (18, dict(model="gat", gat_input=False), None, 4 | 8, False, False),
+]
+
+
+@pytest.mark.parametrize("row,kw,env,flags,native,gat_input", PLAN_ROWS, ids=["row%d" % r[0] for r in PLAN_ROWS])
+def test_the_trainer_follows_its_step_plan(row, kw, env, flags, native, gat_input, monkeypatch):
+    """rows of tests/test_step_plan_cpu.py on a device: the engine has the planned flags (4 = FLAG_TRANSPOSE, 8 =
+    FLAG_TRANSPOSE_ALL), the native stepper exists exactly where planned, and the planned path trains"""
+    from cslicer import splitgnn
+    from cslicer.train import Trainer
+    for name in ("CSLICER_PY_STEP", "CSLICER_NO_TRANSPOSE"):
+        monkeypatch.delenv(name, raising=False)
+    monkeypatch.setattr(splitgnn, "_NO_LOCAL_FUSE", False)
+    monkeypatch.setattr(splitgnn, "_NO_GAT_INPUT", False)
+    if env:
+        monkeypatch.setenv(env, "1")
+    kw = dict(kw)
+    indptr, indices, feats, labels, perm = _task(F0=kw.pop("F0", 24))
+    gat = kw.get("model") == "gat"
+    t = Trainer(indptr, indices, feats, labels, 5, **dict(dict(fanouts=(10, 5), batch=256, streams=2,
+                                                               hidden=16 if gat else 32, heads=4, lr=1e-2), **kw))
+    assert t.eng.flags == flags
+    assert (t.native is not None) == native and t.native_rank is None
+    assert bool(t.gat_input) == gat_input
+    t.set_nodes(perm)
+    losses = t.run(3)
+    assert len(losses) == 3 and all(np.isfinite(losses))
+    t.close()
+
+
 def _dp_rank_main(rank, world, port, q, kind="sage"):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
