@@ -5,6 +5,7 @@ plumbing; the work is done by the HIP kernels in occ-gnn_amd/csrc/aggregate.hip.
 Reference semantics: python/data/bipartite.py:61-99 (gather, self_gather, pull_for_remotes,
 push_from_remotes), src/gnn/sage.cu:7-28, src/gnn/dist_sage.cu:193-199.
 """
+import collections
 import ctypes as C
 import os
 
@@ -17,6 +18,7 @@ from . import _abi, l0
 _abi.load()
 SYMBOLS, FEAT16_SYMBOLS = _abi.BOUND["cslicer_aggr.h"], _abi.BOUND["cslicer_feat16.h"]
 GAT_IN16_SYMBOLS = _abi.BOUND["cslicer_gat_in16.h"]   # the attention input layer over a 16-bit table (forward AND backward)
+DROPOUT_SYMBOLS = _abi.BOUND["cslicer_dropout.h"]     # dropout between the GraphSAGE layers: the kernel and the native step with it
 EXCHANGE_FN, EXCHANGE_WAIT_FN = _abi.EXCHANGE_FN, _abi.EXCHANGE_WAIT_FN
 # element kinds of a 16-bit feature table (CSL_FEAT_F16 / CSL_FEAT_BF16); a float32 table has the fp32 entry points
 FEAT_KINDS = {torch.float16: 1, torch.bfloat16: 2}
@@ -356,6 +358,59 @@ def sage_cat_bwd_t(t_indptr, t_indices, indptr, gcat, y, n_src, n_pad, hub=False
     return out, buf[:H]
 
 
+# Dropout between the GraphSAGE layers (cslicer_dropout.h): probability, the run's seed and the step's counter.  A mask
+# is a pure function of (seed, step, layer, node id, column): nothing is saved for the backward.
+DropSpec = collections.namedtuple("DropSpec", "p seed step")
+
+
+def _i64(v):
+    """a Python int as the int64 the C ABI takes (its low 64 bits, signed)"""
+    v = int(v) & 0xFFFFFFFFFFFFFFFF
+    return v - (1 << 64) if v >> 63 else v
+
+
+def dropout_scale(p):
+    """s = (float)(1.0 / (1.0 - (double) p)) for the float32 p: what a kept element is multiplied by"""
+    p32 = C.c_float(p).value
+    return C.c_float(1.0 / (1.0 - p32)).value
+
+
+def dropout(x, ids, p, seed, layer, step, out=None):
+    """y = keep ? x / (1 - p) : 0 with the Philox mask of cslicer_dropout.h (csl_dropout_f32), keyed by the node ids `ids`
+    (int32, one per row; None: the row index).  out: the destination, x itself for the in-place form (default: a fresh
+    matrix).  x [n, H] float32 with unit column stride, H % 4 == 0; rows may be strided (a multiple of 4)."""
+    if x.dtype != torch.float32 or not x.is_cuda or x.dim() != 2 or x.stride(1) != 1:
+        raise TypeError("expected a float32 CUDA matrix with unit column stride")
+    n, H = x.shape
+    y = torch.empty((n, H), dtype=torch.float32, device=x.device) if out is None else out
+    if y.shape != x.shape or y.dtype != torch.float32 or y.stride(1) != 1 or y.device != x.device:
+        raise ValueError("out must be a float32 matrix of x's shape with unit column stride")
+    if ids is not None:
+        ids = _i32(ids)
+        if ids.numel() != n:
+            raise ValueError("one node id per row expected")
+    _chk(_lib().csl_dropout_f32(_p(x), x.stride(0), _p(y), y.stride(0), _p(ids) if ids is not None else C.c_void_p(0),
+                                n, H, float(p), _i64(seed), int(layer), _i64(step), _stream()), "csl_dropout_f32")
+    return y
+
+
+class Dropout(torch.autograd.Function):
+    """dropout() as an autograd node.  The map is linear: its backward is the same call on the gradient, the mask is
+    recomputed from the counter and never saved.  What is saved is the row's node ids (one int32 per row, through
+    save_for_backward, so that autograd's version check covers them)."""
+
+    @staticmethod
+    def forward(ctx, x, ids, p, seed, layer, step):
+        ctx.save_for_backward(*(() if ids is None else (ids,)))
+        ctx.cfg = (p, seed, layer, step)
+        return dropout(x if x.stride(-1) == 1 else x.contiguous(), ids, p, seed, layer, step)
+
+    @staticmethod
+    def backward(ctx, g):
+        ids = ctx.saved_tensors[0] if ctx.saved_tensors else None
+        return dropout(g if g.stride(-1) == 1 else g.contiguous(), ids, *ctx.cfg), None, None, None, None, None
+
+
 class SageSlice(C.Structure):
     """csl_sage_slice (cslicer_aggr.h)"""
     _fields_ = [("indptr", C.c_void_p), ("indices", C.c_void_p), ("self_ids_in", C.c_void_p),
@@ -426,9 +481,11 @@ class SageStep(_SageNative):
     (their storage must not move: an optimizer that updates in place, as aggr.Adam does)."""
     _stem, _workspace, _slice = "sage_fwd_bwd", "csl_sage_fwd_bwd_workspace", SageSlice
 
-    def __call__(self, slices, feat, labels, scale, loss_out):
+    def __call__(self, slices, feat, labels, scale, loss_out, drop=None):
         """slices: the part's `splitgnn.Slice`s in MODEL order (deepest hop first), from an engine with
-        FLAG_TRANSPOSE; feat: resident [N, F] features; labels int64 [N]; loss_out: one-element float32 tensor."""
+        FLAG_TRANSPOSE; feat: resident [N, F] features; labels int64 [N]; loss_out: one-element float32 tensor.
+        drop: a DropSpec: dropout on the output of every layer but the last (csl_sage_fwd_bwd_dropout), each layer's
+        rows keyed by its out-node ids."""
         A = _abi
         for k, s in enumerate(slices):
             c = self._sl[k]
@@ -440,6 +497,14 @@ class SageStep(_SageNative):
             c.n_out, c.n_in, c.t_max_len = s.n_out, s.n_in, s.t_max_len
             c.t_entries = s.count(A.T_INDICES) if k else 0
         self._grow(feat.device)
+        if drop is not None:
+            ids = (C.c_void_p * max(self.L - 1, 1))(*[s.ptr(A.OUT_NODES) for s in slices[:self.L - 1]])
+            fn = _lib().csl_sage_fwd_bwd_dropout
+            self._chk(fn(self.L, self._dims, self._sl, self._w, self._b, feat.data_ptr(), _table(feat) or 0, feat.stride(0),
+                         slices[0].ptr(A.IN_NODES), slices[-1].ptr(A.OUT_NODES), labels.data_ptr(), float(scale),
+                         self.row_pad, self.n_slabs, self.grads.data_ptr(), loss_out.data_ptr(), self._ws.data_ptr(),
+                         self._ws.numel(), ids, float(drop.p), _i64(drop.seed), _i64(drop.step), _stream()), fn.__name__)
+            return
         # a 16-bit table (float16 / bfloat16) goes to the step's _x16 twin: only its deepest layer's forward differs
         _table_call(self._twins, _table(feat), (self.L, self._dims, self._sl, self._w, self._b, feat.data_ptr()),
                     (feat.stride(0), slices[0].ptr(A.IN_NODES), slices[-1].ptr(A.OUT_NODES), labels.data_ptr(),

@@ -288,10 +288,12 @@ class _SageModelLocal(torch.autograd.Function):
     receives the ReLU mask of layer k-1, the row padding of its GEMM operand and its bias column sums.  Per layer:
     forward = csl_sage_cat_f32 + one GEMM (bias/ReLU epilogue); backward = weight-gradient GEMM (+ input-gradient
     GEMM and the fused gather for k > 0).  The deepest layer reads the resident feature table through its slice's
-    in_nodes.  Arguments: feat table, n_layers, then per layer (weight, bias, Slice) in model order (deepest first)."""
+    in_nodes.  Arguments: feat table, n_layers, drop (an aggr.DropSpec or None), then per layer (weight, bias, Slice) in
+    model order (deepest first).  With drop, every hidden y is dropped in place by its out-node ids (aggr.dropout): the
+    saved y then carries relu' * mask, and the backward multiplies what it hands down by s = 1 / (1 - p) per layer."""
 
     @staticmethod
-    def forward(ctx, feat, n_layers, *args):
+    def forward(ctx, feat, n_layers, drop, *args):
         ws, bs, sls = args[0::3], args[1::3], args[2::3]
         x, rowmap = feat, sls[0].in_nodes
         cats, ys = [], []
@@ -300,10 +302,13 @@ class _SageModelLocal(torch.autograd.Function):
             m, mp = sl.n_out, _pad_rows(sl.n_out)
             cat = aggr.sage_cat(x, sl.self_ids_in, m, mp, indptr=sl.indptr, indices=sl.indices, rowmap=rowmap)
             y = _linear_act(bs[k], cat, ws[k], k + 1 < n_layers)
+            if drop is not None and k + 1 < n_layers:
+                aggr.dropout(y[:m], sl.out_nodes, drop.p, drop.seed, k, drop.step, out=y[:m])
             cats.append(cat)
             ys.append(y)
             x, rowmap = y[:m], None
         ctx.n_layers, ctx.sls = n_layers, sls
+        ctx.drop_scale = None if drop is None else aggr.dropout_scale(drop.p)
         ctx.save_for_backward(*ws, *cats, *ys)
         return x
 
@@ -324,7 +329,9 @@ class _SageModelLocal(torch.autograd.Function):
             # gradient w.r.t. layer k-1's pre-activation output, padded like its GEMM operand, and its bias sums
             gyp, gb = aggr.sage_cat_bwd_t(sl.t_indptr, sl.t_indices, sl.indptr, _input_grad(gyp, ws[k]), ys[k - 1], sl.n_in,
                                           cats[k - 1].shape[0], hub=sl.t_max_len > _abi.T_SORTED_MAX)
-        return (None, None) + tuple(grads)
+            if ctx.drop_scale is not None:
+                gyp, gb = gyp.mul_(ctx.drop_scale), gb * ctx.drop_scale
+        return (None, None, None) + tuple(grads)
 
 
 class DistSageConv(nn.Module):
@@ -393,25 +400,38 @@ class DistSAGEModel(nn.Module):
         # convs[k] consumes engine layer n_layers-1-k (the deepest hop first)
         self.convs = nn.ModuleList([DistSageConv(dims[k], dims[k + 1]) for k in range(n_layers)])
 
-    def forward_parts(self, slices, feats):
+    @staticmethod
+    def _drop(drop, sl, x, k, owned):
+        """dropout (aggr.Dropout) of layer k's hidden output x on one part, keyed by the rows' node ids: the slice's
+        out_nodes, or those of its owned rows where the part holds only these"""
+        ids = sl.out_nodes[sl.owned_out_nodes.long()] if owned else sl.out_nodes
+        return aggr.Dropout.apply(x, ids, drop.p, drop.seed, k, drop.step)
+
+    def forward_parts(self, slices, feats, drop=None):
         """All parts in ONE process (validation / single GPU): slices[l][g], feats[g] = input
-        features of slices[L-1][g].in_nodes.  Returns per part the logits of its owned seeds."""
+        features of slices[L-1][g].in_nodes.  Returns per part the logits of its owned seeds.
+        drop: an aggr.DropSpec: dropout on every hidden layer's output (factory.py:41), here and in the two forms below."""
         L = len(slices)
         parts = sorted(slices[0].keys())
         x = {g: feats[g] for g in parts}
         for k, conv in enumerate(self.convs):
             sl = slices[L - 1 - k]
+            hidden = k + 1 < len(self.convs)
             if len(parts) == 1 and sl[parts[0]].n_parts == 1 and not _NO_LOCAL_FUSE and x[parts[0]].shape[1] % 4 == 0:
-                x = {parts[0]: conv.layer_local(sl[parts[0]], x[parts[0]], k + 1 < len(self.convs))}
+                x = {parts[0]: conv.layer_local(sl[parts[0]], x[parts[0]], hidden)}
+                if drop is not None and hidden:
+                    x = {parts[0]: self._drop(drop, sl[parts[0]], x[parts[0]], k, False)}
                 continue
             agg = {g: conv.local(sl[g], x[g]) for g in parts}
             send = {g: conv.boundary(sl[g], agg[g]) for g in parts}
             for g in parts:
                 agg[g] = conv.merge(sl[g], agg[g], [send[p][g] if p != g else None for p in parts])
-            x = {g: conv.finish_fused(sl[g], agg[g], x[g], k + 1 < len(self.convs)) for g in parts}
+            x = {g: conv.finish_fused(sl[g], agg[g], x[g], hidden) for g in parts}
+            if drop is not None and hidden:
+                x = {g: self._drop(drop, sl[g], x[g], k, True) for g in parts}
         return x
 
-    def forward_local(self, slices, feat_table, part=0):
+    def forward_local(self, slices, feat_table, part=0, drop=None):
         """A single part holding every node (one GPU): each layer is one `_SageLayerLocal` node.  `feat_table` is
         the resident [N, F] feature matrix; the deepest layer indexes it through its slice's in_nodes."""
         L = len(slices)
@@ -420,14 +440,16 @@ class DistSAGEModel(nn.Module):
             args = []
             for k, conv in enumerate(self.convs):
                 args += [conv.fc.weight, conv.fc.bias, slices[L - 1 - k][part]]
-            return _SageModelLocal.apply(feat_table, L, *args)
+            return _SageModelLocal.apply(feat_table, L, drop, *args)
         x, rowmap = feat_table, slices[L - 1][part].in_nodes
         for k, conv in enumerate(self.convs):
             x = conv.layer_local(slices[L - 1 - k][part], x, k + 1 < len(self.convs), rowmap)
+            if drop is not None and k + 1 < len(self.convs):
+                x = self._drop(drop, slices[L - 1 - k][part], x, k, False)
             rowmap = None
         return x
 
-    def forward_rank(self, slices, feat, rank, comm, overlap=False):
+    def forward_rank(self, slices, feat, rank, comm, overlap=False, drop=None):
         """One part per process: boundary partials go through `comm.all_to_all` (RCCL).
         overlap=True runs each layer's exchange on a side stream while the rows that stay on
         this GPU are aggregated (`_RankAggregate`); same numbers, different schedule."""
@@ -439,6 +461,8 @@ class DistSAGEModel(nn.Module):
             # forward whatever the number of peers (the op chain local / boundary / merge of forward_parts is
             # 2 + 2 (P - 1) launches and as many autograd nodes)
             x = conv.finish_fused(sl, _RankAggregate.apply(x, sl, comm, bool(overlap)), x, k + 1 < len(self.convs))
+            if drop is not None and k + 1 < len(self.convs):
+                x = self._drop(drop, sl, x, k, True)
         return x
 
 

@@ -69,13 +69,15 @@ def gat_input_obstacle(kind, world, rank_path, n_layers, F, hidden, n_classes, h
 
 
 def step_plan(kind, world, rank_path, n_layers, F, hidden, n_classes, heads, fanout, table_f32, gat_input, replace,
-              sw=Switches(), width_known=True):
+              sw=Switches(), width_known=True, dropout=0.0):
     """The StepPlan of a configuration, from plain values only (no device, no engine): every rule is written here once.
     ONE function, called when the rank's host rows are in hand -- F is the loaded table's width (feat_dim where given),
     which the path depends on -- so the constructor creates its engine after the host-side loading.
     rank_path: as resolved (None -> world > 1); fanout: the deepest layer's; table_f32: whether the feature table is
     float32; gat_input: the constructor's None / True / False; width_known: whether F was known before the rows were
-    loaded (feat_dim, or the shape of a feature matrix; False: callable features without feat_dim)."""
+    loaded (feat_dim, or the shape of a feature matrix; False: callable features without feat_dim); dropout: the
+    trainer's probability -- above 0 the rank path runs its autograd step (the native rank sequencer has no dropout), with
+    the engine flags that step has always asked for; every other row is what it is at 0."""
     sage, gat = kind == "sage", kind == "gat"
     single = not rank_path and world == 1      # one part in one process, no collective
     want = table_f32 if gat_input is None else gat_input     # (None: a 16-bit table keeps the numbers its runs have had)
@@ -86,6 +88,11 @@ def step_plan(kind, world, rank_path, n_layers, F, hidden, n_classes, heads, fan
     by_source = sage and n_layers > 1 and not sw.no_transpose
     # the single part with every layer as one fused node, the deepest reading the resident table through in_nodes
     local = single and sage and F % 4 == 0 and not sw.no_local_fuse
+    native_rank = rank_path and sage and F % 4 == 0 and hidden % 4 == 0 and n_classes <= 256 and not sw.py_step
+    if native_rank and dropout > 0:
+        # the native rank sequencer has no dropout: the rank's autograd step, planned as CSLICER_PY_STEP plans it
+        return step_plan(kind, world, rank_path, n_layers, F, hidden, n_classes, heads, fanout, table_f32, gat_input,
+                         replace, sw._replace(py_step=True), width_known)
 
     flags = 0
     if by_source and (single or (rank_path and not sw.py_step)):
@@ -99,7 +106,7 @@ def step_plan(kind, world, rank_path, n_layers, F, hidden, n_classes, heads, fan
     if not replace:
         flags |= _abi.FLAG_NO_REPLACE
 
-    if rank_path and sage and F % 4 == 0 and hidden % 4 == 0 and n_classes <= 256 and not sw.py_step:
+    if native_rank:
         path = "native_rank"
     elif local and by_source and hidden % 4 == 0 and not sw.py_step:
         path = "native"
@@ -124,7 +131,7 @@ class Trainer(object):
     def __init__(self, indptr, indices, features, labels, n_classes, rank=0, world=1, fanouts=(15, 10, 5),
                  batch=1024, streams=8, hidden=256, lr=1e-3, device=0, dist=None, seed=0, overlap=False,
                  model="sage", heads=8, rank_path=None, workload=None, feat_dim=None, rng_seed=5489,
-                 feature_dtype="float32", gat_input=None, replace=True):
+                 feature_dtype="float32", gat_input=None, replace=True, dropout=0.0, dropout_seed=None):
         """Part `rank` of `world`.  Ownership = the engine's workload table (`workload` int32 [N], the METIS map of
         python/utils/sampler.py:64-134 / partition_map_opt.bin; None = v % world like pyfrontend.cpp:57): the rank
         keeps the feature and label rows of the nodes it owns, in ascending node order.
@@ -154,9 +161,24 @@ class Trainer(object):
         mt19937 words, mapped by Floyd's subset algorithm), the default of dgl.sampling.sample_neighbors that the
         reference's Python trainers sample with; every fanout must then be <= _abi.noreplace_max_fanout().
 
+        dropout: probability in [0, 1) of dropping each element of every hidden layer's output (after its ReLU; the
+        feature table and the last layer are not dropped: models/factory.py:41), kept elements scaled by 1 / (1 - p).
+        GraphSAGE only.  The mask is a pure function of (dropout_seed, step, layer, node id, column) -- Philox4x32-10,
+        include/cslicer_dropout.h -- with the step counted by `self.steps_done`, so that a node's mask never repeats
+        across epochs and is the same on one GPU and on any number of ranks; dropout_seed=None takes `seed`.  0 (default)
+        runs no dropout code at all; evaluate() / predict() never drop (inverted scaling makes inference the identity).
+
         `self.plan` is the StepPlan of the configuration (step_plan above): which step the trainer runs, decided here
         once; `self.native` / `self.native_rank` are the native stepper of that path, None on every other path."""
         # -- 1. the arguments (before any device call: a request that cannot be served is an error, never a quiet fall-back)
+        dropout = float(dropout)
+        if not 0.0 <= dropout < 1.0:
+            raise ValueError("dropout must be in [0, 1), not %r" % (dropout,))
+        if dropout > 0 and model == "gat":
+            raise ValueError("dropout > 0: the attention model has no dropout (model='sage' only)")
+        if dropout > 0 and hidden % 4 != 0:
+            raise ValueError("dropout > 0: hidden must be a multiple of 4 (the kernel moves float4 columns), not %d" % hidden)
+        self.dropout, self.dropout_seed = dropout, int(seed if dropout_seed is None else dropout_seed)
         if not replace and max(fanouts) > _abi.noreplace_max_fanout():
             raise ValueError("replace=False: fanouts %r exceed the limit of %d neighbours per row"
                              % (tuple(fanouts), _abi.noreplace_max_fanout()))
@@ -214,7 +236,8 @@ class Trainer(object):
         # -- 3. how this configuration trains, 4. the engine it needs.  One process per part: only this rank's slices are
         # materialised (the sampling itself is replicated)
         self.plan = step_plan(model, world, self.rank_path, self.L, F, hidden, n_classes, heads, fanouts[-1],
-                              fdt == torch.float32, gat_input, replace, sw, width_known=F_early is not None)
+                              fdt == torch.float32, gat_input, replace, sw, width_known=F_early is not None,
+                              dropout=dropout)
         self.gat_input, self.replace = self.plan.gat_input, bool(replace)
         self.eng = _abi.Engine(indptr, indices, n_parts=self.P, fanouts=fanouts, max_batch=batch,
                                n_streams=streams, n_slots=self.SLOTS, device=device, mode=_abi.MODE_GRAPH,
@@ -300,6 +323,10 @@ class Trainer(object):
         self.steps_done += 1
         return loss
 
+    def _drop(self):
+        """the DropSpec of the step about to run (its counter: the steps done so far), None without dropout"""
+        return aggr.DropSpec(self.dropout, self.dropout_seed, self.steps_done) if self.dropout > 0 else None
+
     def _next_loss(self):
         """the loss ring's next element (run() sized the ring for its steps)"""
         loss = self._loss_ring[self._ring_at:self._ring_at + 1]
@@ -314,7 +341,7 @@ class Trainer(object):
         # forward, loss, backward: one native call; the optimizer: a second one on the flat gradient buffer
         _roctx.push("step_native")
         loss = self._next_loss()
-        self.native(layers, self.feat, self.labels, 1.0 / self._loss_den(stream, slot, n_seeds), loss)
+        self.native(layers, self.feat, self.labels, 1.0 / self._loss_den(stream, slot, n_seeds), loss, self._drop())
         if self.grad_sync is not None:
             self.grad_sync(self.native.grads)             # (data-parallel: sum over the ranks' shares of the minibatch)
         self.opt.step(flat_grads=self.native.grads)
@@ -338,7 +365,7 @@ class Trainer(object):
         # in_nodes (no gathered input matrix), every layer is one fused node, the loss is one HIP pass
         t1 = time.perf_counter()
         _roctx.push("forward")
-        logits = self.model.forward_local(slices, self.feat)
+        logits = self.model.forward_local(slices, self.feat, drop=self._drop())
         loss = aggr.SoftmaxCE.apply(logits, layers[-1].out_nodes, self.labels, 1.0 / max(n_seeds, 1))
         _roctx.pop()
         self.t_forward += time.perf_counter() - t1
@@ -358,12 +385,14 @@ class Trainer(object):
         _roctx.pop()
         t1 = time.perf_counter()
         _roctx.push("forward")
+        # (drop: GraphSAGE only -- the constructor refuses the attention model with dropout > 0, so self._drop() is None there)
+        kw = {"drop": self._drop()} if self.kind == "sage" else {}
         if not self.rank_path:
-            logits = self.model.forward_parts(slices, {0: x})[0]
+            logits = self.model.forward_parts(slices, {0: x}, **kw)[0]
         elif self.kind == "gat":
             logits = self.model.forward_rank(slices, x, self.rank, self.comm)
         else:
-            logits = self.model.forward_rank(slices, x, self.rank, self.comm, overlap=self.overlap)
+            logits = self.model.forward_rank(slices, x, self.rank, self.comm, overlap=self.overlap, **kw)
         top = layers[-1]
         seeds = top.out_nodes[top.owned_out_nodes.long()]  # the seeds this rank owns, frontier order
         # mean over the WHOLE minibatch: sum of local losses / global seed count
@@ -716,8 +745,10 @@ def main(argv=None):
     --fan-out follows the reference (DGL) convention, input side first (python/train.py:128,
     batch_slice_multi_gpu.py:202): the LAST number is the hop from the seeds.  --graph: an L0 directory
     (cslicer.l0), a preset name (arxiv-like, products-like, papers-like) or `synthetic`.
+    --dropout: `Trainer(dropout=...)`, between the GraphSAGE layers as models/factory.py:41 applies it (the default, 0,
+    runs none; the attention model refuses a value above 0).
     Accepted and ignored (no counterpart here): --cache-per (features are resident in HBM), --num-workers,
-    --dropout, --debug, --log-every.
+    --debug, --log-every.
     --eval-split (extra): `none` (default) trains on every node and never evaluates; `file` trains on the L0 directory's
     train_idx.bin and evaluates val_idx.bin; `holdout` trains on a seeded 80 % of the nodes and evaluates the other
     20 %.  With a split the model is evaluated by full-neighbour inference every --eval-every epochs and after the last
@@ -784,7 +815,8 @@ def main(argv=None):
     tr = Trainer(indptr, indices, feats, labels, n_classes, rank=rank, world=world, fanouts=fan, batch=a.batch_size,
                  streams=8, hidden=max(4, hidden // 4 * 4), lr=a.lr, device=local, dist=dist, model=kind, heads=a.num_heads,
                  workload=workload, feat_dim=fdim, feature_dtype=fdtype,
-                 gat_input={"auto": None, "on": True, "off": False}[a.gat_input], replace=not a.no_replace)
+                 gat_input={"auto": None, "on": True, "off": False}[a.gat_input], replace=not a.no_replace,
+                 dropout=a.dropout)
     if rank == 0 and fdtype != "float32":
         print("feature table: %s, %d bytes on this rank" % (fdtype, tr.feat.numel() * tr.feat.element_size()))
     n = indptr.shape[0] - 1

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "cslicer_aggr.h"
+#include "cslicer_dropout.h"
 #include "cslicer_feat16.h"
 #include "cslicer_hip.h"
 #include "dev_common.h"
@@ -213,6 +214,14 @@ struct Deferred {
   int finish(void* stream) { return csl_reduce_multi_f32(n, src, nblk, h, dst, stream); }
 };
 
+// dropout between the layers (csl_sage_fwd_bwd_dropout, cslicer_dropout.h): layer k's out-node ids, the probability and the
+// counter's seed and step
+struct DropArgs {
+  const int32_t* const* out_ids;
+  float p;
+  int64_t seed, step;
+};
+
 // gW_k = gy_k^T cat_k of either layout (Layout, RankLayout): nothing but a zero fill without rows, in row slabs whose sum
 // is deferred, or one plain GEMM.  group: the timing group of the GEMM (< 0: untimed)
 template <typename Lay>
@@ -263,11 +272,12 @@ int64_t csl_sage_fwd_bwd_workspace(int32_t n_layers, const int32_t* dims, const 
   return o.total;
 }
 
-// the step behind csl_sage_fwd_bwd_f32 (kind 0) and csl_sage_fwd_bwd_x16
+// the step behind csl_sage_fwd_bwd_f32 (kind 0), csl_sage_fwd_bwd_x16 and, with `drop`, csl_sage_fwd_bwd_dropout
 static int sage_fwd_bwd(int32_t n_layers, const int32_t* dims, const csl_sage_slice* sl, const float* const* weights,
                         const float* const* biases, const void* feat, int32_t kind, int64_t ldf, const int32_t* feat_rows,
                         const int32_t* seed_ids, const int64_t* labels, float scale, int64_t row_pad, int32_t n_slabs,
-                        float* grads, float* loss, float* workspace, int64_t workspace_floats, void* stream) {
+                        float* grads, float* loss, float* workspace, int64_t workspace_floats, void* stream,
+                        const DropArgs* drop = nullptr) {
   int k = -1;
   s_err[0] = 0;
   Layout o;
@@ -292,12 +302,20 @@ static int sage_fwd_bwd(int32_t n_layers, const int32_t* dims, const csl_sage_sl
       TSTEP(CSL_STEP_FUSED_FWD, rd::sage_fwd_mfma(sl[0].indptr, sl[0].indices, sl[0].self_ids_in, feat_rows, feat, kind, ldf, weights[0],
                                                   2 * (int64_t)in, biases[0], m, mp, in, out, 0, L > 1 ? 1 : 0, ws + o.cat[0],
                                                   2 * (int64_t)in, ws + o.y[0], out, ws + o.wpack, stream));
+      if (drop && L > 1)
+        TSTEP(CSL_STEP_OTHER, csl_dropout_f32(ws + o.y[0], out, ws + o.y[0], out, drop->out_ids[0], m, out, drop->p, drop->seed, 0,
+                                              drop->step, stream));
       continue;
     }
     TSTEP(CSL_STEP_AGGREGATION, rd::sage_cat(sl[k].indptr, sl[k].indices, sl[k].self_ids_in, nullptr, nullptr, k == 0 ? feat_rows : nullptr, x,
                                              xk, k == 0 ? ldf : (int64_t)in, nullptr, 0, m, mp, ws + o.cat[k], 2 * (int64_t)in, in, 0, stream));
     TSTEP(CSL_STEP_GEMM, csl_gemm_f32(0, 1, mp, out, 2 * (int64_t)in, ws + o.cat[k], 2 * (int64_t)in, 0, weights[k], 2 * (int64_t)in, 0,
                       ws + o.y[k], out, 0, 1, biases[k], k + 1 < L ? 1 : 0, stream));
+    // y_k is stored after its ReLU and read as it is by the layer above and by the backward's mask (y_k > 0): dropped in
+    // place it carries relu' * mask by itself
+    if (drop && k + 1 < L)
+      TSTEP(CSL_STEP_OTHER, csl_dropout_f32(ws + o.y[k], out, ws + o.y[k], out, drop->out_ids[k], m, out, drop->p, drop->seed, k,
+                                            drop->step, stream));
   }
   Deferred later;
   // ---- loss and its gradient w.r.t. the logits (written as the top layer's padded gy), bias column sums alongside
@@ -347,6 +365,22 @@ static int sage_fwd_bwd(int32_t n_layers, const int32_t* dims, const csl_sage_sl
   // ---- every deferred second stage (bias sums, weight-gradient slabs, the loss) in one launch
   k = -1;
   TSTEP(CSL_STEP_OTHER, later.finish(stream));
+  if (drop && L > 1) {
+    // the backward crossed L-1-j dropped layers on its way to layer j with the mask alone: the factor s of each, which
+    // commutes with everything downstream of it, goes onto the finished gradients
+    float* seg[CSL_SCALE_SEGMENTS_MAX];
+    int64_t cnt[CSL_SCALE_SEGMENTS_MAX];
+    float fac[CSL_SCALE_SEGMENTS_MAX];
+    const double s1 = (double)(float)(1.0 / (1.0 - (double)drop->p));
+    double f = 1.0;
+    int ns = 0;
+    for (int j = L - 2; j >= 0; j--) {
+      f *= s1;
+      seg[ns] = gs.gW[j], cnt[ns] = (int64_t)dims[j + 1] * 2 * dims[j], fac[ns] = (float)f, ns++;
+      seg[ns] = gs.gb[j], cnt[ns] = dims[j + 1], fac[ns] = (float)f, ns++;
+    }
+    TSTEP(CSL_STEP_OTHER, csl_scale_segments_f32(ns, seg, cnt, fac, stream));
+  }
   return CSL_OK;
 }
 
@@ -365,6 +399,24 @@ int csl_sage_fwd_bwd_x16(int32_t n_layers, const int32_t* dims, const csl_sage_s
   if (table16_refused(feat, kind, ldf)) return CSL_E_INVALID;
   return sage_fwd_bwd(n_layers, dims, sl, weights, biases, feat, kind, ldf, feat_rows, seed_ids, labels, scale, row_pad,
                       n_slabs, grads, loss, workspace, workspace_floats, stream);
+}
+
+int csl_sage_fwd_bwd_dropout(int32_t n_layers, const int32_t* dims, const csl_sage_slice* sl, const float* const* weights,
+                             const float* const* biases, const void* feat, int32_t kind, int64_t ldf, const int32_t* feat_rows,
+                             const int32_t* seed_ids, const int64_t* labels, float scale, int64_t row_pad, int32_t n_slabs,
+                             float* grads, float* loss, float* workspace, int64_t workspace_floats,
+                             const int32_t* const* out_ids, float p, int64_t seed, int64_t step, void* stream) {
+  if (kind != 0 && table16_refused(feat, kind, ldf)) return CSL_E_INVALID;
+  bool ok = p > 0.f && p < 1.f && n_layers >= 1 && n_layers <= CSL_MAX_LAYERS && sl && (n_layers == 1 || out_ids);
+  for (int k = 0; ok && k + 1 < n_layers; k++) ok = sl[k].n_out <= 0 || out_ids[k];
+  if (!ok) {
+    snprintf(s_err, sizeof(s_err), "dropout: 0 < p < 1 and the out-node ids of every layer but the last expected (p = %g)",
+             (double)p);
+    return CSL_E_INVALID;
+  }
+  const DropArgs drop = {out_ids, p, seed, step};
+  return sage_fwd_bwd(n_layers, dims, sl, weights, biases, feat, kind, ldf, feat_rows, seed_ids, labels, scale, row_pad,
+                      n_slabs, grads, loss, workspace, workspace_floats, stream, &drop);
 }
 
 }  // extern "C"
