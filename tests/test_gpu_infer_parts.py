@@ -110,13 +110,13 @@ def _run_part(kind, lens, W, pack, seed, H=1, D=4, slope=0.2, shift=0.0):
     return err
 
 
-@pytest.mark.parametrize("W", [4, 48, 100, 256])
+@pytest.mark.parametrize("W", [4, 24, 48, 100, 256])
 @pytest.mark.parametrize("pack", [1, 2, 4])
 def test_sage_part_kernel(W, pack):
     assert _run_part("sage", LENS, W, pack, seed=W + pack) <= 1e-5
 
 
-@pytest.mark.parametrize("H,D", [(1, 4), (4, 8), (8, 32), (3, 100)])
+@pytest.mark.parametrize("H,D", [(1, 4), (4, 8), (2, 32), (4, 32), (8, 32), (3, 100)])
 @pytest.mark.parametrize("slope,shift", [(0.0, 0.0), (0.2, 120.0), (1.0, -120.0)])
 def test_gat_part_kernel(H, D, slope, shift):
     for pack in (1, 4):
@@ -136,7 +136,7 @@ def _merge_lists(n, P, seed):
     return ml, r
 
 
-@pytest.mark.parametrize("W,proj", [(4, 0), (48, 1), (100, 0), (256, 1)])
+@pytest.mark.parametrize("W,proj", [(4, 0), (24, 0), (48, 1), (100, 0), (256, 1)])
 def test_sage_merge_kernel(W, proj):
     from cslicer import aggr, infer
     dev = torch.device("cuda", 0)
@@ -168,7 +168,8 @@ def test_sage_merge_kernel(W, proj):
     assert _rel(out.cpu(), want) <= 1e-5
 
 
-@pytest.mark.parametrize("H,D,last,n_cls", [(1, 4, 0, 0), (4, 8, 1, 7), (8, 32, 0, 0), (8, 32, 1, 32)])
+@pytest.mark.parametrize("H,D,last,n_cls", [(1, 4, 0, 0), (4, 8, 1, 7), (2, 32, 0, 0), (4, 32, 1, 20), (8, 32, 0, 0),
+                                            (8, 32, 1, 32)])
 def test_gat_merge_kernel(H, D, last, n_cls):
     from cslicer import aggr, infer
     dev = torch.device("cuda", 0)
