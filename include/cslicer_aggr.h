@@ -276,6 +276,8 @@ int csl_relu_bwd_colsum_f32(const float* g, int64_t ldg, const float* y, int64_t
 /* cross-entropy (python/train.py:86), forward and backward in one pass:
  * *loss = -scale * sum_r log softmax(logits[r])[label_r]; grad[r, :] = scale * (softmax(logits[r]) - onehot(label_r));
  * label_r = labels[rowmap ? rowmap[ids[r]] : ids[r]] (int64 labels, int32 node ids).
+ * A label outside [0, C) is never used as an index: that row's loss is NaN and its gradient row is NaN, in both entry
+ * points, so *loss (its block's loss_partial, and the column sums) come out NaN; every other row is unaffected.
  * scratch: csl_softmax_ce_scratch(n) floats. */
 int64_t csl_softmax_ce_scratch(int64_t n);
 int csl_softmax_ce_f32(const float* logits, int64_t ldl, int64_t n, int32_t C, const int32_t* ids, const int32_t* rowmap,
