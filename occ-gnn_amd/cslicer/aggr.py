@@ -19,6 +19,7 @@ _abi.load()
 SYMBOLS, FEAT16_SYMBOLS = _abi.BOUND["cslicer_aggr.h"], _abi.BOUND["cslicer_feat16.h"]
 GAT_IN16_SYMBOLS = _abi.BOUND["cslicer_gat_in16.h"]   # the attention input layer over a 16-bit table (forward AND backward)
 DROPOUT_SYMBOLS = _abi.BOUND["cslicer_dropout.h"]     # dropout between the GraphSAGE layers: the kernel and the native step with it
+MULTILABEL_SYMBOLS = _abi.BOUND["cslicer_multilabel.h"]   # the sigmoid-BCE loss, the micro-F1 head, the native step with that loss
 EXCHANGE_FN, EXCHANGE_WAIT_FN = _abi.EXCHANGE_FN, _abi.EXCHANGE_WAIT_FN
 # element kinds of a 16-bit feature table (CSL_FEAT_F16 / CSL_FEAT_BF16); a float32 table has the fp32 entry points
 FEAT_KINDS = {torch.float16: 1, torch.bfloat16: 2}
@@ -485,7 +486,9 @@ class SageStep(_SageNative):
         """slices: the part's `splitgnn.Slice`s in MODEL order (deepest hop first), from an engine with
         FLAG_TRANSPOSE; feat: resident [N, F] features; labels int64 [N]; loss_out: one-element float32 tensor.
         drop: a DropSpec: dropout on the output of every layer but the last (csl_sage_fwd_bwd_dropout), each layer's
-        rows keyed by its out-node ids."""
+        rows keyed by its out-node ids.
+        labels int32 [N, W] (pack_labels: a multi-label trainer's): the sigmoid-BCE loss, csl_sage_fwd_bwd_multilabel,
+        with the DropSpec if there is one."""
         A = _abi
         for k, s in enumerate(slices):
             c = self._sl[k]
@@ -497,6 +500,22 @@ class SageStep(_SageNative):
             c.n_out, c.n_in, c.t_max_len = s.n_out, s.n_in, s.t_max_len
             c.t_entries = s.count(A.T_INDICES) if k else 0
         self._grow(feat.device)
+        if labels.dim() == 2:
+            if labels.dtype != torch.int32 or not labels.is_cuda or labels.stride(1) != 1 \
+                    or labels.shape[1] != label_words(self.dims[-1]):
+                raise TypeError("multi-label labels: an int32 CUDA matrix [N, %d] of packed words (pack_labels) expected"
+                                % label_words(self.dims[-1]))
+            ids = None
+            if drop is not None:
+                ids = (C.c_void_p * max(self.L - 1, 1))(*[s.ptr(A.OUT_NODES) for s in slices[:self.L - 1]])
+            fn = _lib().csl_sage_fwd_bwd_multilabel
+            self._chk(fn(self.L, self._dims, self._sl, self._w, self._b, feat.data_ptr(), _table(feat) or 0, feat.stride(0),
+                         slices[0].ptr(A.IN_NODES), slices[-1].ptr(A.OUT_NODES), labels.data_ptr(), labels.stride(0),
+                         float(scale), self.row_pad, self.n_slabs, self.grads.data_ptr(), loss_out.data_ptr(),
+                         self._ws.data_ptr(), self._ws.numel(), ids, float(drop.p) if drop is not None else 0.0,
+                         _i64(drop.seed) if drop is not None else 0, _i64(drop.step) if drop is not None else 0, _stream()),
+                      fn.__name__)
+            return
         if drop is not None:
             ids = (C.c_void_p * max(self.L - 1, 1))(*[s.ptr(A.OUT_NODES) for s in slices[:self.L - 1]])
             fn = _lib().csl_sage_fwd_bwd_dropout
@@ -639,6 +658,49 @@ class SoftmaxCE(torch.autograd.Function):
                                   _p(rowmap) if rowmap is not None else C.c_void_p(0), _p(labels), float(scale),
                                   C.c_void_p(buf.data_ptr()), _p(grad), grad.stride(0),
                                   C.c_void_p(buf.data_ptr() + 4), _stream()), "csl_softmax_ce_f32")
+        ctx.save_for_backward(grad)
+        return buf[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return grad * g, None, None, None, None
+
+
+# Multi-label classification (cslicer_multilabel.h): a node's classes as packed bits, class c = bit c % 32 of word c / 32
+label_words = l0.label_words
+
+
+def pack_labels(y):
+    """[n, C] of 0 / 1 (bool or integer; numpy or a host tensor) -> int32 numpy [n, ceil(C / 32)] (host side); any other
+    value is a ValueError"""
+    return l0.pack_labels(y.cpu().numpy() if torch.is_tensor(y) else y)
+
+
+def unpack_labels(words, C):
+    """int32 [n, ceil(C / 32)] -> bool numpy [n, C] (host side); bits at and above C are not looked at"""
+    return l0.unpack_labels(words.cpu().numpy() if torch.is_tensor(words) else words, C)
+
+
+class SigmoidBCE(torch.autograd.Function):
+    """Binary cross-entropy with logits summed over rows and classes and scaled (torch.nn.BCEWithLogitsLoss() for
+    scale = 1 / (rows * C)), forward and backward in one HIP pass (csl_sigmoid_bce_f32): the packed label row of logits
+    row r = label_words[rowmap[ids[r]]] (rowmap None: label_words[ids[r]]); returns the scalar loss."""
+
+    @staticmethod
+    def forward(ctx, logits, ids, label_words, scale, rowmap=None):
+        logits = _f32(logits)
+        n, Cn = logits.shape
+        if label_words.dtype != torch.int32 or not label_words.is_cuda or label_words.dim() != 2 \
+                or label_words.stride(1) != 1 or label_words.shape[1] != (Cn + 31) // 32:
+            raise TypeError("label_words must be an int32 CUDA matrix [rows, %d] (pack_labels)" % ((Cn + 31) // 32))
+        L = _lib()
+        buf = torch.empty((1 + max(int(L.csl_sigmoid_bce_scratch(n)), 1),), dtype=torch.float32, device=logits.device)
+        grad = torch.empty((n, Cn), dtype=torch.float32, device=logits.device)
+        _chk(L.csl_sigmoid_bce_f32(_p(logits), logits.stride(0), n, Cn, _p(_i32(ids)),
+                                   _p(rowmap) if rowmap is not None else C.c_void_p(0), _p(label_words),
+                                   label_words.stride(0), float(scale), C.c_void_p(buf.data_ptr()), _p(grad),
+                                   grad.stride(0), C.c_void_p(buf.data_ptr() + 4), _stream()), "csl_sigmoid_bce_f32")
         ctx.save_for_backward(grad)
         return buf[0]
 

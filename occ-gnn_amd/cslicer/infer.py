@@ -611,11 +611,53 @@ def eval_head(logits, labels):
     return pred[:n], int(correct.item()), float(loss_sum.item())
 
 
-def evaluate(model, indptr, indices, features, nodes, labels, chunk_rows=CHUNK_ROWS, _zero_padded=False):
+def eval_head_multilabel(logits, label_words):
+    """(pred_words int32 [n, W], (tp, fp, fn), summed binary cross-entropy) of logits [n, C] against the packed labels
+    [n, W = ceil(C / 32)] of the same rows (int32, aggr.pack_labels), in one pass over the logits
+    (csl_infer_eval_multilabel_f32): class c is predicted where logits[:, c] > 0; the loss is summed over rows and
+    classes (float64, fixed order)."""
+    logits = logits if logits.stride(1) == 1 else logits.contiguous()
+    n, C_ = logits.shape
+    W = aggr.label_words(C_)
+    words = torch.as_tensor(label_words).to(logits.device)
+    if words.dtype != torch.int32 or words.dim() != 2 or words.shape != (n, W):
+        raise ValueError("label_words must be int32 [%d, %d] packed words (aggr.pack_labels)" % (n, W))
+    words = words if words.stride(1) == 1 else words.contiguous()
+    pred = torch.empty((max(n, 1), W), dtype=torch.int32, device=logits.device)
+    loss_row = torch.empty((max(n, 1),), dtype=torch.float32, device=logits.device)
+    loss_sum = torch.empty((1,), dtype=torch.float64, device=logits.device)
+    counts = torch.empty((3,), dtype=torch.int64, device=logits.device)
+    _chk(_lib().csl_infer_eval_multilabel_f32(_ptr(logits), logits.stride(0), n, C_, _ptr(words), max(words.stride(0), W),
+                                              _ptr(pred), _ptr(loss_row), _ptr(loss_sum), _ptr(counts), aggr._stream()),
+         "csl_infer_eval_multilabel_f32")
+    tp, fp, fn = (int(v) for v in counts.tolist())
+    return pred[:n], (tp, fp, fn), float(loss_sum.item())
+
+
+def multilabel_scores(tp, fp, fn, loss_sum, n, n_classes):
+    """the dict evaluate(multilabel=True) returns: micro-F1 = 2 tp / (2 tp + fp + fn) (0.0 over an empty denominator),
+    the loss as the mean per element"""
+    den = 2 * tp + fp + fn
+    return {"micro_f1": (2 * tp / den) if den else 0.0, "loss": loss_sum / max(n * n_classes, 1), "n": n,
+            "tp": tp, "fp": fp, "fn": fn}
+
+
+def evaluate(model, indptr, indices, features, nodes, labels, chunk_rows=CHUNK_ROWS, _zero_padded=False, multilabel=False):
     """{"accuracy", "loss", "n"} of the model on `nodes` by full-neighbour inference: argmax accuracy and mean
-    cross-entropy.  labels: int [N], the label of every node of the graph (those of `nodes` are used)."""
+    cross-entropy.  labels: int [N], the label of every node of the graph (those of `nodes` are used).
+    multilabel=True: labels are the packed words int32 [N, ceil(C / 32)] (aggr.pack_labels) and the result is
+    {"micro_f1", "loss", "n", "tp", "fp", "fn"} (multilabel_scores)."""
     nodes = _node_ids(nodes)
     lab = torch.as_tensor(labels)
+    if multilabel:
+        if lab.dim() != 2 or lab.shape[0] != features.shape[0] or lab.dtype != torch.int32:
+            raise ValueError("multilabel=True: labels must be the packed int32 words of every node of the graph ([%d, W])"
+                             % features.shape[0])
+        logits = full_inference(model, indptr, indices, features, nodes=nodes, chunk_rows=chunk_rows,
+                                _zero_padded=_zero_padded)
+        lab = lab[torch.from_numpy(nodes).to(lab.device)]
+        _, (tp, fp, fn), loss = eval_head_multilabel(logits, lab)
+        return multilabel_scores(tp, fp, fn, loss, int(nodes.shape[0]), int(logits.shape[1]))
     if lab.dim() != 1 or lab.shape[0] != features.shape[0]:
         raise ValueError("labels must hold one label per node of the graph ([%d])" % features.shape[0])
     logits = full_inference(model, indptr, indices, features, nodes=nodes, chunk_rows=chunk_rows,
@@ -1006,16 +1048,22 @@ def owns(N, P, rank, nodes, owner=None):
 
 
 def evaluate_parts(model, indptr, indices, features_own, comm, nodes, labels_own, owner=None, chunk_rows=CHUNK_ROWS,
-                   _zero_padded=False):
+                   _zero_padded=False, multilabel=False):
     """evaluate() on one rank of a split-parallel run (collective, see full_inference_parts): {"accuracy", "loss", "n"}
     of the model on `nodes`, the same dict on every rank.  labels_own: int [n_own], the labels of the rank's own nodes in
     ascending node order.  Each rank scores its own nodes among `nodes`; the per-rank (correct, float64 loss sum, n) are
-    all-gathered and added in rank order, so the result is reproducible bit for bit."""
+    all-gathered and added in rank order, so the result is reproducible bit for bit.
+    multilabel=True: labels_own are the packed words int32 [n_own, ceil(C / 32)]; the per-rank (tp, fp, fn, float64 loss
+    sum, n) are gathered and added the same way, the result is multilabel_scores'."""
     nodes = _node_ids(nodes)
     lab = torch.as_tensor(labels_own)
 
     def check(n_own):
-        if lab.dim() != 1 or lab.shape[0] != n_own:
+        if multilabel:
+            if lab.dim() != 2 or lab.shape[0] != n_own or lab.dtype != torch.int32:
+                raise ValueError("multilabel=True: labels_own must be the packed int32 words of the rank's own nodes "
+                                 "([%d, W])" % n_own)
+        elif lab.dim() != 1 or lab.shape[0] != n_own:
             raise ValueError("labels_own must hold one label per own node of the rank ([%d])" % n_own)
     logits = full_inference_parts(model, indptr, indices, features_own, comm, owner=owner, nodes=nodes,
                                   chunk_rows=chunk_rows, _check=check, _zero_padded=_zero_padded)
@@ -1023,6 +1071,13 @@ def evaluate_parts(model, indptr, indices, features_own, comm, nodes, labels_own
     rg = rank_graph(indptr, indices, owner_table(N, comm.world, owner), comm.world, comm.rank)
     mine = nodes[rg.owner[nodes] == comm.rank] if nodes.size else nodes
     rows = torch.from_numpy(rg.lrow[mine].astype(np.int64)).to(lab.device)
+    if multilabel:
+        _, (tp, fp, fn), loss = eval_head_multilabel(logits, lab[rows])
+        got = _gather(comm, [tp, fp, fn, int(np.float64(loss).view(np.int64)), int(mine.shape[0])])
+        t = [0, 0, 0, 0.0, 0]
+        for a, b, c, l, n in got:
+            t = [t[0] + a, t[1] + b, t[2] + c, t[3] + float(np.int64(l).view(np.float64)), t[4] + n]
+        return multilabel_scores(t[0], t[1], t[2], t[3], t[4], int(logits.shape[1]))
     _, correct, loss = eval_head(logits, lab[rows].to(logits.device))
     got = _gather(comm, [correct, int(np.float64(loss).view(np.int64)), int(mine.shape[0])])
     tc, tl, tn = 0, 0.0, 0

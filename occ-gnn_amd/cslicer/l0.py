@@ -13,7 +13,10 @@ reader cslicer/dataset.cpp:18-113):
     <dir>/features.bin        float32[N*feature_dim]   (unused by the slicer);
                               float16 / bfloat16 (raw 16-bit words) when
                               meta.txt says so
-    <dir>/labels.bin          int32[N]                 (unused by the slicer)
+    <dir>/labels.bin          int32[N]                 (unused by the slicer);
+                              multi-label (meta.txt: multilabel=1): the
+                              packed words int32[N, ceil(num_classes / 32)],
+                              class c = bit c % 32 of word c / 32
     <dir>/partition_map_opt.bin int32[N]               (loaded, ignored: the
                               reference uses v % 4, cslicer/pyfrontend.cpp:57)
     <dir>/train_idx.bin       int64[...]  optional training / evaluation node
@@ -158,6 +161,40 @@ def read_features(path, meta=None, mmap=True):
     return np.fromfile(f, dtype=dt, count=shape[0] * shape[1]).reshape(shape), meta["feature_dtype"]
 
 
+def label_words(num_classes):
+    """W = ceil(C / 32): the 32-bit words of a node's packed multi-label row"""
+    return (int(num_classes) + 31) // 32
+
+
+def pack_labels(y):
+    """[n, C] of 0 / 1 (bool or integer) -> int32 [n, ceil(C / 32)]: class c is bit c % 32 of word c / 32, the bits at and
+    above C of the last word zero (include/cslicer_multilabel.h).  Any other value is a ValueError."""
+    y = np.asarray(y)
+    if y.ndim != 2 or y.shape[1] < 1:
+        raise ValueError("pack_labels: a matrix [n, C] with C >= 1 expected, not shape %r" % (y.shape,))
+    if y.dtype != np.bool_:
+        if y.dtype.kind not in "iu":
+            raise ValueError("pack_labels: bool or integer labels expected, not %s" % y.dtype)
+        if y.size and not np.isin(y, (0, 1)).all():
+            raise ValueError("pack_labels: every label must be 0 or 1")
+    n, C = y.shape
+    W = label_words(C)
+    bits = np.zeros((n, W * 32), dtype=np.uint8)
+    bits[:, :C] = y != 0
+    # (bitorder little: column c lands in bit c % 8 of byte c / 8, i.e. bit c % 32 of the little-endian word c / 32)
+    return np.ascontiguousarray(np.packbits(bits, axis=1, bitorder="little")).view("<u4").astype(np.uint32).view(np.int32)
+
+
+def unpack_labels(words, num_classes):
+    """int32 (or uint32) [n, ceil(C / 32)] -> bool [n, C]; bits at and above C are not looked at"""
+    w = np.ascontiguousarray(words)
+    C = int(num_classes)
+    if w.ndim != 2 or w.dtype.kind not in "iu" or w.dtype.itemsize != 4 or C < 1 or w.shape[1] != label_words(C):
+        raise ValueError("unpack_labels: 32-bit words [n, %d] expected for %d classes" % (label_words(max(C, 1)), C))
+    by = w.view(np.uint32).astype("<u4").view(np.uint8).reshape(w.shape[0], -1)
+    return np.unpackbits(by, axis=1, bitorder="little")[:, :C].astype(np.bool_)
+
+
 def write_l0(path, indptr, indices, features=None, labels=None, partition=None,
              feature_dim=None, num_classes=2, train_idx=None, val_idx=None, feature_dtype=None):
     """Write an L0 dataset directory readable by the reference's Dataset class.  train_idx / val_idx (both or
@@ -181,7 +218,16 @@ def write_l0(path, indptr, indices, features=None, labels=None, partition=None,
     features = np.ascontiguousarray(features, dtype=np.float32).reshape(n, -1)
     if labels is None:
         labels = np.zeros(n, dtype=np.int32)
-    labels = np.ascontiguousarray(labels, dtype=np.int32)
+    multilabel = np.ndim(labels) == 2
+    if multilabel:
+        if np.shape(labels) != (n, int(num_classes)):
+            raise ValueError("write_l0: multi-label labels must be [%d, num_classes = %d], not %r"
+                             % (n, int(num_classes), np.shape(labels)))
+        labels = pack_labels(labels).astype("<i4")
+        lsum = int(labels.view(np.uint32).sum(dtype=np.int64))
+    else:
+        labels = np.ascontiguousarray(labels, dtype=np.int32)
+        lsum = int(labels.sum(dtype=np.int64))
     if partition is None:
         partition = (np.arange(n) % 4).astype(np.int32)
     partition = np.ascontiguousarray(partition, dtype=np.int32)
@@ -206,7 +252,7 @@ def write_l0(path, indptr, indices, features=None, labels=None, partition=None,
         "num_edges": int(indices.shape[0]),
         "feature_dim": int(features.shape[1]),
         "csum_features": int(fsum),
-        "csum_labels": int(labels.sum(dtype=np.int64)),
+        "csum_labels": lsum,
     }
     if train_idx is not None:
         train_idx = np.ascontiguousarray(train_idx, dtype=np.int64)
@@ -228,7 +274,11 @@ def write_l0(path, indptr, indices, features=None, labels=None, partition=None,
             f.write("%s=%d\n" % (k, v))
         if feature_dtype is not None:
             f.write("feature_dtype=%s\n" % feature_dtype)
+        if multilabel:
+            f.write("multilabel=1\n")
     meta["feature_dtype"] = feature_dtype or "float32"
+    if multilabel:
+        meta["multilabel"] = 1
     return meta
 
 
@@ -248,8 +298,27 @@ def read_meta(path):
     return meta
 
 
+def read_labels(path, meta=None, mmap=True):
+    """labels.bin of an L0 directory: int32 [N], or for a multi-label directory (meta.txt: multilabel=1) the packed words
+    int32 [N, ceil(num_classes / 32)] (unpack_labels)."""
+    meta = read_meta(path) if meta is None else meta
+    n = meta["num_nodes"]
+    shape = (n, label_words(meta["num_classes"])) if meta.get("multilabel") else (n,)
+    f = os.path.join(path, "labels.bin")
+    if mmap:
+        return np.memmap(f, dtype="<i4", mode="r", shape=shape)
+    return np.fromfile(f, dtype="<i4", count=int(np.prod(shape))).reshape(shape)
+
+
+def labels_checksum(labels, multilabel):
+    """csum_labels of meta.txt: the int64 sum of the labels, of a multi-label file's words read as unsigned"""
+    a = np.asarray(labels)
+    return int((a.view(np.uint32) if multilabel else a).sum(dtype=np.int64))
+
+
 def read_l0(path, mmap=True, check=True):
-    """Read the graph part of an L0 directory. Returns (indptr, indices, meta)."""
+    """Read the graph part of an L0 directory. Returns (indptr, indices, meta).  check: the checksums of indptr.bin,
+    indices.bin and (where the file and its csum_labels are there) labels.bin, in either label format."""
     meta = read_meta(path)
     n, e = meta["num_nodes"], meta["num_edges"]
     if mmap:
@@ -265,6 +334,14 @@ def read_l0(path, mmap=True, check=True):
             raise ValueError("indptr checksum mismatch in %s" % path)
         if int(np.sum(indices, dtype=np.int64)) != meta["csum_edges"]:
             raise ValueError("indices checksum mismatch in %s" % path)
+        lf = os.path.join(path, "labels.bin")
+        if "csum_labels" in meta and os.path.exists(lf):
+            multi = bool(meta.get("multilabel"))
+            want = (n * label_words(meta["num_classes"]) if multi else n) * 4
+            if os.path.getsize(lf) != want:
+                raise ValueError("labels.bin of %s holds %d bytes, %d expected" % (path, os.path.getsize(lf), want))
+            if labels_checksum(read_labels(path, meta), multi) != meta["csum_labels"]:
+                raise ValueError("labels checksum mismatch in %s" % path)
     return indptr, indices, meta
 
 

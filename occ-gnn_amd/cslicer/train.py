@@ -69,7 +69,7 @@ def gat_input_obstacle(kind, world, rank_path, n_layers, F, hidden, n_classes, h
 
 
 def step_plan(kind, world, rank_path, n_layers, F, hidden, n_classes, heads, fanout, table_f32, gat_input, replace,
-              sw=Switches(), width_known=True, dropout=0.0):
+              sw=Switches(), width_known=True, dropout=0.0, multilabel=False):
     """The StepPlan of a configuration, from plain values only (no device, no engine): every rule is written here once.
     ONE function, called when the rank's host rows are in hand -- F is the loaded table's width (feat_dim where given),
     which the path depends on -- so the constructor creates its engine after the host-side loading.
@@ -77,7 +77,8 @@ def step_plan(kind, world, rank_path, n_layers, F, hidden, n_classes, heads, fan
     float32; gat_input: the constructor's None / True / False; width_known: whether F was known before the rows were
     loaded (feat_dim, or the shape of a feature matrix; False: callable features without feat_dim); dropout: the
     trainer's probability -- above 0 the rank path runs its autograd step (the native rank sequencer has no dropout), with
-    the engine flags that step has always asked for; every other row is what it is at 0."""
+    the engine flags that step has always asked for; every other row is what it is at 0.  multilabel: the trainer's --
+    the native rank sequencer has no sigmoid-BCE loss either, so with True its row moves the same way and no other does."""
     sage, gat = kind == "sage", kind == "gat"
     single = not rank_path and world == 1      # one part in one process, no collective
     want = table_f32 if gat_input is None else gat_input     # (None: a 16-bit table keeps the numbers its runs have had)
@@ -89,8 +90,9 @@ def step_plan(kind, world, rank_path, n_layers, F, hidden, n_classes, heads, fan
     # the single part with every layer as one fused node, the deepest reading the resident table through in_nodes
     local = single and sage and F % 4 == 0 and not sw.no_local_fuse
     native_rank = rank_path and sage and F % 4 == 0 and hidden % 4 == 0 and n_classes <= 256 and not sw.py_step
-    if native_rank and dropout > 0:
-        # the native rank sequencer has no dropout: the rank's autograd step, planned as CSLICER_PY_STEP plans it
+    if native_rank and (dropout > 0 or multilabel):
+        # the native rank sequencer has no dropout and no multi-label loss: the rank's autograd step, planned as
+        # CSLICER_PY_STEP plans it
         return step_plan(kind, world, rank_path, n_layers, F, hidden, n_classes, heads, fanout, table_f32, gat_input,
                          replace, sw._replace(py_step=True), width_known)
 
@@ -131,7 +133,8 @@ class Trainer(object):
     def __init__(self, indptr, indices, features, labels, n_classes, rank=0, world=1, fanouts=(15, 10, 5),
                  batch=1024, streams=8, hidden=256, lr=1e-3, device=0, dist=None, seed=0, overlap=False,
                  model="sage", heads=8, rank_path=None, workload=None, feat_dim=None, rng_seed=5489,
-                 feature_dtype="float32", gat_input=None, replace=True, dropout=0.0, dropout_seed=None):
+                 feature_dtype="float32", gat_input=None, replace=True, dropout=0.0, dropout_seed=None,
+                 multilabel=False):
         """Part `rank` of `world`.  Ownership = the engine's workload table (`workload` int32 [N], the METIS map of
         python/utils/sampler.py:64-134 / partition_map_opt.bin; None = v % world like pyfrontend.cpp:57): the rank
         keeps the feature and label rows of the nodes it owns, in ascending node order.
@@ -168,9 +171,32 @@ class Trainer(object):
         across epochs and is the same on one GPU and on any number of ranks; dropout_seed=None takes `seed`.  0 (default)
         runs no dropout code at all; evaluate() / predict() never drop (inverted scaling makes inference the identity).
 
+        multilabel: False (default): one class per node, `labels` int [N], softmax cross-entropy.  True: a node carries a
+        SET of classes (PPI, ogbn-proteins, Yelp, Amazon): `labels` is a host array [N, n_classes] of 0 / 1 (bool or
+        integer), or a callable returning the rank's [n_own, n_classes] rows; they are packed on the host
+        (aggr.pack_labels: 32 classes per int32 word) and `self.labels` is the int32 [n_own, ceil(n_classes / 32)] device
+        tensor.  The loss is the mean binary cross-entropy with logits over the minibatch's seeds x classes
+        (torch.nn.BCEWithLogitsLoss()): one fused HIP pass, inside the native step (csl_sage_fwd_bwd_multilabel) or as
+        aggr.SigmoidBCE on the autograd paths, both models; on the rank path the autograd step runs (the native rank
+        sequencer has no multi-label loss).  evaluate() then reports micro-F1.  Dropout, a 16-bit table and
+        replace=False combine with it unchanged.
+
         `self.plan` is the StepPlan of the configuration (step_plan above): which step the trainer runs, decided here
         once; `self.native` / `self.native_rank` are the native stepper of that path, None on every other path."""
         # -- 1. the arguments (before any device call: a request that cannot be served is an error, never a quiet fall-back)
+        self.multilabel, self.n_classes = bool(multilabel), int(n_classes)
+        if not callable(labels):
+            shape = np.shape(labels)
+            if self.multilabel and len(shape) != 2:
+                raise ValueError("multilabel=True: labels must be a matrix [num_nodes, n_classes] of 0 / 1, not shape %r"
+                                 % (shape,))
+            if self.multilabel and shape != (indptr.shape[0] - 1, n_classes):
+                raise ValueError("multilabel=True: labels must be [num_nodes = %d, n_classes = %d], not %r"
+                                 % (indptr.shape[0] - 1, n_classes, shape))
+            if self.multilabel:
+                la = np.asarray(labels)
+                if la.dtype != np.bool_ and (la.dtype.kind not in "iu" or (la.size and not np.isin(la, (0, 1)).all())):
+                    raise ValueError("multilabel=True: every label must be 0 or 1 (bool or integer)")
         dropout = float(dropout)
         if not 0.0 <= dropout < 1.0:
             raise ValueError("dropout must be in [0, 1), not %r" % (dropout,))
@@ -228,8 +254,14 @@ class Trainer(object):
             raise ValueError("features: a float32, float16 or bfloat16 matrix expected")
         # converted on the HOST (round to nearest even), so that the device only ever holds the table in its stored type
         f_own = f_own.to(fdt).contiguous()
-        l_own = np.ascontiguousarray((labels(own) if callable(labels) else (labels[own] if self.P > 1 else labels)),
-                                     dtype=np.int64)
+        l_own = labels(own) if callable(labels) else (labels[own] if self.P > 1 else labels)
+        if self.multilabel:
+            if np.shape(l_own) != (self.n_own, n_classes):
+                raise ValueError("multilabel=True: the rank's label rows must be [%d, %d], not %r"
+                                 % (self.n_own, n_classes, np.shape(l_own)))
+            l_own = aggr.pack_labels(l_own)          # (ValueError for anything but 0 / 1)
+        else:
+            l_own = np.ascontiguousarray(l_own, dtype=np.int64)
         if f_own.shape[0] != self.n_own or l_own.shape[0] != self.n_own:
             raise ValueError("features / labels do not cover the rank's %d nodes" % self.n_own)
         F = f_own.shape[1] if feat_dim is None else feat_dim
@@ -237,7 +269,7 @@ class Trainer(object):
         # materialised (the sampling itself is replicated)
         self.plan = step_plan(model, world, self.rank_path, self.L, F, hidden, n_classes, heads, fanouts[-1],
                               fdt == torch.float32, gat_input, replace, sw, width_known=F_early is not None,
-                              dropout=dropout)
+                              dropout=dropout, multilabel=self.multilabel)
         self.gat_input, self.replace = self.plan.gat_input, bool(replace)
         self.eng = _abi.Engine(indptr, indices, n_parts=self.P, fanouts=fanouts, max_batch=batch,
                                n_streams=streams, n_slots=self.SLOTS, device=device, mode=_abi.MODE_GRAPH,
@@ -327,6 +359,11 @@ class Trainer(object):
         """the DropSpec of the step about to run (its counter: the steps done so far), None without dropout"""
         return aggr.DropSpec(self.dropout, self.dropout_seed, self.steps_done) if self.dropout > 0 else None
 
+    def _scale(self, den):
+        """what the summed loss is multiplied by: 1 / seeds, and for the multi-label loss 1 / (seeds * classes), the
+        mean over elements"""
+        return 1.0 / (den * self.n_classes) if self.multilabel else 1.0 / den
+
     def _next_loss(self):
         """the loss ring's next element (run() sized the ring for its steps)"""
         loss = self._loss_ring[self._ring_at:self._ring_at + 1]
@@ -341,7 +378,7 @@ class Trainer(object):
         # forward, loss, backward: one native call; the optimizer: a second one on the flat gradient buffer
         _roctx.push("step_native")
         loss = self._next_loss()
-        self.native(layers, self.feat, self.labels, 1.0 / self._loss_den(stream, slot, n_seeds), loss, self._drop())
+        self.native(layers, self.feat, self.labels, self._scale(self._loss_den(stream, slot, n_seeds)), loss, self._drop())
         if self.grad_sync is not None:
             self.grad_sync(self.native.grads)             # (data-parallel: sum over the ranks' shares of the minibatch)
         self.opt.step(flat_grads=self.native.grads)
@@ -366,7 +403,8 @@ class Trainer(object):
         t1 = time.perf_counter()
         _roctx.push("forward")
         logits = self.model.forward_local(slices, self.feat, drop=self._drop())
-        loss = aggr.SoftmaxCE.apply(logits, layers[-1].out_nodes, self.labels, 1.0 / max(n_seeds, 1))
+        loss_fn = aggr.SigmoidBCE if self.multilabel else aggr.SoftmaxCE
+        loss = loss_fn.apply(logits, layers[-1].out_nodes, self.labels, self._scale(max(n_seeds, 1)))
         _roctx.pop()
         self.t_forward += time.perf_counter() - t1
         return self._backward_and_update(loss)
@@ -396,7 +434,10 @@ class Trainer(object):
         top = layers[-1]
         seeds = top.out_nodes[top.owned_out_nodes.long()]  # the seeds this rank owns, frontier order
         # mean over the WHOLE minibatch: sum of local losses / global seed count
-        if self.kind == "sage" and logits.shape[0] > 0:
+        if self.multilabel:
+            den = max(n_seeds, 1) if self.rank_path else self._loss_den(stream, slot, n_seeds)   # (data-parallel: global)
+            loss = aggr.SigmoidBCE.apply(logits, seeds, self.labels, self._scale(den), self.local_row)
+        elif self.kind == "sage" and logits.shape[0] > 0:
             loss = aggr.SoftmaxCE.apply(logits, seeds, self.labels, 1.0 / max(n_seeds, 1), self.local_row)
         else:
             seeds = seeds.long()
@@ -579,9 +620,12 @@ class Trainer(object):
     def evaluate(self, nodes, chunk_rows=None):
         """{"accuracy", "loss", "n"} of the current weights on `nodes` (argmax accuracy, mean cross-entropy against the
         trainer's labels) by full-neighbour inference; see predict().  Rank path: collective, the same dict on every
-        rank (cslicer.infer.evaluate_parts)."""
+        rank (cslicer.infer.evaluate_parts).  A multi-label trainer: {"micro_f1", "loss", "n", "tp", "fp", "fn"}
+        (micro-F1 of logits > 0, mean binary cross-entropy per element)."""
         from . import infer
         args, kw = self._infer_args(), self._infer_kw(nodes, chunk_rows)
+        if self.multilabel:
+            kw["multilabel"] = True
         if self.rank_path:
             del kw["nodes"]
             return infer.evaluate_parts(*args, self.comm, nodes, self.labels, owner=self.owner, **kw)
@@ -678,6 +722,18 @@ def synthetic_node_data(num_nodes, feat_dim, n_classes, seed=0, rows=None):
     return feats, labels
 
 
+def synthetic_multilabels(num_nodes, n_classes, seed=0, rows=None, feat_dim=128):
+    """bool [len(rows) (or num_nodes), n_classes]: multi-label targets for synthetic_node_data's features of width
+    `feat_dim` under the same seed.  Class c of node v is x[v, a] + x[v, b] - x[v, d] > 0.5 for three columns (a, b, d)
+    fixed by c: a half-space of the node's OWN feature row (so a model can learn it), true for half of the nodes.  The
+    features are hashes of (seed, node id, column), hence so are these: `rows` yields exactly the rows of the full
+    matrix, and a rank generates only the nodes it owns."""
+    x = synthetic_node_data(num_nodes, feat_dim, 1, seed=seed, rows=rows)[0]
+    c = np.arange(n_classes)
+    a, b, d = c % feat_dim, (3 * c + 1) % feat_dim, (5 * c + 2) % feat_dim
+    return (x[:, a] + x[:, b] - x[:, d]) > np.float32(0.5)
+
+
 def _parser():
     import argparse
     ap = argparse.ArgumentParser("split-parallel training on MI355X")
@@ -715,6 +771,9 @@ def _parser():
     ap.add_argument("--no-replace", action="store_true",
                     help="(extra) sample rows with at least fan-out edges WITHOUT replacement (`Trainer(replace=False)`), "
                          "as dgl.sampling.sample_neighbors does by default; every fan-out must be <= 64")
+    ap.add_argument("--multilabel", action="store_true",
+                    help="(extra) multi-label classification (`Trainer(multilabel=True)`): sigmoid + binary cross-entropy "
+                         "over n_classes targets per node, evaluation by micro-F1; an L0 directory must say multilabel=1")
     return ap
 
 
@@ -762,7 +821,12 @@ def main(argv=None):
     --no-replace (extra): `Trainer(replace=False)`: a row with at least fan-out edges yields that many DISTINCT edges
     (the default of dgl.sampling.sample_neighbors) instead of independent draws.  Every --fan-out number must then be
     <= 64 (_abi.noreplace_max_fanout()).
+    --multilabel (extra): `Trainer(multilabel=True)`: a node carries a set of classes; the loss is the mean binary
+    cross-entropy with logits and rank 0 prints `Eval F1` (micro-F1) where it prints `Eval Acc`.  `synthetic` and the
+    presets train on synthetic_multilabels; an L0 directory must hold packed multi-label words (multilabel=1 in its
+    meta.txt, cslicer.l0.write_l0 with a 2-D `labels`).
 
+        python -m cslicer.train --graph products-like --multilabel --eval-split holdout --max-steps 50
         python -m cslicer.train --graph <L0 dir> --feature-dtype bfloat16 --eval-split holdout
         python -m cslicer.train --graph products-like --model-name gat --feature-dtype bfloat16 --gat-input on"""
     a = _parser().parse_args(argv)
@@ -789,6 +853,8 @@ def main(argv=None):
         # every rank generates only the rows of the nodes it owns
         feats = lambda own: synthetic_node_data(n, fdim, n_classes, seed=0, rows=own)[0]    # noqa: E731
         labels = lambda own: synthetic_node_data(n, 1, n_classes, seed=0, rows=own)[1]      # noqa: E731
+        if a.multilabel:
+            labels = lambda own: synthetic_multilabels(n, n_classes, seed=0, rows=own, feat_dim=fdim)   # noqa: E731
         if a.partition == "file":
             raise SystemExit("--partition file needs an L0 directory")
     else:
@@ -796,7 +862,12 @@ def main(argv=None):
         n, fdim = meta["num_nodes"], meta["feature_dim"]
         # memory-mapped: a rank touches only the rows it owns
         fmap, stored = l0.read_features(a.graph, meta)          # (in the stored element type)
-        lmap = np.memmap(os.path.join(a.graph, "labels.bin"), dtype=np.int32, mode="r", shape=(n,))
+        if bool(meta.get("multilabel")) != bool(a.multilabel):
+            raise SystemExit("--multilabel needs an L0 directory whose meta.txt says multilabel=1 (%s does not)" % a.graph
+                             if a.multilabel else
+                             "%s is a multi-label directory (multilabel=1 in its meta.txt): pass --multilabel" % a.graph)
+        lmap = (l0.read_labels(a.graph, meta) if a.multilabel else
+                np.memmap(os.path.join(a.graph, "labels.bin"), dtype=np.int32, mode="r", shape=(n,)))
         if stored == "bfloat16":    # (numpy has no bfloat16: the rank's words become a torch.bfloat16 tensor)
             feats = lambda own: torch.from_numpy(np.asarray(fmap[own]).view(np.int16)).view(torch.bfloat16)   # noqa: E731
         else:
@@ -804,6 +875,8 @@ def main(argv=None):
         fdtype = a.feature_dtype or stored
         labels = lambda own: np.asarray(lmap[own]).astype(np.int64)                          # noqa: E731
         n_classes = meta["num_classes"]
+        if a.multilabel:
+            labels = lambda own: l0.unpack_labels(np.asarray(lmap[own]), n_classes)              # noqa: E731
         if a.partition == "file":
             workload = np.fromfile(os.path.join(a.graph, "partition_map_opt.bin"), dtype=np.int32)
     train_nodes, eval_nodes = _split(a, indptr.shape[0] - 1)
@@ -816,7 +889,7 @@ def main(argv=None):
                  streams=8, hidden=max(4, hidden // 4 * 4), lr=a.lr, device=local, dist=dist, model=kind, heads=a.num_heads,
                  workload=workload, feat_dim=fdim, feature_dtype=fdtype,
                  gat_input={"auto": None, "on": True, "off": False}[a.gat_input], replace=not a.no_replace,
-                 dropout=a.dropout)
+                 dropout=a.dropout, **({"multilabel": True} if a.multilabel else {}))
     if rank == 0 and fdtype != "float32":
         print("feature table: %s, %d bytes on this rank" % (fdtype, tr.feat.numel() * tr.feat.element_size()))
     n = indptr.shape[0] - 1
@@ -835,7 +908,10 @@ def main(argv=None):
             ev = tr.evaluate(eval_nodes)
             if rank == 0:
                 # the key of the reference's trainers (pa_cache_multi_gpu.py:252)
-                print("Eval Acc %.4f | loss %.4f | %d nodes in %.2f s" % (ev["accuracy"], ev["loss"], ev["n"], time.time() - t0))
+                if a.multilabel:
+                    print("Eval F1 %.4f | loss %.4f | %d nodes in %.2f s" % (ev["micro_f1"], ev["loss"], ev["n"], time.time() - t0))
+                else:
+                    print("Eval Acc %.4f | loss %.4f | %d nodes in %.2f s" % (ev["accuracy"], ev["loss"], ev["n"], time.time() - t0))
     if rank == 0:
         print(tr.report())
     tr.close()

@@ -29,6 +29,7 @@
 #include "cslicer_dropout.h"
 #include "cslicer_feat16.h"
 #include "cslicer_hip.h"
+#include "cslicer_multilabel.h"
 #include "dev_common.h"
 #include "feat_elem.h"
 #include "table_readers.h"
@@ -222,6 +223,12 @@ struct DropArgs {
   int64_t seed, step;
 };
 
+// the multi-label loss (csl_sage_fwd_bwd_multilabel, cslicer_multilabel.h): the packed label words in place of `labels`
+struct MultiArgs {
+  const int32_t* words;
+  int64_t ldw;
+};
+
 // gW_k = gy_k^T cat_k of either layout (Layout, RankLayout): nothing but a zero fill without rows, in row slabs whose sum
 // is deferred, or one plain GEMM.  group: the timing group of the GEMM (< 0: untimed)
 template <typename Lay>
@@ -272,12 +279,13 @@ int64_t csl_sage_fwd_bwd_workspace(int32_t n_layers, const int32_t* dims, const 
   return o.total;
 }
 
-// the step behind csl_sage_fwd_bwd_f32 (kind 0), csl_sage_fwd_bwd_x16 and, with `drop`, csl_sage_fwd_bwd_dropout
+// the step behind csl_sage_fwd_bwd_f32 (kind 0), csl_sage_fwd_bwd_x16, with `drop` csl_sage_fwd_bwd_dropout and, with
+// `multi` (sigmoid-BCE on packed labels where the others run the softmax cross-entropy), csl_sage_fwd_bwd_multilabel
 static int sage_fwd_bwd(int32_t n_layers, const int32_t* dims, const csl_sage_slice* sl, const float* const* weights,
                         const float* const* biases, const void* feat, int32_t kind, int64_t ldf, const int32_t* feat_rows,
                         const int32_t* seed_ids, const int64_t* labels, float scale, int64_t row_pad, int32_t n_slabs,
                         float* grads, float* loss, float* workspace, int64_t workspace_floats, void* stream,
-                        const DropArgs* drop = nullptr) {
+                        const DropArgs* drop = nullptr, const MultiArgs* multi = nullptr) {
   int k = -1;
   s_err[0] = 0;
   Layout o;
@@ -324,10 +332,18 @@ static int sage_fwd_bwd(int32_t n_layers, const int32_t* dims, const csl_sage_sl
     const int32_t C = dims[L];
     const int64_t m = sl[k].n_out;
     if (o.top_cols) {
+      if (multi)
+        TSTEP(CSL_STEP_OTHER, csl_sigmoid_bce_partial_f32(ws + o.y[k], C, m, o.mp[k], C, seed_ids, nullptr, multi->words, multi->ldw,
+                                                          scale, ws + o.gy[k], C, ws + o.lpart, ws + o.bpart[k], stream));
+      else
       TSTEP(CSL_STEP_OTHER, csl_softmax_ce_partial_f32(ws + o.y[k], C, m, o.mp[k], C, seed_ids, nullptr, labels, scale, ws + o.gy[k], C,
                                       ws + o.lpart, ws + o.bpart[k], stream));
       later.add(ws + o.bpart[k], o.bblocks[k], C, gs.gb[k]);
     } else {
+      if (multi)
+        TSTEP(CSL_STEP_OTHER, csl_sigmoid_bce_partial_f32(ws + o.y[k], C, m, m, C, seed_ids, nullptr, multi->words, multi->ldw, scale,
+                                                          ws + o.g, C, ws + o.lpart, nullptr, stream));
+      else
       TSTEP(CSL_STEP_OTHER, csl_softmax_ce_partial_f32(ws + o.y[k], C, m, m, C, seed_ids, nullptr, labels, scale, ws + o.g, C, ws + o.lpart,
                                       nullptr, stream));
       TSTEP(CSL_STEP_AGGREGATION, csl_relu_bwd_colsum_f32(ws + o.g, C, nullptr, 0, m, o.mp[k], ws + o.gy[k], C, gs.gb[k], ws + o.scratch, C, stream));
@@ -417,6 +433,30 @@ int csl_sage_fwd_bwd_dropout(int32_t n_layers, const int32_t* dims, const csl_sa
   const DropArgs drop = {out_ids, p, seed, step};
   return sage_fwd_bwd(n_layers, dims, sl, weights, biases, feat, kind, ldf, feat_rows, seed_ids, labels, scale, row_pad,
                       n_slabs, grads, loss, workspace, workspace_floats, stream, &drop);
+}
+
+int csl_sage_fwd_bwd_multilabel(int32_t n_layers, const int32_t* dims, const csl_sage_slice* sl, const float* const* weights,
+                                const float* const* biases, const void* feat, int32_t kind, int64_t ldf,
+                                const int32_t* feat_rows, const int32_t* seed_ids, const int32_t* label_words, int64_t ldw,
+                                float scale, int64_t row_pad, int32_t n_slabs, float* grads, float* loss, float* workspace,
+                                int64_t workspace_floats, const int32_t* const* out_ids, float p, int64_t seed, int64_t step,
+                                void* stream) {
+  if (kind != 0 && table16_refused(feat, kind, ldf)) return CSL_E_INVALID;
+  const bool plain = p == 0.f && !out_ids;
+  bool ok = n_layers >= 1 && n_layers <= CSL_MAX_LAYERS && sl && dims && label_words && dims[n_layers] >= 1 &&
+            dims[n_layers] <= 4096 && ldw >= (dims[n_layers] + 31) / 32 &&
+            (plain || (p > 0.f && p < 1.f && (n_layers == 1 || out_ids)));
+  for (int k = 0; ok && !plain && k + 1 < n_layers; k++) ok = sl[k].n_out <= 0 || out_ids[k];
+  if (!ok) {
+    snprintf(s_err, sizeof(s_err), "multilabel: packed label words of at least ceil(C / 32) per row, 1 <= C <= 4096, and "
+             "either p == 0 without out-node ids or 0 < p < 1 with those of every layer but the last expected (p = %g)",
+             (double)p);
+    return CSL_E_INVALID;
+  }
+  const DropArgs drop = {out_ids, p, seed, step};
+  const MultiArgs multi = {label_words, ldw};
+  return sage_fwd_bwd(n_layers, dims, sl, weights, biases, feat, kind, ldf, feat_rows, seed_ids, nullptr, scale, row_pad,
+                      n_slabs, grads, loss, workspace, workspace_floats, stream, plain ? nullptr : &drop, &multi);
 }
 
 }  // extern "C"
