@@ -180,7 +180,8 @@ typedef struct {
    * reorder() does not deduplicate.  Equals len(out_nodes) unless the minibatch repeats a seed id (layer 0).
    * graph mode: len(out_nodes) + 1 when the layer is not empty (the CSR row pointers). */
   uint32_t indptr_len[CSL_MAX_PARTS];
-  /* CSL_FLAG_TRANSPOSE: length of the longest list of slice g by source (0 without the flag) */
+  /* CSL_FLAG_TRANSPOSE: length of the longest list of slice g by source (0 without the flag, and for a part that
+   * csl_config.part_mask leaves out: its slice by source is not built) */
   uint32_t t_max_len[CSL_MAX_PARTS];
 } csl_layer_meta;
 

@@ -38,8 +38,10 @@ def assert_same_graph(got, want, what=""):
         np.testing.assert_array_equal(a, b, err_msg="%s frontier[%d]" % (what, l))
 
 
-def check_graph_invariants(d, indptr, indices, P):
-    """Every edge of the slice CSRs is a real edge of the input graph, boundary lists pair up."""
+def check_graph_invariants(d, indptr, indices, P, workload=None):
+    """Every edge of the slice CSRs is a real edge of the input graph, boundary lists pair up.  Owners are v % P, or
+    the workload table the engine was given."""
+    owner = (lambda v: np.asarray(v) % P) if workload is None else (lambda v: np.asarray(workload)[np.asarray(v)])
     for l, parts in enumerate(d["layers"]):
         fr = d["frontier"][l]
         edges = 0
@@ -51,13 +53,13 @@ def check_graph_invariants(d, indptr, indices, P):
             edges += len(ix)
             src = bp["in_nodes"][ix]
             dst = np.repeat(bp["out_nodes"], np.diff(ip))
-            assert (src % P == g).all()
+            assert (owner(src) == g).all()
             for k in range(0, len(src), max(1, len(src) // 200)):   # spot-check real adjacency
                 row = indices[indptr[dst[k]]:indptr[dst[k] + 1]]
                 assert src[k] in row
             own = bp["owned_out_nodes"]
-            np.testing.assert_array_equal(bp["out_nodes"][own], fr[fr % P == g])
-            np.testing.assert_array_equal(bp["in_nodes"][bp["self_ids_in"]], fr[fr % P == g])
+            np.testing.assert_array_equal(bp["out_nodes"][own], fr[owner(fr) == g])
+            np.testing.assert_array_equal(bp["in_nodes"][bp["self_ids_in"]], fr[owner(fr) == g])
             np.testing.assert_array_equal(bp["self_ids_out"], own)
         for g in range(P):
             for p in range(P):
@@ -67,7 +69,7 @@ def check_graph_invariants(d, indptr, indices, P):
                     assert len(a) == 0
                     continue
                 np.testing.assert_array_equal(parts[g]["out_nodes"][a], parts[p]["out_nodes"][b])
-                assert (parts[g]["out_nodes"][a] % P == p).all()
+                assert (owner(parts[g]["out_nodes"][a]) == p).all()
         # total degree of owned nodes == all edges of the layer
         assert sum(int(bp["owned_degree"].sum()) for bp in parts) == edges
 
@@ -76,6 +78,7 @@ def check_transposed(d, deepest_too=False):
     """FLAG_TRANSPOSE: t_indptr / t_indices of every layer but the deepest (FLAG_TRANSPOSE_ALL: of every layer) are the
     slice CSR + self lists sorted by source (cslicer_hip.h, CSL_T_INDPTR): per in node ~r of its self entry, then the
     out rows of its edges ascending."""
+    from cslicer import _abi
     L = len(d["layers"])
     for l, parts in enumerate(d["layers"]):
         for g, bp in enumerate(parts):
@@ -93,7 +96,7 @@ def check_transposed(d, deepest_too=False):
             want_ptr = np.concatenate([[0], np.cumsum(np.bincount(u, minlength=n_in))])
             np.testing.assert_array_equal(bp["t_indptr"], want_ptr, err_msg=tag + "t_indptr")
             got_idx, lens = bp["t_indices"].copy(), np.diff(want_ptr)
-            for u in np.flatnonzero(lens > 128):         # a hub's list (> CSL_T_SORTED_MAX) comes in unspecified order
+            for u in np.flatnonzero(lens > _abi.T_SORTED_MAX):   # a hub's list comes in unspecified order
                 got_idx[want_ptr[u]:want_ptr[u + 1]] = np.sort(got_idx[want_ptr[u]:want_ptr[u + 1]])
             np.testing.assert_array_equal(got_idx, val[order], err_msg=tag + "t_indices")
             assert bp["t_max_len"] == (int(lens.max()) if len(lens) else 0), tag
