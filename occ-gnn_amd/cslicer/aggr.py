@@ -460,6 +460,16 @@ class _SageNative(object):
         self._twins, self._need = _twins(self._stem), getattr(_lib(), self._workspace)
         gemm_load_plans()
 
+    @staticmethod
+    def _fill(c, s, by_source):
+        """the fields csl_sage_slice and csl_sage_rank_slice share, from a `splitgnn.Slice`; by_source: whether the step
+        counts the slice by source as present (else those four fields are empty)"""
+        A = _abi
+        c.indptr, c.indices, c.self_ids_in = s.ptr(A.INDPTR), s.ptr(A.INDICES), s.ptr(A.SELF_IDS_IN)
+        c.n_out, c.n_in = s.n_out, s.n_in
+        c.t_indptr, c.t_indices, c.t_max_len, c.t_entries = \
+            (s.ptr(A.T_INDPTR), s.ptr(A.T_INDICES), s.t_max_len, s.count(A.T_INDICES)) if by_source else (None, None, 0, 0)
+
     def _grow(self, device):
         """self._ws: at least the floats the slices in self._sl need"""
         need = self._need(self.L, self._dims, self._sl, self.row_pad, self.n_slabs)
@@ -491,44 +501,33 @@ class SageStep(_SageNative):
         with the DropSpec if there is one."""
         A = _abi
         for k, s in enumerate(slices):
-            c = self._sl[k]
-            c.indptr, c.indices, c.self_ids_in = s.ptr(A.INDPTR), s.ptr(A.INDICES), s.ptr(A.SELF_IDS_IN)
             # (an EMPTY layer -- a rank's empty share of a short minibatch -- has no row pointers at all)
             if k and s.count(A.T_INDPTR) != s.n_in + 1 and (s.n_in or s.n_out or s.count(A.T_INDPTR)):
                 raise ValueError("layer %d has no slice by source: create the engine with flags=FLAG_TRANSPOSE" % k)
-            c.t_indptr, c.t_indices = (s.ptr(A.T_INDPTR), s.ptr(A.T_INDICES)) if k else (None, None)
-            c.n_out, c.n_in, c.t_max_len = s.n_out, s.n_in, s.t_max_len
-            c.t_entries = s.count(A.T_INDICES) if k else 0
+            self._fill(self._sl[k], s, k > 0)
         self._grow(feat.device)
-        if labels.dim() == 2:
-            if labels.dtype != torch.int32 or not labels.is_cuda or labels.stride(1) != 1 \
-                    or labels.shape[1] != label_words(self.dims[-1]):
-                raise TypeError("multi-label labels: an int32 CUDA matrix [N, %d] of packed words (pack_labels) expected"
-                                % label_words(self.dims[-1]))
-            ids = None
-            if drop is not None:
-                ids = (C.c_void_p * max(self.L - 1, 1))(*[s.ptr(A.OUT_NODES) for s in slices[:self.L - 1]])
-            fn = _lib().csl_sage_fwd_bwd_multilabel
-            self._chk(fn(self.L, self._dims, self._sl, self._w, self._b, feat.data_ptr(), _table(feat) or 0, feat.stride(0),
-                         slices[0].ptr(A.IN_NODES), slices[-1].ptr(A.OUT_NODES), labels.data_ptr(), labels.stride(0),
-                         float(scale), self.row_pad, self.n_slabs, self.grads.data_ptr(), loss_out.data_ptr(),
-                         self._ws.data_ptr(), self._ws.numel(), ids, float(drop.p) if drop is not None else 0.0,
-                         _i64(drop.seed) if drop is not None else 0, _i64(drop.step) if drop is not None else 0, _stream()),
-                      fn.__name__)
+        multi = labels.dim() == 2
+        if multi and (labels.dtype != torch.int32 or not labels.is_cuda or labels.stride(1) != 1
+                      or labels.shape[1] != label_words(self.dims[-1])):
+            raise TypeError("multi-label labels: an int32 CUDA matrix [N, %d] of packed words (pack_labels) expected"
+                            % label_words(self.dims[-1]))
+        # what every entry point takes, from n_layers to workspace_floats: the table's kind goes after its pointer, the
+        # multi-label step takes the packed words with their row stride where the others take the labels
+        kind = _table(feat)
+        upto_table = (self.L, self._dims, self._sl, self._w, self._b, feat.data_ptr())
+        rest = (feat.stride(0), slices[0].ptr(A.IN_NODES), slices[-1].ptr(A.OUT_NODES), labels.data_ptr(),
+                *((labels.stride(0),) if multi else ()), float(scale), self.row_pad, self.n_slabs, self.grads.data_ptr(),
+                loss_out.data_ptr(), self._ws.data_ptr(), self._ws.numel())
+        if not multi and drop is None:
+            # a 16-bit table (float16 / bfloat16) goes to the step's _x16 twin: only its deepest layer's forward differs
+            _table_call(self._twins, kind, upto_table, rest + (_stream(),), self._chk)
             return
+        dropped = (None, 0.0, 0, 0)
         if drop is not None:
             ids = (C.c_void_p * max(self.L - 1, 1))(*[s.ptr(A.OUT_NODES) for s in slices[:self.L - 1]])
-            fn = _lib().csl_sage_fwd_bwd_dropout
-            self._chk(fn(self.L, self._dims, self._sl, self._w, self._b, feat.data_ptr(), _table(feat) or 0, feat.stride(0),
-                         slices[0].ptr(A.IN_NODES), slices[-1].ptr(A.OUT_NODES), labels.data_ptr(), float(scale),
-                         self.row_pad, self.n_slabs, self.grads.data_ptr(), loss_out.data_ptr(), self._ws.data_ptr(),
-                         self._ws.numel(), ids, float(drop.p), _i64(drop.seed), _i64(drop.step), _stream()), fn.__name__)
-            return
-        # a 16-bit table (float16 / bfloat16) goes to the step's _x16 twin: only its deepest layer's forward differs
-        _table_call(self._twins, _table(feat), (self.L, self._dims, self._sl, self._w, self._b, feat.data_ptr()),
-                    (feat.stride(0), slices[0].ptr(A.IN_NODES), slices[-1].ptr(A.OUT_NODES), labels.data_ptr(),
-                     float(scale), self.row_pad, self.n_slabs, self.grads.data_ptr(), loss_out.data_ptr(),
-                     self._ws.data_ptr(), self._ws.numel(), _stream()), self._chk)
+            dropped = (ids, float(drop.p), _i64(drop.seed), _i64(drop.step))
+        fn = _lib().csl_sage_fwd_bwd_multilabel if multi else _lib().csl_sage_fwd_bwd_dropout
+        self._chk(fn(*upto_table, kind or 0, *rest, *dropped, _stream()), fn.__name__)
 
 
 class SageRankSlice(C.Structure):
@@ -614,17 +613,11 @@ class SageRankStep(_SageNative):
         A = _abi
         for k, s in enumerate(slices):
             c = self._sl[k]
-            c.indptr, c.indices, c.self_ids_in = s.ptr(A.INDPTR), s.ptr(A.INDICES), s.ptr(A.SELF_IDS_IN)
+            # the part's slice by source, where the engine emitted it (FLAG_TRANSPOSE): the backward gathers over it
+            self._fill(c, s, k > 0 and s.count(A.T_INDPTR) == s.n_in + 1 and s.n_in > 0)
             c.owned_out_nodes, c.owned_degree = s.ptr(A.OWNED_OUT_NODES), s.ptr(A.OWNED_DEGREE)
             c.from_all, c.to_all = s.ptr(A.FROM_IDS), s.ptr(A.TO_IDS)
-            c.n_out, c.n_in, c.n_owned = s.n_out, s.n_in, s.n_owned
-            c.n_from, c.n_to = sum(s.from_counts), sum(s.to_counts)
-            # the part's slice by source, where the engine emitted it (FLAG_TRANSPOSE): the backward gathers over it
-            if k and s.count(A.T_INDPTR) == s.n_in + 1 and s.n_in > 0:
-                c.t_indptr, c.t_indices = s.ptr(A.T_INDPTR), s.ptr(A.T_INDICES)
-                c.t_max_len, c.t_entries = s.t_max_len, s.count(A.T_INDICES)
-            else:
-                c.t_indptr, c.t_indices, c.t_max_len, c.t_entries = None, None, 0, 0
+            c.n_owned, c.n_from, c.n_to = s.n_owned, sum(s.from_counts), sum(s.to_counts)
         self._grow(feat.device)
         self._cur, self._exc = slices, None
         # (a 16-bit table: the step's _x16 twin, the same exchanges)

@@ -1,28 +1,47 @@
-// sage_step.hip -- forward, loss and backward of the GraphSAGE model of ONE part (a GPU that holds every node) for one
-// minibatch as ONE call behind the C ABI (cslicer_aggr.h, csl_sage_fwd_bwd_f32): the sequence of this library's fused
-// kernels and plain GEMMs that python/train.py:56-88 + python/layers/dist_sageconv.py:42-84 amount to on one GPU.
+// sage_step.hip -- forward, loss and backward of the GraphSAGE model for one minibatch as ONE call behind the C ABI: the
+// sequence of this library's fused kernels and plain GEMMs that python/train.py:56-88 + python/layers/dist_sageconv.py:42-84
+// amount to, on ONE part that holds every node (cslicer_aggr.h: csl_sage_fwd_bwd_f32, its _x16, _dropout and _multilabel
+// forms) and on one RANK of the split-parallel job (csl_sage_rank_fwd_bwd_f32 / _x16).  No kernels here, only sequencing.
 //
 // Why a native sequencer: the step is ~25 kernel launches and 8 GEMMs of 5-90 us each.  Issued from Python (one ctypes
 // call or torch op each, an autograd graph around them) they cost 0.55-0.75 ms of host time per step, more than the
 // 0.6 ms the GPU needs, and the rate then follows the host's speed (1.2-1.8 k minibatches/s from box to box).  Issued
-// from here a step is ~0.15 ms of host time and the GPU sets the pace.
+// from here a step is ~0.15 ms of host time and the GPU sets the pace (a rank: the 2 L callbacks plus ~0.25 ms instead of
+// ~1.2 ms of interpreter + autograd work, which is what bounds a rank once the GPU work is split N ways).
 //
-// Per model layer k (deepest hop first; slice k = the engine's layer n_layers-1-k, graph mode, FLAG_TRANSPOSE):
+// ONE layout (Layout, lay_out) and ONE body (sage_step) serve both; the six entry points check their own arguments and call
+// it.  Per model layer k (deepest hop first; slice k = the engine's layer n_layers-1-k, graph mode):
 //   forward   cat_k = [x[self] | mean_{CSR row} x[src]]       csl_sage_cat_f32 (k = 0 reads the resident feature table
 //             y_k   = cat_k W_k^T + b_k (ReLU for k < L-1)     through the slice's in_nodes)      + csl_gemm_f32
-//   loss      csl_softmax_ce_partial_f32 on y_{L-1} (forward, gradient = the top layer's padded gy, bias column sums)
+//             (k = 0, widths allowing: both as csl_sage_fwd_mfma_f32); dropout on y_k in place (k < L-1)
+//   loss      csl_softmax_ce_partial_f32 / csl_sigmoid_bce_partial_f32 on y_{L-1} (forward, gradient = the top layer's
+//             padded gy, bias column sums)
 //   backward  gW_k  = gy_k^T cat_k (row slabs)                 csl_gemm_f32 (batched)
 //             gcat  = gy_k W_k                                 csl_gemm_f32
 //             gy_{k-1}, gb_{k-1} = gather of gcat over the slice by source, ReLU mask of y_{k-1}, row padding and
 //                                  bias column sums in the same pass                   csl_sage_cat_bwd_t_f32
 //   the second stage of every reduction above (bias sums, slab sums, the loss): ONE launch (csl_reduce_multi_f32)
 // Rows are padded to a multiple of `row_pad` so that GEMM shapes repeat from minibatch to minibatch.
+//
+// A RANK (Layer::rank set; part g of P) differs from this in the places marked "rank" below and nowhere else:
+//   - its rows are the out rows it OWNS (n_owned <= n_out, n_in of a layer = n_owned of the layer below);
+//   - forward, the partial sums of the boundary rows go to their owners and come back merged (pull_for_remotes /
+//     push_from_remotes, dist_sageconv.py:52-65), and the backward runs the reverse exchange.  The exchange itself is the
+//     CALLER's (Exchange: a callback over torch.distributed's all_to_all_single on RCCL, gloo in the tests): this file has
+//     no communicator.  The fused layer 0 is taken when this part has no boundary rows there, and still enters the
+//     exchange (a collective every rank must enter) with the empty buffers;
+//   - a layer without a slice by source scatters its input gradient with atomics, where the single-GPU step refuses;
+//   - the gather by source reads g2 (gcat in out-row order, the peers' rows filled in by the reverse exchange), not gcat;
+//   - gcat is kept for layer 0 too, more than 256 classes are refused (no separate column-sum pass), an empty layer
+//     below defers a reduction over no blocks where the single-GPU step zero-fills, and nothing is timed;
+//   - no dropout and no multi-label loss yet: its entry points pass neither (what adding them takes).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "cslicer_aggr.h"
@@ -49,72 +68,123 @@ inline int64_t pad_rows(int64_t m, int64_t row_pad) {
   return (m + q - 1) / q * q;
 }
 
+// one model layer's slice as both steps read it
+struct Layer {
+  const int32_t *indptr, *indices, *self_ids_in, *t_indptr, *t_indices;
+  int64_t t_max_len, t_entries;
+  int64_t rows;                      // the rows that are computed and padded: n_out on one GPU, n_owned on a rank
+  int64_t n_in;
+  const csl_sage_rank_slice* rank;   // what only a rank has (owned rows, boundary lists); null: the single-GPU step
+  bool by_source() const { return t_indptr && t_indices; }
+};
+Layer view(const csl_sage_slice& s) {
+  return {s.indptr, s.indices, s.self_ids_in, s.t_indptr, s.t_indices, s.t_max_len, s.t_entries, s.n_out, s.n_in, nullptr};
+}
+Layer view(const csl_sage_rank_slice& s) {
+  return {s.indptr, s.indices, s.self_ids_in, s.t_indptr, s.t_indices, s.t_max_len, s.t_entries, s.n_owned, s.n_in, &s};
+}
+struct Layers {
+  Layer v[CSL_MAX_LAYERS] = {};
+  bool rank, ok;   // ok: slices given, 1..CSL_MAX_LAYERS of them
+  template <typename Slice>
+  Layers(int32_t L, const Slice* sl) : rank(std::is_same<Slice, csl_sage_rank_slice>::value), ok(sl && L >= 1 && L <= CSL_MAX_LAYERS) {
+    for (int k = 0; ok && k < L; k++) v[k] = view(sl[k]);
+  }
+};
+
 struct Layout {
   int64_t cat[CSL_MAX_LAYERS], y[CSL_MAX_LAYERS], gy[CSL_MAX_LAYERS], gcat[CSL_MAX_LAYERS], mp[CSL_MAX_LAYERS];
+  // rank only.  send / recv: forward the partial sums of peer-owned rows and the partials received for owned rows,
+  // backward their gradients the other way; agg: the merged sums of the owned rows, backward their gradient; gx: the input
+  // gradient of a layer that scatters it; g2: gcat in out-row order of a layer that gathers it by source
+  int64_t send[CSL_MAX_LAYERS], recv[CSL_MAX_LAYERS], agg[CSL_MAX_LAYERS], gx[CSL_MAX_LAYERS], g2[CSL_MAX_LAYERS];
   bool hub[CSL_MAX_LAYERS];
   // first stages of the step's reductions, each in a buffer of its own: they are all finished by ONE launch at the end
   int64_t slabs[CSL_MAX_LAYERS];    // [n_slabs][out][2 in] of a layer whose weight gradient is computed in row slabs
-  int64_t bpart[CSL_MAX_LAYERS];    // [blocks][out]: per-block column sums behind gb_k (k < L-1: from layer k+1's gather)
-  int64_t bblocks[CSL_MAX_LAYERS];
-  int64_t lpart, lblocks;           // [blocks]: the loss
+  int64_t bpart[CSL_MAX_LAYERS];    // [blocks][out]: per-block column sums behind gb_k (k < L-1: from layer k+1's backward)
+  int64_t bblocks[CSL_MAX_LAYERS];  // (0 exactly when the layer has no rows: every *_scratch is ceil(mp / rows per block) wide)
+  int64_t lpart;                    // [blocks of four rows]: the loss
   int64_t wpack;                    // W_0 in MFMA operand order (csl_sage_fwd_mfma_f32), -1: the deepest layer is not fused
   bool slabbed[CSL_MAX_LAYERS];
-  bool top_cols;                    // the softmax pass also leaves the top layer's bias column sums
-  int64_t g, scratch, total;
+  bool top_cols;                    // the loss pass also leaves the top layer's bias column sums
+  int64_t g, scratch, total;        // single GPU, more than 256 classes: the logits' gradient and the column-sum scratch
 };
 
 // bump allocation of the step's buffers (floats); returns false for an unsupported model
-bool lay_out(int32_t L, const int32_t* dims, const csl_sage_slice* sl, int64_t row_pad, int32_t n_slabs, Layout& o) {
-  if (L < 1 || L > CSL_MAX_LAYERS || n_slabs < 1) return false;
-  int64_t at = 0, scratch = 0;
+bool lay_out(int32_t L, const int32_t* dims, const Layers& lv, int64_t row_pad, int32_t n_slabs, Layout& o) {
+  if (!dims || !lv.ok || n_slabs < 1) return false;
+  const Layer* v = lv.v;
+  int64_t at = 0;
   for (int k = 0; k < L; k++) {
     const int64_t in = dims[k], out = dims[k + 1];
-    if (in < 4 || in % 4 != 0 || out < 1 || sl[k].n_out < 0 || sl[k].n_in < 0) return false;
+    const Layer& s = v[k];
+    const csl_sage_rank_slice* r = s.rank;
+    if (in < 4 || in % 4 != 0 || out < 1 || s.rows < 0 || s.n_in < 0) return false;
     if (k + 1 < L && out % 4 != 0) return false;  // a hidden width feeds the next layer's float4 kernels
-    if (k > 0 && sl[k].n_in != sl[k - 1].n_out) return false;  // layer k's sources are layer k-1's outputs
-    const int64_t mp = pad_rows(sl[k].n_out, row_pad);
+    if (r && (r->n_out < 0 || r->n_from < 0 || r->n_to < 0 || r->n_owned > r->n_out)) return false;
+    // layer k's sources are layer k-1's rows: its outputs on one GPU, the nodes this part owns below on a rank
+    if (k > 0 && s.n_in != v[k - 1].rows) return false;
+    const int64_t mp = pad_rows(s.rows, row_pad);
     o.mp[k] = mp;
+    o.send[k] = at, at += r ? up4(r->n_from * in) : 0;
+    o.recv[k] = at, at += r ? up4(r->n_to * in) : 0;
+    o.agg[k] = at, at += r ? up4(r->n_out * in) : 0;
     o.cat[k] = at, at += up4(mp * 2 * in);
     o.y[k] = at, at += up4(mp * out);
     o.gy[k] = at, at += up4(mp * out);
-    o.gcat[k] = at, at += k > 0 ? up4(mp * 2 * in) : 0;
-    o.hub[k] = k > 0 && sl[k].t_max_len > CSL_T_SORTED_MAX;   // a hub list: its rows are gathered by many workgroups
+    o.gcat[k] = at, at += k > 0 || r ? up4(mp * 2 * in) : 0;   // (layer 0 has no input gradient; a rank keeps the buffer)
+    const bool by_src = k > 0 && s.by_source();                // this layer's input gradient is gathered by source
+    o.gx[k] = at, at += r && k > 0 && !by_src ? up4(s.n_in * in) : 0;
+    o.g2[k] = at, at += r && by_src ? up4(r->n_out * 2 * in) : 0;
+    o.hub[k] = k > 0 && s.t_max_len > CSL_T_SORTED_MAX;        // a hub list: its rows are gathered by many workgroups
     const int64_t wn = out * 2 * in;
     o.slabbed[k] = row_pad > 0 && mp >= row_pad && n_slabs > 1 && mp % n_slabs == 0 && wn % 4 == 0;
     o.slabs[k] = at, at += o.slabbed[k] ? up4(wn * n_slabs) : 0;
-    // gb_k's first stage: written by layer k+1's gather (k < L-1; twice the blocks when that layer has hub lists), or by
-    // the loss pass / relu_bwd_colsum (k = L-1)
-    const bool hub_above = k + 1 < L && sl[k + 1].t_max_len > CSL_T_SORTED_MAX;
-    const int64_t part = k + 1 < L ? (hub_above ? csl_sage_cat_bwd_t_hub_scratch(mp, (int32_t)out)
-                                                : csl_sage_cat_bwd_t_scratch(mp, (int32_t)out)) : 0;
-    o.bblocks[k] = out > 0 ? part / out : 0;
+    // gb_k's first stage is written by layer k+1's backward (k < L-1): the gather by source (twice the blocks when that
+    // layer has hub lists) or, on a rank without one, the mask pass behind the atomic scatter; k = L-1: see below
+    int64_t part = 0;
+    if (k + 1 < L)
+      part = v[k + 1].rank && !v[k + 1].by_source()  ? csl_relu_bwd_colsum_scratch(mp, (int32_t)out)
+             : v[k + 1].t_max_len > CSL_T_SORTED_MAX ? csl_sage_cat_bwd_t_hub_scratch(mp, (int32_t)out)
+                                                     : csl_sage_cat_bwd_t_scratch(mp, (int32_t)out);
+    o.bblocks[k] = part / out;
     o.bpart[k] = at, at += up4(part);
   }
   {
     const int k = L - 1;
-    const int64_t C = dims[L], rows = o.mp[k];
+    const int64_t C = dims[L], rows = o.mp[k], lblocks = (rows + 3) / 4;
+    int64_t scratch = 0;
     o.top_cols = C <= 256;
-    o.lblocks = (rows + 3) / 4;
-    o.lpart = at, at += up4(o.lblocks);
+    if (lv.rank && !o.top_cols) return false;   // (a rank has no separate column-sum pass)
+    o.lpart = at, at += up4(lblocks);
     if (o.top_cols) {
-      o.bblocks[k] = o.lblocks;
-      o.bpart[k] = at, at += up4(o.lblocks * C);
+      o.bblocks[k] = lblocks;
+      o.bpart[k] = at, at += up4(lblocks * C);
     } else {
       scratch = csl_relu_bwd_colsum_scratch(rows, (int32_t)C);
     }
     // the gradient w.r.t. the logits IS the top layer's (padded) gy when the loss pass pads it; else a buffer of its own
     o.g = o.top_cols ? o.gy[k] : at;
-    at += o.top_cols ? 0 : up4(sl[k].n_out * C);
+    at += o.top_cols ? 0 : up4(v[k].rows * C);
+    o.scratch = at, at += up4(scratch);
   }
-  o.scratch = at, at += up4(scratch);
   {
-    // the deepest layer as ONE kernel (gather -> fp32 MFMA -> bias + ReLU) where its widths allow
-    const int64_t wp = getenv("CSLICER_NO_MFMA_FWD") ? -1 : csl_sage_fwd_mfma_scratch(dims[0], dims[1]);
+    // the deepest layer as ONE kernel (gather -> fp32 MFMA -> bias + ReLU) where its widths allow.  A rank: only WITHOUT
+    // boundary rows on this part (every out row owned, nothing sent or received: a world of one, or a partition that keeps
+    // a minibatch's neighbourhoods local), when its deepest layer is the single-GPU layer
+    const csl_sage_rank_slice* r = v[0].rank;
+    const bool local = !r || (r->n_from == 0 && r->n_to == 0 && r->n_owned == r->n_out);
+    const int64_t wp = local && !getenv("CSLICER_NO_MFMA_FWD") ? csl_sage_fwd_mfma_scratch(dims[0], dims[1]) : -1;
     o.wpack = wp > 0 ? at : -1;
     if (wp > 0) at += up4(wp);
   }
   o.total = at;
   return true;
+}
+
+int64_t workspace_floats_of(int32_t L, const int32_t* dims, const Layers& lv, int64_t row_pad, int32_t n_slabs) {
+  Layout o;
+  return lay_out(L, dims, lv, row_pad, n_slabs, o) ? o.total : (int64_t)CSL_E_INVALID;
 }
 
 // ---- diagnostics: device time of the step's launches by group (csl_sage_step_timing / _read): HIP events around every
@@ -154,24 +224,22 @@ struct SpanGuard {   // records e0 now and e1 when it goes out of scope
     g_spans.push_back(sp);
   }
 };
-#define TSTEP(group, x)              \
-  do {                               \
-    SpanGuard sg_((group), stream);  \
-    STEP(x);                         \
+
+int failed(const char* what, int rc, int layer) {
+  snprintf(s_err, sizeof(s_err), "%s failed (%d), layer %d", what, rc, layer);
+  return rc;
+}
+// one launch of the step on `stream`, timed under `group` (< 0: untimed); a failure ends the step with its layer named
+#define STEP(group, layer, x)                              \
+  do {                                                     \
+    SpanGuard sg_((group), stream);                        \
+    const int rc_ = (x);                                   \
+    if (rc_ < 0) return failed(#x, rc_, (layer));          \
   } while (0)
 
-#define STEP(x)                                                              \
-  do {                                                                       \
-    const int rc_ = (x);                                                     \
-    if (rc_ < 0) {                                                           \
-      snprintf(s_err, sizeof(s_err), "%s failed (%d), layer %d", #x, rc_, k); \
-      return rc_;                                                            \
-    }                                                                        \
-  } while (0)
-
-// ---- what the single-GPU step and the rank step share.  The resident feature table is float32 (kind 0: the _f32 entry
-// points) or 16-bit (CSL_FEAT_F16 / CSL_FEAT_BF16: the _x16 twins, cslicer_feat16.h); only the deepest layer's forward reads
-// it, through the readers of table_readers.h, and everything downstream of them is fp32 either way.
+// ---- the resident feature table is float32 (kind 0: the _f32 entry points) or 16-bit (CSL_FEAT_F16 / CSL_FEAT_BF16: the
+// _x16 twins, cslicer_feat16.h); only the deepest layer's forward reads it, through the readers of table_readers.h, and
+// everything downstream of them is fp32 either way.
 
 // the _x16 entry points refuse a table no reader takes before anything else
 bool table16_refused(const void* feat, int32_t kind, int64_t ldf) {
@@ -229,10 +297,30 @@ struct MultiArgs {
   int64_t ldw;
 };
 
-// gW_k = gy_k^T cat_k of either layout (Layout, RankLayout): nothing but a zero fill without rows, in row slabs whose sum
-// is deferred, or one plain GEMM.  group: the timing group of the GEMM (< 0: untimed)
-template <typename Lay>
-int weight_grad(int group, const Lay& o, int k, const int32_t* dims, int32_t n_slabs, float* ws, float* gW, Deferred& later,
+// a rank's boundary exchange: the caller's callbacks.  `wait` given: `exchange` only STARTS the exchange (on a stream of
+// the caller's) and `wait` makes `stream` wait for it -- called right before the received rows are first used, so the rows
+// that never leave the GPU are aggregated while the boundary rows travel (dist_sageconv.py:57-64 on a side stream)
+struct Exchange {
+  csl_exchange_fn exchange;
+  csl_exchange_wait_fn wait;
+  void *user, *stream;
+  int start(int layer, int backward, const float* src, float* dst, int32_t width) const {
+    const int rc = exchange(user, layer, backward, src, dst, width, stream);
+    if (rc >= 0) return CSL_OK;
+    snprintf(s_err, sizeof(s_err), "the exchange callback failed (%d), layer %d, %s", rc, layer, backward ? "backward" : "forward");
+    return rc;
+  }
+  int finish(int layer, int backward) const {
+    const int rc = wait ? wait(user, layer, backward, stream) : 0;
+    if (rc >= 0) return CSL_OK;
+    snprintf(s_err, sizeof(s_err), "the exchange-wait callback failed (%d), layer %d", rc, layer);
+    return rc;
+  }
+};
+
+// gW_k = gy_k^T cat_k: nothing but a zero fill without rows, in row slabs whose sum is deferred, or one plain GEMM.
+// group: the timing group of the GEMM (< 0: untimed)
+int weight_grad(int group, const Layout& o, int k, const int32_t* dims, int32_t n_slabs, float* ws, float* gW, Deferred& later,
                 void* stream) {
   const int64_t in = dims[k], out = dims[k + 1], mp = o.mp[k], wn = out * 2 * in;
   if (mp == 0) return hipMemsetAsync(gW, 0, sizeof(float) * wn, (hipStream_t)stream) == hipSuccess ? CSL_OK : CSL_E_HIP;
@@ -243,6 +331,188 @@ int weight_grad(int group, const Lay& o, int k, const int32_t* dims, int32_t n_s
   later.add(ws + o.slabs[k], n_slabs, (int32_t)wn, gW);
   return csl_gemm_f32(1, 0, out, 2 * in, rs, ws + o.gy[k], out, rs * out, ws + o.cat[k], 2 * in, rs * 2 * in, ws + o.slabs[k],
                       2 * in, wn, n_slabs, nullptr, 0, stream);
+}
+
+// gy_below [mp_below, in] = the gather of g [., 2 in] over layer s's slice by source, under the ReLU mask of y_below and
+// padded like its GEMM operand; its column sums stay as per-block partials in bpart.  indptr: the CSR whose row lengths
+// divide the mean half, null where g carries it divided already (a rank's g2).
+// A hub's list in the slice by source is thousands of entries, one wave's serial walk (1.3 ms instead of 30 us per launch
+// on a Zipf graph: profiles/hub_probe.py): those rows are summed by a workgroup per segment of entries
+int gather_by_source(const Layer& s, bool hub, const int32_t* indptr, const float* g, int32_t in, const float* y_below,
+                     int64_t mp_below, float* gy_below, float* bpart, void* stream) {
+  const int64_t ldg = 2 * (int64_t)in;
+  if (hub)
+    return csl_sage_cat_bwd_t_hub_f32(s.t_indptr, s.t_indices, s.t_entries, indptr, g, ldg, y_below, in, s.n_in, mp_below,
+                                      gy_below, in, nullptr, bpart, in, stream);
+  return csl_sage_cat_bwd_t_f32(s.t_indptr, s.t_indices, indptr, g, ldg, y_below, in, s.n_in, mp_below, gy_below, in, nullptr,
+                                bpart, in, stream);
+}
+
+// The step behind all six entry points.  lv: the slices (lv.rank: of a rank, with `xc` its exchange and `label_rows`);
+// kind: the feature table's element kind (0: float32).  Single GPU only: `drop` (csl_sage_fwd_bwd_dropout) and `multi`
+// (sigmoid-BCE on packed labels in place of the softmax cross-entropy: csl_sage_fwd_bwd_multilabel).
+int sage_step(int32_t n_layers, const int32_t* dims, const Layers& lv, const float* const* weights, const float* const* biases,
+              const void* feat, int32_t kind, int64_t ldf, const int32_t* feat_rows, const int32_t* seed_ids,
+              const int32_t* label_rows, const int64_t* labels, float scale, int64_t row_pad, int32_t n_slabs,
+              const Exchange* xc, float* grads, float* loss, float* workspace, int64_t workspace_floats, void* stream,
+              const DropArgs* drop, const MultiArgs* multi) {
+  s_err[0] = 0;
+  Layout o;
+  if (!weights || !biases || !grads || !loss || (lv.rank && !xc->exchange) || !lay_out(n_layers, dims, lv, row_pad, n_slabs, o)) {
+    if (lv.rank)
+      snprintf(s_err, sizeof(s_err), "bad argument or unsupported model (widths multiples of 4, <= 256 classes, 1..%d layers, "
+               "n_in of a layer = n_owned of the layer below)", CSL_MAX_LAYERS);
+    else
+      snprintf(s_err, sizeof(s_err), "bad argument or unsupported model (widths must be multiples of 4, 1..%d layers, "
+               "n_in of a layer = n_out of the layer below)", CSL_MAX_LAYERS);
+    return CSL_E_INVALID;
+  }
+  if (!workspace_fits(o.total, workspace, workspace_floats)) return CSL_E_INVALID;
+  const int L = n_layers;
+  float* ws = workspace;
+  const GradSlots gs(grads, L, dims);
+  // the timing groups of csl_sage_step_timing: the single-GPU step records them, a rank nothing
+  const int t_fused = lv.rank ? -1 : CSL_STEP_FUSED_FWD, t_gemm = lv.rank ? -1 : CSL_STEP_GEMM;
+  const int t_aggr = lv.rank ? -1 : CSL_STEP_AGGREGATION, t_other = lv.rank ? -1 : CSL_STEP_OTHER;
+  // ---- forward
+  for (int k = 0; k < L; k++) {
+    const int32_t in = dims[k], out = dims[k + 1];
+    const Layer& s = lv.v[k];
+    const csl_sage_rank_slice* r = s.rank;
+    const int64_t m = s.rows, mp = o.mp[k], ldc = 2 * (int64_t)in;
+    // the deepest layer reads the resident feature rows through feat_rows (no gathered input matrix)
+    const void* x = k == 0 ? feat : ws + o.y[k - 1];
+    const int32_t xk = k == 0 ? kind : 0;   // (only the feature table may be 16-bit)
+    const int64_t ldx = k == 0 ? ldf : (int64_t)in;
+    const int32_t* map = k == 0 ? feat_rows : nullptr;
+    if (k == 0 && o.wpack >= 0) {
+      // rank: "no boundary rows" is a property of THIS part's slice: a peer may have some in the same minibatch, and the
+      // exchange is a collective every rank must enter -- so it is issued here too, with the empty buffers (whether a
+      // collective is entered depends only on L, which all ranks share)
+      if (r) {
+        if (const int rc = xc->start(0, 0, ws + o.send[0], ws + o.recv[0], in); rc < 0) return rc;
+        if (const int rc = xc->finish(0, 0); rc < 0) return rc;
+      }
+      // gather [self | mean] into LDS, multiply on the fp32 matrix cores, bias + ReLU on the way out; the operand is
+      // also written (the weight gradient reads it), but never read back by the forward
+      STEP(t_fused, k, rd::sage_fwd_mfma(s.indptr, s.indices, s.self_ids_in, feat_rows, feat, kind, ldf, weights[0], ldc, biases[0],
+                                         m, mp, in, out, 0, L > 1 ? 1 : 0, ws + o.cat[0], ldc, ws + o.y[0], out, ws + o.wpack,
+                                         stream));
+    } else {
+      if (r) {
+        // partial sums of the rows peers own, straight into the send buffer; then the rows this part owns
+        STEP(-1, k, rd::spmm_sum_map(s.indptr, s.indices, r->from_all, r->n_from, x, xk, ldx, map, ws + o.send[k], in, in, 1, stream));
+        if (const int rc = xc->start(k, 0, ws + o.send[k], ws + o.recv[k], in); rc < 0) return rc;
+        STEP(-1, k, rd::spmm_sum_map(s.indptr, s.indices, r->owned_out_nodes, r->n_owned, x, xk, ldx, map, ws + o.agg[k], in, in, 0, stream));
+        if (const int rc = xc->finish(k, 0); rc < 0) return rc;
+        STEP(-1, k, csl_scatter_add_rows_atomic_f32(ws + o.agg[k], in, r->to_all, r->n_to, ws + o.recv[k], in, in, stream));
+        STEP(-1, k, rd::sage_cat(nullptr, nullptr, s.self_ids_in, r->owned_out_nodes, r->owned_degree, map, x, xk, ldx, ws + o.agg[k],
+                                 in, m, mp, ws + o.cat[k], ldc, in, 0, stream));
+      } else {
+        STEP(t_aggr, k, rd::sage_cat(s.indptr, s.indices, s.self_ids_in, nullptr, nullptr, map, x, xk, ldx, nullptr, 0, m, mp,
+                                     ws + o.cat[k], ldc, in, 0, stream));
+      }
+      STEP(t_gemm, k, csl_gemm_f32(0, 1, mp, out, ldc, ws + o.cat[k], ldc, 0, weights[k], ldc, 0, ws + o.y[k], out, 0, 1, biases[k],
+                                   k + 1 < L ? 1 : 0, stream));
+    }
+    // y_k is stored after its ReLU and read as it is by the layer above and by the backward's mask (y_k > 0): dropped in
+    // place it carries relu' * mask by itself
+    if (drop && k + 1 < L)
+      STEP(t_other, k, csl_dropout_f32(ws + o.y[k], out, ws + o.y[k], out, drop->out_ids[k], m, out, drop->p, drop->seed, k,
+                                       drop->step, stream));
+  }
+  Deferred later;
+  // ---- loss and its gradient w.r.t. the logits, bias column sums alongside (a rank: over the seeds this part owns, the
+  // caller's `scale` = 1 / seeds of the WHOLE minibatch).  <= 256 classes: the pass pads the gradient into the top layer's
+  // gy and leaves the column sums' first stage; more (single GPU): a column-sum pass of its own does both
+  {
+    const int k = L - 1;
+    const int32_t C = dims[L];
+    const int64_t m = lv.v[k].rows, rows = o.top_cols ? o.mp[k] : m;
+    float* cols = o.top_cols ? ws + o.bpart[k] : nullptr;
+    if (multi)
+      STEP(t_other, k, csl_sigmoid_bce_partial_f32(ws + o.y[k], C, m, rows, C, seed_ids, label_rows, multi->words, multi->ldw, scale,
+                                                   ws + o.g, C, ws + o.lpart, cols, stream));
+    else
+      STEP(t_other, k, csl_softmax_ce_partial_f32(ws + o.y[k], C, m, rows, C, seed_ids, label_rows, labels, scale, ws + o.g, C,
+                                                  ws + o.lpart, cols, stream));
+    if (o.top_cols) later.add(cols, o.bblocks[k], C, gs.gb[k]);
+    else STEP(t_aggr, k, csl_relu_bwd_colsum_f32(ws + o.g, C, nullptr, 0, m, o.mp[k], ws + o.gy[k], C, gs.gb[k], ws + o.scratch, C, stream));
+    later.add(ws + o.lpart, (rows + 3) / 4, 1, loss);  // (blocks of four rows the loss pass covered)
+  }
+  // ---- backward
+  for (int k = L - 1; k >= 0; k--) {
+    const int32_t in = dims[k], out = dims[k + 1];
+    const Layer& s = lv.v[k];
+    const csl_sage_rank_slice* r = s.rank;
+    const int64_t mp = o.mp[k], ldc = 2 * (int64_t)in;
+    STEP(-1, k, weight_grad(t_gemm, o, k, dims, n_slabs, ws, gs.gW[k], later, stream));
+    if (k == 0) break;   // (no gradient flows into the input features; the deepest layer's exchange has no backward)
+    if (!r && !s.by_source()) {
+      snprintf(s_err, sizeof(s_err), "layer %d has no slice by source (engine flag CSL_FLAG_TRANSPOSE)", k);
+      return CSL_E_INVALID;
+    }
+    STEP(t_gemm, k, csl_gemm_f32(0, 0, mp, ldc, out, ws + o.gy[k], out, 0, weights[k], ldc, 0, ws + o.gcat[k], ldc, 0, 1, nullptr, 0,
+                                 stream));
+    // gradient w.r.t. layer k-1's pre-activation output (= this layer's input x), padded like its GEMM operand; its
+    // column sums (gb_{k-1}) stay as per-block partials
+    const int64_t mp_below = o.mp[k - 1];
+    const float* y_below = ws + o.y[k - 1];
+    float *gy_below = ws + o.gy[k - 1], *bpart = ws + o.bpart[k - 1];
+    if (r && !s.by_source()) {
+      // rank, no slice by source: operand gradient -> self rows of gx and owned rows of the merged sums' gradient (both
+      // zeroed inside)
+      STEP(-1, k, csl_sage_cat_rows_bwd_f32(s.self_ids_in, r->owned_out_nodes, r->owned_degree, r->n_owned, ws + o.gcat[k], ldc,
+                                            ws + o.gx[k], s.n_in, ws + o.agg[k], r->n_out, in, stream));
+      // what this part received forward gets its gradient back; the reverse exchange returns the gradients of the
+      // partial sums this part sent
+      STEP(-1, k, csl_gather_rows_f32(ws + o.agg[k], in, r->to_all, r->n_to, ws + o.recv[k], in, in, stream));
+      if (const int rc = xc->start(k, 1, ws + o.recv[k], ws + o.send[k], in); rc < 0) return rc;
+      STEP(-1, k, csl_spmm_sum_bwd_f32(s.indptr, s.indices, r->owned_out_nodes, r->n_owned, ws + o.agg[k], in, 0, ws + o.gx[k], in, in,
+                                       stream));
+      if (const int rc = xc->finish(k, 1); rc < 0) return rc;
+      STEP(-1, k, csl_spmm_sum_bwd_f32(s.indptr, s.indices, r->from_all, r->n_from, ws + o.send[k], in, 1, ws + o.gx[k], in, in, stream));
+      // ReLU mask of the layer below, padding of its GEMM operand, its bias column sums (first stage)
+      if (mp_below > 0)
+        STEP(-1, k, csl_relu_bwd_colsum_f32(ws + o.gx[k], in, y_below, in, s.n_in, mp_below, gy_below, in, nullptr, bpart, in, stream));
+    } else if (r) {
+      // rank, BY SOURCE: the operand gradient goes into out-row order (mean half / true degree), the rows peers own get
+      // theirs from the reverse exchange, and ONE gather over the part's slice by source writes the input gradient with
+      // the ReLU mask of the layer below, its padding and its bias sums -- no atomics, no zero fill
+      float* g2 = ws + o.g2[k];
+      STEP(-1, k, csl_sage_rank_g2_f32(r->owned_out_nodes, r->owned_degree, r->n_owned, ws + o.gcat[k], ldc, g2, ldc, in, stream));
+      // what this part received forward gets its gradient back (the mean halves of the owned rows it was merged into)
+      STEP(-1, k, csl_gather_rows_f32(g2 + in, ldc, r->to_all, r->n_to, ws + o.recv[k], in, in, stream));
+      if (const int rc = xc->start(k, 1, ws + o.recv[k], ws + o.send[k], in); rc < 0) return rc;
+      if (const int rc = xc->finish(k, 1); rc < 0) return rc;
+      STEP(-1, k, csl_scatter_rows_f32(g2 + in, ldc, r->from_all, r->n_from, ws + o.send[k], in, in, stream));
+      if (mp_below > 0) STEP(-1, k, gather_by_source(s, o.hub[k], nullptr, g2, in, y_below, mp_below, gy_below, bpart, stream));
+    } else {
+      STEP(t_aggr, k, gather_by_source(s, o.hub[k], s.indptr, ws + o.gcat[k], in, y_below, mp_below, gy_below, bpart, stream));
+    }
+    // gb_{k-1}.  An empty layer below (no blocks): a rank defers a reduction over none, the single-GPU step zero-fills
+    if (r || o.bblocks[k - 1] > 0) later.add(bpart, o.bblocks[k - 1], in, gs.gb[k - 1]);
+    else if (hipMemsetAsync(gs.gb[k - 1], 0, sizeof(float) * in, (hipStream_t)stream) != hipSuccess) return CSL_E_HIP;
+  }
+  // ---- every deferred second stage (bias sums, weight-gradient slabs, the loss) in one launch
+  STEP(t_other, -1, later.finish(stream));
+  if (drop && L > 1) {
+    // the backward crossed L-1-j dropped layers on its way to layer j with the mask alone: the factor s of each, which
+    // commutes with everything downstream of it, goes onto the finished gradients
+    float* seg[CSL_SCALE_SEGMENTS_MAX];
+    int64_t cnt[CSL_SCALE_SEGMENTS_MAX];
+    float fac[CSL_SCALE_SEGMENTS_MAX];
+    const double s1 = (double)(float)(1.0 / (1.0 - (double)drop->p));
+    double f = 1.0;
+    int ns = 0;
+    for (int j = L - 2; j >= 0; j--) {
+      f *= s1;
+      seg[ns] = gs.gW[j], cnt[ns] = (int64_t)dims[j + 1] * 2 * dims[j], fac[ns] = (float)f, ns++;
+      seg[ns] = gs.gb[j], cnt[ns] = dims[j + 1], fac[ns] = (float)f, ns++;
+    }
+    STEP(t_other, -1, csl_scale_segments_f32(ns, seg, cnt, fac, stream));
+  }
+  return CSL_OK;
 }
 
 }  // namespace
@@ -274,138 +544,20 @@ int csl_sage_step_timing_read(double* ms, int64_t* launches) {
 
 int64_t csl_sage_fwd_bwd_workspace(int32_t n_layers, const int32_t* dims, const csl_sage_slice* slices, int64_t row_pad,
                                    int32_t n_slabs) {
-  Layout o;
-  if (!dims || !slices || !lay_out(n_layers, dims, slices, row_pad, n_slabs, o)) return CSL_E_INVALID;
-  return o.total;
+  return workspace_floats_of(n_layers, dims, Layers(n_layers, slices), row_pad, n_slabs);
 }
 
-// the step behind csl_sage_fwd_bwd_f32 (kind 0), csl_sage_fwd_bwd_x16, with `drop` csl_sage_fwd_bwd_dropout and, with
-// `multi` (sigmoid-BCE on packed labels where the others run the softmax cross-entropy), csl_sage_fwd_bwd_multilabel
-static int sage_fwd_bwd(int32_t n_layers, const int32_t* dims, const csl_sage_slice* sl, const float* const* weights,
-                        const float* const* biases, const void* feat, int32_t kind, int64_t ldf, const int32_t* feat_rows,
-                        const int32_t* seed_ids, const int64_t* labels, float scale, int64_t row_pad, int32_t n_slabs,
-                        float* grads, float* loss, float* workspace, int64_t workspace_floats, void* stream,
-                        const DropArgs* drop = nullptr, const MultiArgs* multi = nullptr) {
-  int k = -1;
-  s_err[0] = 0;
-  Layout o;
-  if (!dims || !sl || !weights || !biases || !grads || !loss || !lay_out(n_layers, dims, sl, row_pad, n_slabs, o)) {
-    snprintf(s_err, sizeof(s_err), "bad argument or unsupported model (widths must be multiples of 4, 1..%d layers, "
-             "n_in of a layer = n_out of the layer below)", CSL_MAX_LAYERS);
-    return CSL_E_INVALID;
-  }
-  if (!workspace_fits(o.total, workspace, workspace_floats)) return CSL_E_INVALID;
-  const int L = n_layers;
-  float* ws = workspace;
-  const GradSlots gs(grads, L, dims);
-  // ---- forward
-  for (k = 0; k < L; k++) {
-    const int32_t in = dims[k], out = dims[k + 1];
-    const int64_t m = sl[k].n_out, mp = o.mp[k];
-    const void* x = k == 0 ? feat : ws + o.y[k - 1];
-    const int32_t xk = k == 0 ? kind : 0;   // (only the feature table may be 16-bit)
-    if (k == 0 && o.wpack >= 0) {
-      // gather [self | mean] into LDS, multiply on the fp32 matrix cores, bias + ReLU on the way out; the operand is
-      // also written (the weight gradient reads it), but never read back by the forward
-      TSTEP(CSL_STEP_FUSED_FWD, rd::sage_fwd_mfma(sl[0].indptr, sl[0].indices, sl[0].self_ids_in, feat_rows, feat, kind, ldf, weights[0],
-                                                  2 * (int64_t)in, biases[0], m, mp, in, out, 0, L > 1 ? 1 : 0, ws + o.cat[0],
-                                                  2 * (int64_t)in, ws + o.y[0], out, ws + o.wpack, stream));
-      if (drop && L > 1)
-        TSTEP(CSL_STEP_OTHER, csl_dropout_f32(ws + o.y[0], out, ws + o.y[0], out, drop->out_ids[0], m, out, drop->p, drop->seed, 0,
-                                              drop->step, stream));
-      continue;
-    }
-    TSTEP(CSL_STEP_AGGREGATION, rd::sage_cat(sl[k].indptr, sl[k].indices, sl[k].self_ids_in, nullptr, nullptr, k == 0 ? feat_rows : nullptr, x,
-                                             xk, k == 0 ? ldf : (int64_t)in, nullptr, 0, m, mp, ws + o.cat[k], 2 * (int64_t)in, in, 0, stream));
-    TSTEP(CSL_STEP_GEMM, csl_gemm_f32(0, 1, mp, out, 2 * (int64_t)in, ws + o.cat[k], 2 * (int64_t)in, 0, weights[k], 2 * (int64_t)in, 0,
-                      ws + o.y[k], out, 0, 1, biases[k], k + 1 < L ? 1 : 0, stream));
-    // y_k is stored after its ReLU and read as it is by the layer above and by the backward's mask (y_k > 0): dropped in
-    // place it carries relu' * mask by itself
-    if (drop && k + 1 < L)
-      TSTEP(CSL_STEP_OTHER, csl_dropout_f32(ws + o.y[k], out, ws + o.y[k], out, drop->out_ids[k], m, out, drop->p, drop->seed, k,
-                                            drop->step, stream));
-  }
-  Deferred later;
-  // ---- loss and its gradient w.r.t. the logits (written as the top layer's padded gy), bias column sums alongside
-  k = L - 1;
-  {
-    const int32_t C = dims[L];
-    const int64_t m = sl[k].n_out;
-    if (o.top_cols) {
-      if (multi)
-        TSTEP(CSL_STEP_OTHER, csl_sigmoid_bce_partial_f32(ws + o.y[k], C, m, o.mp[k], C, seed_ids, nullptr, multi->words, multi->ldw,
-                                                          scale, ws + o.gy[k], C, ws + o.lpart, ws + o.bpart[k], stream));
-      else
-      TSTEP(CSL_STEP_OTHER, csl_softmax_ce_partial_f32(ws + o.y[k], C, m, o.mp[k], C, seed_ids, nullptr, labels, scale, ws + o.gy[k], C,
-                                      ws + o.lpart, ws + o.bpart[k], stream));
-      later.add(ws + o.bpart[k], o.bblocks[k], C, gs.gb[k]);
-    } else {
-      if (multi)
-        TSTEP(CSL_STEP_OTHER, csl_sigmoid_bce_partial_f32(ws + o.y[k], C, m, m, C, seed_ids, nullptr, multi->words, multi->ldw, scale,
-                                                          ws + o.g, C, ws + o.lpart, nullptr, stream));
-      else
-      TSTEP(CSL_STEP_OTHER, csl_softmax_ce_partial_f32(ws + o.y[k], C, m, m, C, seed_ids, nullptr, labels, scale, ws + o.g, C, ws + o.lpart,
-                                      nullptr, stream));
-      TSTEP(CSL_STEP_AGGREGATION, csl_relu_bwd_colsum_f32(ws + o.g, C, nullptr, 0, m, o.mp[k], ws + o.gy[k], C, gs.gb[k], ws + o.scratch, C, stream));
-    }
-    later.add(ws + o.lpart, o.top_cols ? o.lblocks : (m + 3) / 4, 1, loss);  // (blocks of four rows the loss pass covered)
-  }
-  // ---- backward
-  for (k = L - 1; k >= 0; k--) {
-    const int32_t in = dims[k], out = dims[k + 1];
-    const int64_t mp = o.mp[k];
-    STEP(weight_grad(CSL_STEP_GEMM, o, k, dims, n_slabs, ws, gs.gW[k], later, stream));
-    if (k == 0) break;
-    if (!sl[k].t_indptr || !sl[k].t_indices) {
-      snprintf(s_err, sizeof(s_err), "layer %d has no slice by source (engine flag CSL_FLAG_TRANSPOSE)", k);
-      return CSL_E_INVALID;
-    }
-    TSTEP(CSL_STEP_GEMM, csl_gemm_f32(0, 0, mp, 2 * (int64_t)in, out, ws + o.gy[k], out, 0, weights[k], 2 * (int64_t)in, 0, ws + o.gcat[k],
-                      2 * (int64_t)in, 0, 1, nullptr, 0, stream));
-    // gradient w.r.t. layer k-1's pre-activation output (= this layer's input x), padded like its GEMM operand;
-    // its column sums (gb_{k-1}) stay as per-block partials
-    if (o.hub[k]) {
-      // a hub's list in the slice by source is thousands of entries, one wave's serial walk (1.3 ms instead of 30 us per
-      // launch on a Zipf graph: profiles/hub_probe.py): those rows are summed by a workgroup per segment of entries
-      TSTEP(CSL_STEP_AGGREGATION, csl_sage_cat_bwd_t_hub_f32(sl[k].t_indptr, sl[k].t_indices, sl[k].t_entries, sl[k].indptr,
-                                                              ws + o.gcat[k], 2 * (int64_t)in, ws + o.y[k - 1], in, sl[k].n_in,
-                                                              o.mp[k - 1], ws + o.gy[k - 1], in, nullptr, ws + o.bpart[k - 1],
-                                                              in, stream));
-    } else
-    TSTEP(CSL_STEP_AGGREGATION, csl_sage_cat_bwd_t_f32(sl[k].t_indptr, sl[k].t_indices, sl[k].indptr, ws + o.gcat[k], 2 * (int64_t)in,
-                                ws + o.y[k - 1], in, sl[k].n_in, o.mp[k - 1], ws + o.gy[k - 1], in, nullptr,
-                                ws + o.bpart[k - 1], in, stream));
-    if (o.bblocks[k - 1] > 0) later.add(ws + o.bpart[k - 1], o.bblocks[k - 1], in, gs.gb[k - 1]);
-    else if (hipMemsetAsync(gs.gb[k - 1], 0, sizeof(float) * in, (hipStream_t)stream) != hipSuccess) return CSL_E_HIP;
-  }
-  // ---- every deferred second stage (bias sums, weight-gradient slabs, the loss) in one launch
-  k = -1;
-  TSTEP(CSL_STEP_OTHER, later.finish(stream));
-  if (drop && L > 1) {
-    // the backward crossed L-1-j dropped layers on its way to layer j with the mask alone: the factor s of each, which
-    // commutes with everything downstream of it, goes onto the finished gradients
-    float* seg[CSL_SCALE_SEGMENTS_MAX];
-    int64_t cnt[CSL_SCALE_SEGMENTS_MAX];
-    float fac[CSL_SCALE_SEGMENTS_MAX];
-    const double s1 = (double)(float)(1.0 / (1.0 - (double)drop->p));
-    double f = 1.0;
-    int ns = 0;
-    for (int j = L - 2; j >= 0; j--) {
-      f *= s1;
-      seg[ns] = gs.gW[j], cnt[ns] = (int64_t)dims[j + 1] * 2 * dims[j], fac[ns] = (float)f, ns++;
-      seg[ns] = gs.gb[j], cnt[ns] = dims[j + 1], fac[ns] = (float)f, ns++;
-    }
-    TSTEP(CSL_STEP_OTHER, csl_scale_segments_f32(ns, seg, cnt, fac, stream));
-  }
-  return CSL_OK;
+int64_t csl_sage_rank_workspace(int32_t n_layers, const int32_t* dims, const csl_sage_rank_slice* slices, int64_t row_pad,
+                                int32_t n_slabs) {
+  return workspace_floats_of(n_layers, dims, Layers(n_layers, slices), row_pad, n_slabs);
 }
 
 int csl_sage_fwd_bwd_f32(int32_t n_layers, const int32_t* dims, const csl_sage_slice* sl, const float* const* weights,
                          const float* const* biases, const float* feat, int64_t ldf, const int32_t* feat_rows,
                          const int32_t* seed_ids, const int64_t* labels, float scale, int64_t row_pad, int32_t n_slabs,
                          float* grads, float* loss, float* workspace, int64_t workspace_floats, void* stream) {
-  return sage_fwd_bwd(n_layers, dims, sl, weights, biases, feat, 0, ldf, feat_rows, seed_ids, labels, scale, row_pad, n_slabs,
-                      grads, loss, workspace, workspace_floats, stream);
+  return sage_step(n_layers, dims, Layers(n_layers, sl), weights, biases, feat, 0, ldf, feat_rows, seed_ids, nullptr, labels, scale,
+                   row_pad, n_slabs, nullptr, grads, loss, workspace, workspace_floats, stream, nullptr, nullptr);
 }
 
 int csl_sage_fwd_bwd_x16(int32_t n_layers, const int32_t* dims, const csl_sage_slice* sl, const float* const* weights,
@@ -413,8 +565,8 @@ int csl_sage_fwd_bwd_x16(int32_t n_layers, const int32_t* dims, const csl_sage_s
                          const int32_t* seed_ids, const int64_t* labels, float scale, int64_t row_pad, int32_t n_slabs,
                          float* grads, float* loss, float* workspace, int64_t workspace_floats, void* stream) {
   if (table16_refused(feat, kind, ldf)) return CSL_E_INVALID;
-  return sage_fwd_bwd(n_layers, dims, sl, weights, biases, feat, kind, ldf, feat_rows, seed_ids, labels, scale, row_pad,
-                      n_slabs, grads, loss, workspace, workspace_floats, stream);
+  return sage_step(n_layers, dims, Layers(n_layers, sl), weights, biases, feat, kind, ldf, feat_rows, seed_ids, nullptr, labels,
+                   scale, row_pad, n_slabs, nullptr, grads, loss, workspace, workspace_floats, stream, nullptr, nullptr);
 }
 
 int csl_sage_fwd_bwd_dropout(int32_t n_layers, const int32_t* dims, const csl_sage_slice* sl, const float* const* weights,
@@ -431,8 +583,8 @@ int csl_sage_fwd_bwd_dropout(int32_t n_layers, const int32_t* dims, const csl_sa
     return CSL_E_INVALID;
   }
   const DropArgs drop = {out_ids, p, seed, step};
-  return sage_fwd_bwd(n_layers, dims, sl, weights, biases, feat, kind, ldf, feat_rows, seed_ids, labels, scale, row_pad,
-                      n_slabs, grads, loss, workspace, workspace_floats, stream, &drop);
+  return sage_step(n_layers, dims, Layers(n_layers, sl), weights, biases, feat, kind, ldf, feat_rows, seed_ids, nullptr, labels,
+                   scale, row_pad, n_slabs, nullptr, grads, loss, workspace, workspace_floats, stream, &drop, nullptr);
 }
 
 int csl_sage_fwd_bwd_multilabel(int32_t n_layers, const int32_t* dims, const csl_sage_slice* sl, const float* const* weights,
@@ -455,232 +607,8 @@ int csl_sage_fwd_bwd_multilabel(int32_t n_layers, const int32_t* dims, const csl
   }
   const DropArgs drop = {out_ids, p, seed, step};
   const MultiArgs multi = {label_words, ldw};
-  return sage_fwd_bwd(n_layers, dims, sl, weights, biases, feat, kind, ldf, feat_rows, seed_ids, nullptr, scale, row_pad,
-                      n_slabs, grads, loss, workspace, workspace_floats, stream, plain ? nullptr : &drop, &multi);
-}
-
-}  // extern "C"
-
-// ===== one rank of the SPLIT-PARALLEL step (python/train.py + dist_sageconv.py:42-84 with several GPUs) =============
-// The same sequencing for part g of P: per layer the partial sums of the boundary rows go to their owners and come
-// back merged (pull_for_remotes / push_from_remotes, dist_sageconv.py:52-65), backward mirrors it.  The exchange itself
-// is the CALLER's (a callback: torch.distributed's all_to_all_single over RCCL, or gloo in the tests) -- this file has no
-// communicator; everything between two exchanges is issued from here, so a step costs the host the 2 L callbacks plus
-// ~0.25 ms instead of ~1.2 ms of interpreter + autograd work, which is what bounds a rank once the GPU work is split N ways.
-namespace {
-
-struct RankLayout {
-  int64_t x0, send[CSL_MAX_LAYERS], recv[CSL_MAX_LAYERS], agg[CSL_MAX_LAYERS], cat[CSL_MAX_LAYERS], y[CSL_MAX_LAYERS],
-      gy[CSL_MAX_LAYERS], gcat[CSL_MAX_LAYERS], gx[CSL_MAX_LAYERS], g2[CSL_MAX_LAYERS], slabs[CSL_MAX_LAYERS], bpart[CSL_MAX_LAYERS],
-      bblocks[CSL_MAX_LAYERS], mp[CSL_MAX_LAYERS];
-  bool slabbed[CSL_MAX_LAYERS];
-  int64_t lpart, lblocks, total;
-  int64_t wpack;   // W_0 in MFMA operand order when the deepest layer has no boundary rows on this part (else -1)
-};
-
-bool rank_lay_out(int32_t L, const int32_t* dims, const csl_sage_rank_slice* sl, int64_t row_pad, int32_t n_slabs,
-                  RankLayout& o) {
-  if (L < 1 || L > CSL_MAX_LAYERS || n_slabs < 1) return false;
-  int64_t at = 0;
-  o.x0 = 0;   // (the deepest layer reads the resident feature rows through feat_rows: no gathered input matrix)
-  for (int k = 0; k < L; k++) {
-    const int64_t in = dims[k], out = dims[k + 1];
-    const csl_sage_rank_slice& s = sl[k];
-    if (in < 4 || in % 4 != 0 || out < 1 || (k + 1 < L && out % 4 != 0)) return false;
-    if (s.n_out < 0 || s.n_in < 0 || s.n_owned < 0 || s.n_from < 0 || s.n_to < 0 || s.n_owned > s.n_out) return false;
-    if (k > 0 && s.n_in != sl[k - 1].n_owned) return false;  // a layer's sources are the nodes this part owns below
-    const int64_t mp = pad_rows(s.n_owned, row_pad);
-    o.mp[k] = mp;
-    o.send[k] = at, at += up4(s.n_from * in);   // forward: partial sums of peer-owned rows; backward: their gradients back
-    o.recv[k] = at, at += up4(s.n_to * in);     // forward: partials received for owned rows; backward: their gradients
-    o.agg[k] = at, at += up4(s.n_out * in);     // forward: merged sums (owned rows); backward: their gradient
-    o.cat[k] = at, at += up4(mp * 2 * in);
-    o.y[k] = at, at += up4(mp * out);
-    o.gy[k] = at, at += up4(mp * out);
-    o.gcat[k] = at, at += up4(mp * 2 * in);
-    const bool by_src = k > 0 && s.t_indptr && s.t_indices;      // this layer's input gradient is gathered by source
-    o.gx[k] = at, at += (k > 0 && !by_src) ? up4(s.n_in * in) : 0;
-    o.g2[k] = at, at += by_src ? up4(s.n_out * 2 * in) : 0;
-    const int64_t wn = out * 2 * in;
-    o.slabbed[k] = row_pad > 0 && mp >= row_pad && n_slabs > 1 && mp % n_slabs == 0 && wn % 4 == 0;
-    o.slabs[k] = at, at += o.slabbed[k] ? up4(wn * n_slabs) : 0;
-    // gb_k's first stage is written by layer k+1's backward: the mask pass behind the atomic scatter, or the gather by source
-    const bool src_above = k + 1 < L && sl[k + 1].t_indptr && sl[k + 1].t_indices;
-    const int64_t part = k + 1 < L ? (!src_above ? csl_relu_bwd_colsum_scratch(mp, (int32_t)out)
-                                     : sl[k + 1].t_max_len > CSL_T_SORTED_MAX ? csl_sage_cat_bwd_t_hub_scratch(mp, (int32_t)out)
-                                                                              : csl_sage_cat_bwd_t_scratch(mp, (int32_t)out)) : 0;
-    o.bblocks[k] = part / out;
-    o.bpart[k] = at, at += up4(part);
-  }
-  const int64_t C = dims[L];
-  if (C > 256) return false;  // (the loss pass leaves the bias column sums: csl_softmax_ce_partial_f32)
-  o.lblocks = (o.mp[L - 1] + 3) / 4;
-  o.lpart = at, at += up4(o.lblocks);
-  o.bblocks[L - 1] = o.lblocks;
-  o.bpart[L - 1] = at, at += up4(o.lblocks * C);
-  {
-    // a deepest layer WITHOUT boundary rows on this part (every out row owned, nothing sent or received: a world of one,
-    // or a partition that keeps a minibatch's neighbourhoods local) is the single-GPU layer: one fused kernel
-    const csl_sage_rank_slice& s0 = sl[0];
-    const bool local = s0.n_from == 0 && s0.n_to == 0 && s0.n_owned == s0.n_out && !getenv("CSLICER_NO_MFMA_FWD");
-    const int64_t wp = local ? csl_sage_fwd_mfma_scratch(dims[0], dims[1]) : -1;
-    o.wpack = wp > 0 ? at : -1;
-    if (wp > 0) at += up4(wp);
-  }
-  o.total = at;
-  return true;
-}
-
-}  // namespace
-
-extern "C" {
-
-int64_t csl_sage_rank_workspace(int32_t n_layers, const int32_t* dims, const csl_sage_rank_slice* slices, int64_t row_pad,
-                                int32_t n_slabs) {
-  RankLayout o;
-  if (!dims || !slices || !rank_lay_out(n_layers, dims, slices, row_pad, n_slabs, o)) return CSL_E_INVALID;
-  return o.total;
-}
-
-// the rank step behind csl_sage_rank_fwd_bwd_f32 (kind 0) and csl_sage_rank_fwd_bwd_x16
-static int sage_rank_fwd_bwd(int32_t n_layers, const int32_t* dims, const csl_sage_rank_slice* sl,
-                             const float* const* weights, const float* const* biases, const void* feat, int32_t kind,
-                             int64_t ldf, const int32_t* feat_rows, const int32_t* seed_ids, const int32_t* label_rows,
-                             const int64_t* labels, float scale, int64_t row_pad, int32_t n_slabs,
-                             csl_exchange_fn exchange, csl_exchange_wait_fn wait, void* user, float* grads, float* loss,
-                             float* workspace, int64_t workspace_floats, void* stream) {
-  int k = -1;
-  s_err[0] = 0;
-  RankLayout o;
-  if (!dims || !sl || !weights || !biases || !grads || !loss || !exchange ||
-      !rank_lay_out(n_layers, dims, sl, row_pad, n_slabs, o)) {
-    snprintf(s_err, sizeof(s_err), "bad argument or unsupported model (widths multiples of 4, <= 256 classes, 1..%d layers, "
-             "n_in of a layer = n_owned of the layer below)", CSL_MAX_LAYERS);
-    return CSL_E_INVALID;
-  }
-  if (!workspace_fits(o.total, workspace, workspace_floats)) return CSL_E_INVALID;
-  const int L = n_layers;
-  float* ws = workspace;
-  const GradSlots gs(grads, L, dims);
-#define XCHG(layer, backward, src, dst, width)                                                     \
-  do {                                                                                             \
-    const int rc_ = exchange(user, (layer), (backward), (src), (dst), (width), stream);            \
-    if (rc_ < 0) {                                                                                 \
-      snprintf(s_err, sizeof(s_err), "the exchange callback failed (%d), layer %d, %s", rc_, (layer), \
-               (backward) ? "backward" : "forward");                                               \
-      return rc_;                                                                                  \
-    }                                                                                              \
-  } while (0)
-  // `wait` given: `exchange` only STARTS the exchange (on a stream of the caller's) and `wait` makes `stream` wait for
-  // it -- called right before the received rows are first used, so the rows that never leave the GPU are aggregated
-  // while the boundary rows travel (dist_sageconv.py:57-64 on a side stream)
-#define XWAIT(layer, backward)                                                                     \
-  do {                                                                                             \
-    if (wait) {                                                                                    \
-      const int rc_ = wait(user, (layer), (backward), stream);                                     \
-      if (rc_ < 0) {                                                                               \
-        snprintf(s_err, sizeof(s_err), "the exchange-wait callback failed (%d), layer %d", rc_, (layer)); \
-        return rc_;                                                                                \
-      }                                                                                            \
-    }                                                                                              \
-  } while (0)
-  // ---- forward
-  for (k = 0; k < L; k++) {
-    const int32_t in = dims[k], out = dims[k + 1];
-    const csl_sage_rank_slice& s = sl[k];
-    // the deepest layer reads the resident feature rows through feat_rows (no gathered input matrix)
-    const void* x = k == 0 ? feat : ws + o.y[k - 1];
-    const int32_t xk = k == 0 ? kind : 0;   // (only the feature table may be 16-bit)
-    const int64_t ldx = k == 0 ? ldf : (int64_t)in;
-    const int32_t* map = k == 0 ? feat_rows : nullptr;
-    if (k == 0 && o.wpack >= 0) {
-      // no boundary rows: the single-GPU layer as one kernel (gather -> fp32 MFMA -> bias + ReLU); the CSR degree IS the
-      // true degree, the owned rows ARE the out rows.  "No boundary rows" is a property of THIS part's slice: a peer may
-      // have some in the same minibatch, and the exchange is a collective every rank must enter -- so it is issued here
-      // too, with the empty buffers (whether a collective is entered depends only on L, which all ranks share)
-      XCHG(0, 0, ws + o.send[0], ws + o.recv[0], in);
-      XWAIT(0, 0);
-      STEP(rd::sage_fwd_mfma(s.indptr, s.indices, s.self_ids_in, feat_rows, feat, kind, ldf, weights[0], 2 * (int64_t)in,
-                             biases[0], s.n_owned, o.mp[0], in, out, 0, L > 1 ? 1 : 0, ws + o.cat[0], 2 * (int64_t)in,
-                             ws + o.y[0], out, ws + o.wpack, stream));
-      continue;
-    }
-    // partial sums of the rows peers own, straight into the send buffer; then the rows this part owns
-    STEP(rd::spmm_sum_map(s.indptr, s.indices, s.from_all, s.n_from, x, xk, ldx, map, ws + o.send[k], in, in, 1, stream));
-    XCHG(k, 0, ws + o.send[k], ws + o.recv[k], in);
-    STEP(rd::spmm_sum_map(s.indptr, s.indices, s.owned_out_nodes, s.n_owned, x, xk, ldx, map, ws + o.agg[k], in, in, 0, stream));
-    XWAIT(k, 0);
-    STEP(csl_scatter_add_rows_atomic_f32(ws + o.agg[k], in, s.to_all, s.n_to, ws + o.recv[k], in, in, stream));
-    STEP(rd::sage_cat(nullptr, nullptr, s.self_ids_in, s.owned_out_nodes, s.owned_degree, map, x, xk, ldx, ws + o.agg[k], in,
-                      s.n_owned, o.mp[k], ws + o.cat[k], 2 * (int64_t)in, in, 0, stream));
-    STEP(csl_gemm_f32(0, 1, o.mp[k], out, 2 * (int64_t)in, ws + o.cat[k], 2 * (int64_t)in, 0, weights[k], 2 * (int64_t)in, 0,
-                      ws + o.y[k], out, 0, 1, biases[k], k + 1 < L ? 1 : 0, stream));
-  }
-  Deferred later;
-  // ---- loss over the seeds this part owns (the caller's `scale` = 1 / seeds of the WHOLE minibatch)
-  k = L - 1;
-  {
-    const int32_t C = dims[L];
-    STEP(csl_softmax_ce_partial_f32(ws + o.y[k], C, sl[k].n_owned, o.mp[k], C, seed_ids, label_rows, labels, scale,
-                                    ws + o.gy[k], C, ws + o.lpart, ws + o.bpart[k], stream));
-    later.add(ws + o.bpart[k], o.bblocks[k], C, gs.gb[k]);
-    later.add(ws + o.lpart, o.lblocks, 1, loss);
-  }
-  // ---- backward
-  for (k = L - 1; k >= 0; k--) {
-    const int32_t in = dims[k], out = dims[k + 1];
-    const csl_sage_rank_slice& s = sl[k];
-    const int64_t mp = o.mp[k];
-    STEP(weight_grad(-1, o, k, dims, n_slabs, ws, gs.gW[k], later, stream));
-    if (k == 0) break;   // (no gradient flows into the input features; the deepest layer's exchange has no backward)
-    STEP(csl_gemm_f32(0, 0, mp, 2 * (int64_t)in, out, ws + o.gy[k], out, 0, weights[k], 2 * (int64_t)in, 0, ws + o.gcat[k],
-                      2 * (int64_t)in, 0, 1, nullptr, 0, stream));
-    if (s.t_indptr && s.t_indices) {
-      // BY SOURCE: the operand gradient goes into out-row order (mean half / true degree), the rows peers own get theirs
-      // from the reverse exchange, and ONE gather over the part's slice by source writes the input gradient with the ReLU
-      // mask of the layer below, its padding and its bias sums -- no atomics, no zero fill
-      float* g2 = ws + o.g2[k];
-      STEP(csl_sage_rank_g2_f32(s.owned_out_nodes, s.owned_degree, s.n_owned, ws + o.gcat[k], 2 * (int64_t)in, g2, 2 * (int64_t)in,
-                                in, stream));
-      // what this part received forward gets its gradient back (the mean halves of the owned rows it was merged into)
-      STEP(csl_gather_rows_f32(g2 + in, 2 * (int64_t)in, s.to_all, s.n_to, ws + o.recv[k], in, in, stream));
-      XCHG(k, 1, ws + o.recv[k], ws + o.send[k], in);
-      XWAIT(k, 1);
-      STEP(csl_scatter_rows_f32(g2 + in, 2 * (int64_t)in, s.from_all, s.n_from, ws + o.send[k], in, in, stream));
-      if (o.mp[k - 1] > 0) {
-        if (s.t_max_len > CSL_T_SORTED_MAX)
-          STEP(csl_sage_cat_bwd_t_hub_f32(s.t_indptr, s.t_indices, s.t_entries, nullptr, g2, 2 * (int64_t)in, ws + o.y[k - 1], in,
-                                          s.n_in, o.mp[k - 1], ws + o.gy[k - 1], in, nullptr, ws + o.bpart[k - 1], in, stream));
-        else
-          STEP(csl_sage_cat_bwd_t_f32(s.t_indptr, s.t_indices, nullptr, g2, 2 * (int64_t)in, ws + o.y[k - 1], in, s.n_in,
-                                      o.mp[k - 1], ws + o.gy[k - 1], in, nullptr, ws + o.bpart[k - 1], in, stream));
-      }
-      later.add(ws + o.bpart[k - 1], o.mp[k - 1] > 0 ? o.bblocks[k - 1] : 0, in, gs.gb[k - 1]);
-      continue;
-    }
-    // operand gradient -> self rows of gx and owned rows of the merged sums' gradient (both zeroed inside)
-    STEP(csl_sage_cat_rows_bwd_f32(s.self_ids_in, s.owned_out_nodes, s.owned_degree, s.n_owned, ws + o.gcat[k],
-                                   2 * (int64_t)in, ws + o.gx[k], s.n_in, ws + o.agg[k], s.n_out, in, stream));
-    // what this part received forward gets its gradient back; the reverse exchange returns the gradients of the
-    // partial sums this part sent
-    STEP(csl_gather_rows_f32(ws + o.agg[k], in, s.to_all, s.n_to, ws + o.recv[k], in, in, stream));
-    XCHG(k, 1, ws + o.recv[k], ws + o.send[k], in);
-    STEP(csl_spmm_sum_bwd_f32(s.indptr, s.indices, s.owned_out_nodes, s.n_owned, ws + o.agg[k], in, 0, ws + o.gx[k], in, in,
-                              stream));
-    XWAIT(k, 1);
-    STEP(csl_spmm_sum_bwd_f32(s.indptr, s.indices, s.from_all, s.n_from, ws + o.send[k], in, 1, ws + o.gx[k], in, in,
-                              stream));
-    // ReLU mask of the layer below, padding of its GEMM operand, its bias column sums (first stage)
-    if (o.mp[k - 1] > 0)
-      STEP(csl_relu_bwd_colsum_f32(ws + o.gx[k], in, ws + o.y[k - 1], in, s.n_in, o.mp[k - 1], ws + o.gy[k - 1], in,
-                                   nullptr, ws + o.bpart[k - 1], in, stream));
-    later.add(ws + o.bpart[k - 1], o.mp[k - 1] > 0 ? o.bblocks[k - 1] : 0, in, gs.gb[k - 1]);
-  }
-  k = -1;
-  STEP(later.finish(stream));
-#undef XCHG
-#undef XWAIT
-  return CSL_OK;
+  return sage_step(n_layers, dims, Layers(n_layers, sl), weights, biases, feat, kind, ldf, feat_rows, seed_ids, nullptr, nullptr,
+                   scale, row_pad, n_slabs, nullptr, grads, loss, workspace, workspace_floats, stream, plain ? nullptr : &drop, &multi);
 }
 
 int csl_sage_rank_fwd_bwd_f32(int32_t n_layers, const int32_t* dims, const csl_sage_rank_slice* sl,
@@ -689,8 +617,9 @@ int csl_sage_rank_fwd_bwd_f32(int32_t n_layers, const int32_t* dims, const csl_s
                               const int64_t* labels, float scale, int64_t row_pad, int32_t n_slabs,
                               csl_exchange_fn exchange, csl_exchange_wait_fn wait, void* user, float* grads, float* loss,
                               float* workspace, int64_t workspace_floats, void* stream) {
-  return sage_rank_fwd_bwd(n_layers, dims, sl, weights, biases, feat, 0, ldf, feat_rows, seed_ids, label_rows, labels, scale,
-                           row_pad, n_slabs, exchange, wait, user, grads, loss, workspace, workspace_floats, stream);
+  const Exchange xc = {exchange, wait, user, stream};
+  return sage_step(n_layers, dims, Layers(n_layers, sl), weights, biases, feat, 0, ldf, feat_rows, seed_ids, label_rows, labels,
+                   scale, row_pad, n_slabs, &xc, grads, loss, workspace, workspace_floats, stream, nullptr, nullptr);
 }
 
 int csl_sage_rank_fwd_bwd_x16(int32_t n_layers, const int32_t* dims, const csl_sage_rank_slice* sl,
@@ -700,8 +629,9 @@ int csl_sage_rank_fwd_bwd_x16(int32_t n_layers, const int32_t* dims, const csl_s
                               csl_exchange_fn exchange, csl_exchange_wait_fn wait, void* user, float* grads, float* loss,
                               float* workspace, int64_t workspace_floats, void* stream) {
   if (table16_refused(feat, kind, ldf)) return CSL_E_INVALID;
-  return sage_rank_fwd_bwd(n_layers, dims, sl, weights, biases, feat, kind, ldf, feat_rows, seed_ids, label_rows, labels,
-                           scale, row_pad, n_slabs, exchange, wait, user, grads, loss, workspace, workspace_floats, stream);
+  const Exchange xc = {exchange, wait, user, stream};
+  return sage_step(n_layers, dims, Layers(n_layers, sl), weights, biases, feat, kind, ldf, feat_rows, seed_ids, label_rows, labels,
+                   scale, row_pad, n_slabs, &xc, grads, loss, workspace, workspace_floats, stream, nullptr, nullptr);
 }
 
 }  // extern "C"

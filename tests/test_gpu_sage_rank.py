@@ -6,7 +6,10 @@
   communicator, no process group, nothing that could hang;
 * its numbers: the ranks' summed loss and gradients against tests/sage_ref.py (float64) on the ORACLE's traversal of the
   same seeds, ranks over gloo on one GPU (worlds of 2, 3 and 4, sequential and side-stream exchanges, backward by
-  destination and by source, partitions that leave a rank without boundary rows and without any row).
+  destination and by source, partitions that leave a rank without boundary rows and without any row);
+* the branches it shares with the single-GPU step (row padding, weight-gradient slabs, hub lists by source, one to four
+  layers, the deepest layer fused and not), which the widths above do not reach: a world of one over the table of
+  tests/test_gpu_sage_step.py, against the same float64 model.
 
 Tolerances (north_star, as tests/test_gpu_step_bench_widths.py): loss 1e-5 relative, every parameter gradient within 1e-4
 of its largest entry.
@@ -205,25 +208,76 @@ def test_a_world_of_one_starts_no_exchange():
 
 # ---- D: the ranks' sum against float64 on the oracle's traversal -----------------------------------------------------
 
-def _check_against_float64(indptr, indices, seeds, feats, labels, model, got_loss, got_grads, n, frontiers=None):
+def _check_against_float64(indptr, indices, seeds, feats, labels, model, got_loss, got_grads, n, frontiers=None, fan=FAN):
     import sage_ref
     from oracle import oracle as orc
-    trav = orc.Oracle(indptr, indices, n_parts=1, fanouts=FAN).sample(seeds)
+    trav = orc.Oracle(indptr, indices, n_parts=1, fanouts=fan).sample(seeds)
     if frontiers is not None:
         # the same sample: the ranks' owned rows add up to the oracle's frontier at every layer
         for l, rows in enumerate(frontiers):
             assert np.array_equal(np.sort(rows), np.sort(np.asarray(trav["frontier"][l]))), "frontier of hop %d" % l
     ws, bs = [c.fc.weight for c in model.convs], [c.fc.bias for c in model.convs]
     want_loss, want = sage_ref.model_on_traversal(trav, feats, labels, ws, bs, n)
+    print("loss %.9g (float64 %.9g)" % (got_loss, want_loss))
     assert abs(got_loss - want_loss) <= 1e-5 * abs(want_loss), (got_loss, want_loss)
     at = 0
     for k, g in enumerate(want):
         seg = got_grads[at:at + g.numel()].reshape(g.shape)
         at += g.numel()
         err, ref = float((seg - g).abs().max()), float(g.abs().max())
+        print("gradient %d: max error %.3g, largest entry %.3g" % (k, err, ref))
         assert err <= 1e-4 * ref, "gradient %d (%s of layer %d): max error %.3g against a largest entry of %.3g" % (
             k, "weight" if k % 2 == 0 else "bias", k // 2, err, ref)
     assert at == got_grads.numel()
+
+
+def _world_of_one_cases():
+    """the single-GPU step's table (at most 256 classes: a rank has no separate column-sum pass), the slice by source
+    present; and one row without it: the atomic fallback"""
+    from test_gpu_sage_step import CASES
+    return [c + (True,) for c in CASES if c[2] <= 256] + [(3, (5, 4, 3), 5, 64, 4, "random", True, False)]
+
+
+@pytest.mark.parametrize("L,fan,classes,row_pad,n_slabs,graph,fused,by_source", _world_of_one_cases())
+def test_a_world_of_one_matches_float64_on_the_oracle_traversal(L, fan, classes, row_pad, n_slabs, graph, fused, by_source,
+                                                                monkeypatch):
+    """The rank step where it runs the code it shares with the single-GPU step: no padding, padding to row_pad and to
+    256, slabs that do and do not divide the rows, L = 1 .. 4, hub lists by source, the deepest layer fused and not."""
+    from cslicer import _abi, aggr, splitgnn
+    from test_gpu_sage_step import _graph
+    _abi.load()
+    if not fused:
+        monkeypatch.setenv("CSLICER_NO_MFMA_FWD", "1")
+    n, f0, hidden, B = 20000, 12, 24, 200
+    indptr, indices = _graph(graph, n)
+    rng = np.random.default_rng(7)
+    feats_np = rng.standard_normal((n, f0)).astype(np.float32)
+    labels_np = rng.integers(0, classes, size=n).astype(np.int64)
+    seeds = rng.permutation(n)[:B]
+    torch.manual_seed(L)
+    model = splitgnn.DistSAGEModel(f0, hidden, classes, n_layers=L).cuda()
+    with torch.no_grad():
+        for c in model.convs:
+            c.fc.bias.normal_(0, 0.3)
+    eng = _abi.Engine(indptr, indices, n_parts=1, fanouts=fan, max_batch=B, n_streams=1, mode=_abi.MODE_GRAPH,
+                      flags=_abi.FLAG_TRANSPOSE if by_source else 0, part_mask=1)
+    try:
+        eng.submit_seeds([seeds])
+        sl = splitgnn.slices_of(eng, parts=[0])
+        slices = [sl[L - 1 - k][0] for k in range(L)]
+        assert slices[-1].n_owned == B
+        if graph == "hub" and L > 1:
+            assert max(s.t_max_len for s in slices[1:]) > _abi.T_SORTED_MAX
+        comm = _RecordingComm(1)
+        step = aggr.SageRankStep(model, row_pad, n_slabs, comm)
+        feats, labels = torch.from_numpy(feats_np).cuda(), torch.from_numpy(labels_np).cuda()
+        for _ in range(2):   # (the second call runs on the recorded GEMM plans and the reused workspace)
+            loss = run_step(step, slices, feats, labels, B)
+        assert comm.calls == []
+        got_loss, got = float(loss), step.grads.double().cpu()
+    finally:
+        eng.close()
+    _check_against_float64(indptr, indices, seeds, feats_np, labels_np, model, got_loss, got, n, fan=fan)
 
 
 def _free_port():

@@ -29,7 +29,8 @@ def _graph(kind, n, seed=0):
     return indptr, rng.integers(0, n, size=int(indptr[-1])).astype(np.int64)
 
 
-@pytest.mark.parametrize("L,fan,classes,row_pad,n_slabs,graph,fused", [
+# (L, fan, classes, row_pad, n_slabs, graph, fused); tests/test_gpu_sage_rank.py runs the rows of at most 256 classes too
+CASES = [
     (2, (6, 4), 7, 0, 4, "random", True),          # no padding at all
     (2, (6, 4), 7, 64, 4, "random", True),         # rows up to a multiple of 64; 4 slabs divide them
     (2, (6, 4), 7, 64, 3, "random", False),        # ... 3 slabs do not divide every layer's rows
@@ -41,7 +42,10 @@ def _graph(kind, n, seed=0):
     (2, (8, 6), 7, 64, 4, "hub", True),            # hub lists by source in the upper layer
     (3, (6, 4, 3), 300, 64, 4, "random", True),    # more than 256 classes
     (2, (8, 6), 300, 0, 1, "hub", False),
-])
+]
+
+
+@pytest.mark.parametrize("L,fan,classes,row_pad,n_slabs,graph,fused", CASES)
 def test_native_step_at_small_widths_matches_float64_on_the_oracle_traversal(L, fan, classes, row_pad, n_slabs, graph,
                                                                                fused, monkeypatch):
     import sage_ref
