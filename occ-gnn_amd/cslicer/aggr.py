@@ -20,6 +20,7 @@ SYMBOLS, FEAT16_SYMBOLS = _abi.BOUND["cslicer_aggr.h"], _abi.BOUND["cslicer_feat
 GAT_IN16_SYMBOLS = _abi.BOUND["cslicer_gat_in16.h"]   # the attention input layer over a 16-bit table (forward AND backward)
 DROPOUT_SYMBOLS = _abi.BOUND["cslicer_dropout.h"]     # dropout between the GraphSAGE layers: the kernel and the native step with it
 MULTILABEL_SYMBOLS = _abi.BOUND["cslicer_multilabel.h"]   # the sigmoid-BCE loss, the micro-F1 head, the native step with that loss
+OPTIM_SYMBOLS = _abi.BOUND["cslicer_optim.h"]             # the optimizer step with weight decay, clipping and the non-finite guard
 EXCHANGE_FN, EXCHANGE_WAIT_FN = _abi.EXCHANGE_FN, _abi.EXCHANGE_WAIT_FN
 # element kinds of a 16-bit feature table (CSL_FEAT_F16 / CSL_FEAT_BF16); a float32 table has the fp32 entry points
 FEAT_KINDS = {torch.float16: 1, torch.bfloat16: 2}
@@ -1245,25 +1246,61 @@ def attention_gather(indptr, indices, u_in, v_in, n_rows):
 
 
 class Adam(object):
-    """torch.optim.Adam's update (lr, betas, eps; no weight decay, no amsgrad: what python/train.py:83 uses) for a
-    handful of fp32 CUDA parameters in ONE HIP launch per step (csl_adam_f32).  Same interface as far as the
-    trainer needs it: zero_grad(set_to_none=True), step(); the moments live in `state`."""
+    """torch.optim.Adam's update (lr, betas, eps; no amsgrad: what python/train.py:83 uses) for a handful of fp32 CUDA
+    parameters in ONE HIP launch per step (csl_adam_f32).  Same interface as far as the trainer needs it:
+    zero_grad(set_to_none=True), step(); the moments live in `state`.
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
+    weight_decay: a number for every tensor, or one per tensor (0: that tensor is not decayed).  decoupled=True
+    (default): torch.optim.AdamW's form, p <- p (1 - lr wd) before the update; False: torch.optim.Adam(weight_decay=)'s,
+    wd p added to the gradient.
+    max_grad_norm: None (default), or a number > 0: the gradients are scaled by min(1, max_grad_norm / (norm + 1e-6)),
+    norm the 2-norm over ALL tensors (torch.nn.utils.clip_grad_norm_), summed in float64 on the device in a fixed order
+    (one more launch); and a step whose norm is not finite -- a NaN or Inf in any gradient -- is SKIPPED on the device:
+    parameters and moments keep their bits, `skipped` goes up by one.  float("inf") gives the norm and the guard without
+    ever clipping.  `self.t` advances on a skipped step too (the host is not told: step() never synchronises).
+    `grad_norm` (1 float32 on the device; None without max_grad_norm) is the last step's norm, `skipped` (1 int32 on the
+    device) the count of skipped steps: reading them is the caller's synchronisation.
+
+    With every decay 0 and max_grad_norm None, step() is the csl_adam_f32 call it always was; anything else goes through
+    csl_adamw_f32 (include/cslicer_optim.h), which with a clip coefficient of 1 and no decay gives bitwise the same."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=True,
+                 max_grad_norm=None):
         self.params = [p for p in params]
         if not self.params or len(self.params) > 24:
             raise ValueError("1..24 parameter tensors")
+        n = len(self.params)
+        wd = [float(w) for w in weight_decay] if hasattr(weight_decay, "__len__") else [float(weight_decay)] * n
+        if len(wd) != n:
+            raise ValueError("weight_decay: one value, or one per parameter tensor (%d), not %d" % (n, len(wd)))
+        if not all(w >= 0.0 for w in wd):      # (a NaN compares false)
+            raise ValueError("weight_decay must be >= 0, not %r" % (weight_decay,))
+        if max_grad_norm is not None:
+            max_grad_norm = float(max_grad_norm)
+            if not max_grad_norm > 0.0:
+                raise ValueError("max_grad_norm must be None or > 0 (float('inf'): norm and guard, no clipping), not %r"
+                                 % (max_grad_norm,))
         for p in self.params:
             if p.dtype != torch.float32 or not p.is_cuda or not p.is_contiguous():
                 raise TypeError("contiguous float32 CUDA parameters expected")
         self.lr, self.betas, self.eps, self.t = float(lr), (float(betas[0]), float(betas[1])), float(eps), 0
+        self.weight_decay, self.decoupled, self.max_grad_norm = wd, bool(decoupled), max_grad_norm
         self.state = [(torch.zeros_like(p), torch.zeros_like(p)) for p in self.params]
-        n = len(self.params)
         self._p = (C.c_void_p * n)(*[p.data_ptr() for p in self.params])
         self._m = (C.c_void_p * n)(*[m.data_ptr() for m, _ in self.state])
         self._v = (C.c_void_p * n)(*[v.data_ptr() for _, v in self.state])
         self._n = (C.c_int64 * n)(*[p.numel() for p in self.params])
         self._g = (C.c_void_p * n)()
+        self._wd = (C.c_float * n)(*wd)
+        self._plain = max_grad_norm is None and not any(wd)     # today's csl_adam_f32 call
+        dev = self.params[0].device
+        self.skipped = torch.zeros((1,), dtype=torch.int32, device=dev)
+        self.grad_norm = self._scratch = None
+        if max_grad_norm is not None:
+            self.grad_norm = torch.zeros((1,), dtype=torch.float32, device=dev)
+            nbytes = int(_lib().csl_adamw_scratch(n, self._n))
+            _chk(nbytes, "csl_adamw_scratch")
+            self._scratch = torch.empty((max(nbytes, 8) // 8,), dtype=torch.float64, device=dev)
 
     def zero_grad(self, set_to_none=True):
         for p in self.params:
@@ -1288,5 +1325,11 @@ class Adam(object):
                 g = p.grad = g.contiguous()
             self._g[k] = g.data_ptr()
         self.t += 1
-        _chk(_lib().csl_adam_f32(len(self.params), self._p, self._g, self._m, self._v, self._n, self.lr,
-                                 self.betas[0], self.betas[1], self.eps, self.t, _stream()), "csl_adam_f32")
+        if self._plain:
+            _chk(_lib().csl_adam_f32(len(self.params), self._p, self._g, self._m, self._v, self._n, self.lr,
+                                     self.betas[0], self.betas[1], self.eps, self.t, _stream()), "csl_adam_f32")
+            return
+        _chk(_lib().csl_adamw_f32(len(self.params), self._p, self._g, self._m, self._v, self._n, self._wd,
+                                  1 if self.decoupled else 0, self.max_grad_norm or 0.0, self.lr, self.betas[0],
+                                  self.betas[1], self.eps, self.t, _p(self.grad_norm), _p(self.skipped),
+                                  _p(self._scratch), _stream()), "csl_adamw_f32")

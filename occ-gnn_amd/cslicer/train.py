@@ -14,6 +14,7 @@ The print keys of train.py:101-103 are kept (`avg forward time`, `batch slice ti
 one is reported as 0).
 """
 import collections
+import math
 import os
 import time
 
@@ -134,7 +135,8 @@ class Trainer(object):
                  batch=1024, streams=8, hidden=256, lr=1e-3, device=0, dist=None, seed=0, overlap=False,
                  model="sage", heads=8, rank_path=None, workload=None, feat_dim=None, rng_seed=5489,
                  feature_dtype="float32", gat_input=None, replace=True, dropout=0.0, dropout_seed=None,
-                 multilabel=False):
+                 multilabel=False, weight_decay=0.0, decoupled_weight_decay=True, decay_bias=False, max_grad_norm=None,
+                 lr_schedule=None):
         """Part `rank` of `world`.  Ownership = the engine's workload table (`workload` int32 [N], the METIS map of
         python/utils/sampler.py:64-134 / partition_map_opt.bin; None = v % world like pyfrontend.cpp:57): the rank
         keeps the feature and label rows of the nodes it owns, in ascending node order.
@@ -181,6 +183,18 @@ class Trainer(object):
         sequencer has no multi-label loss).  evaluate() then reports micro-F1.  Dropout, a 16-bit table and
         replace=False combine with it unchanged.
 
+        weight_decay (default 0: none): the optimizer's weight decay (aggr.Adam, csl_adamw_f32).
+        decoupled_weight_decay=True: AdamW's p <- p (1 - lr wd); False: the L2 term wd p added to the gradient
+        (torch.optim.Adam(weight_decay=)).  decay_bias=False: only parameters with ndim >= 2 decay (the layers' weight
+        matrices, the attention model's attn_l / attn_r), bias vectors do not; True: every parameter.
+        max_grad_norm (default None: off): a number > 0 clips the gradient's global 2-norm to it
+        (torch.nn.utils.clip_grad_norm_) and SKIPS, on the device, a step whose gradient holds a NaN or an Inf: weights and
+        moments are left as they were.  float("inf"): the norm and the guard, never a clip.  On the rank path and in the
+        data-parallel trainer the norm is that of the all-reduced gradient: the same on every rank, the weights stay
+        replicated.  `self.opt.grad_norm` / `self.opt.skipped` (device tensors) hold the last norm and the skipped count.
+        lr_schedule (default None: `lr` throughout): a callable steps_done -> learning rate, evaluated before every step
+        and stored into `self.opt.lr` (lr_schedule() below builds warm-up + constant / cosine ones).
+
         `self.plan` is the StepPlan of the configuration (step_plan above): which step the trainer runs, decided here
         once; `self.native` / `self.native_rank` are the native stepper of that path, None on every other path."""
         # -- 1. the arguments (before any device call: a request that cannot be served is an error, never a quiet fall-back)
@@ -205,6 +219,17 @@ class Trainer(object):
         if dropout > 0 and hidden % 4 != 0:
             raise ValueError("dropout > 0: hidden must be a multiple of 4 (the kernel moves float4 columns), not %d" % hidden)
         self.dropout, self.dropout_seed = dropout, int(seed if dropout_seed is None else dropout_seed)
+        weight_decay = float(weight_decay)
+        if not weight_decay >= 0.0:      # (a NaN compares false)
+            raise ValueError("weight_decay must be >= 0, not %r" % (weight_decay,))
+        if max_grad_norm is not None:
+            max_grad_norm = float(max_grad_norm)
+            if not max_grad_norm > 0.0:
+                raise ValueError("max_grad_norm must be None or > 0 (float('inf'): the norm and the non-finite guard "
+                                 "without clipping), not %r" % (max_grad_norm,))
+        if lr_schedule is not None and not callable(lr_schedule):
+            raise ValueError("lr_schedule must be None or a callable steps_done -> lr, not %r" % (lr_schedule,))
+        self.lr_schedule = lr_schedule
         if not replace and max(fanouts) > _abi.noreplace_max_fanout():
             raise ValueError("replace=False: fanouts %r exceed the limit of %d neighbours per row"
                              % (tuple(fanouts), _abi.noreplace_max_fanout()))
@@ -305,7 +330,9 @@ class Trainer(object):
             raise ValueError("model must be 'sage' or 'gat'")
         # -- 6. torch.optim.Adam's update in one HIP launch per step (the library's for-each form is eight small
         # launches, ~0.1 ms of GPU time per step; its fused form one of 42 us for these six small tensors)
-        self.opt = aggr.Adam(list(self.model.parameters()), lr=lr)
+        params = list(self.model.parameters())
+        self.opt = aggr.Adam(params, lr=lr, decoupled=bool(decoupled_weight_decay), max_grad_norm=max_grad_norm,
+                             weight_decay=[weight_decay if (decay_bias or p.dim() >= 2) else 0.0 for p in params])
         # data-parallel replicas: called with the flat gradient, sums it over the ranks' shares of the minibatch
         self.grad_sync = None
         # rank path, autograd step: called with the flat gradient right after its all-reduce (what the optimizer applies)
@@ -351,6 +378,8 @@ class Trainer(object):
             u["rows"] += sl.n_owned
             u["src"] += sl.n_in
             u["edges"] += sl.n_edges
+        if self.lr_schedule is not None:
+            self.opt.lr = float(self.lr_schedule(self.steps_done))
         loss = self._path_step(slices, layers, int(meta.n_seeds), stream, slot)    # (_step_<plan.path>)
         self.steps_done += 1
         return loss
@@ -585,8 +614,12 @@ class Trainer(object):
     def report(self):
         n = max(self.steps_done, 1)
         # keys of python/train.py:101-103 (parsed by experiments/exp6/occ.py:21-23)
-        return ("avg forward time: %.6f sec\nbatch slice time: %.6f sec\ncache refresh time: %.6f sec"
-                % (self.t_forward / n, self.t_slice / n, 0.0))
+        out = ("avg forward time: %.6f sec\nbatch slice time: %.6f sec\ncache refresh time: %.6f sec"
+               % (self.t_forward / n, self.t_slice / n, 0.0))
+        if self.opt.grad_norm is not None:     # (clipping on: two more lines; reading the two elements waits for the stream)
+            out += "\nlast gradient norm: %.6g\nskipped steps (non-finite gradient): %d" % (
+                float(self.opt.grad_norm), int(self.opt.skipped))
+        return out
 
     # -- evaluation: full-neighbour, layer-wise inference of the model as trained (cslicer.infer)
     def _infer_args(self):
@@ -677,6 +710,31 @@ class DataParallelTrainer(Trainer):
 
     def _loss_den(self, stream, slot, n_seeds):
         return self._den[(stream, slot)]
+
+
+def lr_schedule(kind, base_lr, warmup=0, total=0, min_lr=0.0):
+    """A learning-rate schedule for Trainer(lr_schedule=...): the callable t -> lr, t the steps done so far.
+        t < warmup:  base_lr (t + 1) / warmup                       (linear warm-up; its last step runs at base_lr)
+        then `constant`: base_lr;
+             `cosine`:   min_lr + (base_lr - min_lr) (1 + cos(pi (t - warmup) / (total - warmup))) / 2 for t < total, half
+                         a cosine from base_lr at the end of the warm-up down to min_lr at t = total, min_lr from there on."""
+    if kind not in ("constant", "cosine"):
+        raise ValueError("lr schedule kind must be 'constant' or 'cosine', not %r" % (kind,))
+    base_lr, min_lr, warmup, total = float(base_lr), float(min_lr), int(warmup), int(total)
+    if warmup < 0 or not base_lr > 0.0 or not 0.0 <= min_lr <= base_lr:
+        raise ValueError("lr schedule: warmup >= 0 and 0 <= min_lr <= base_lr, base_lr > 0 expected")
+    if kind == "cosine" and total <= warmup:
+        raise ValueError("cosine lr schedule: total (%d) must exceed warmup (%d)" % (total, warmup))
+
+    def at(t):
+        if t < warmup:
+            return base_lr * (t + 1) / warmup
+        if kind == "constant":
+            return base_lr
+        if t >= total:
+            return min_lr
+        return min_lr + (base_lr - min_lr) * 0.5 * (1.0 + math.cos(math.pi * (t - warmup) / (total - warmup)))
+    return at
 
 
 TUNED_GEMMS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "tunableop_gfx950.csv")
@@ -774,7 +832,39 @@ def _parser():
     ap.add_argument("--multilabel", action="store_true",
                     help="(extra) multi-label classification (`Trainer(multilabel=True)`): sigmoid + binary cross-entropy "
                          "over n_classes targets per node, evaluation by micro-F1; an L0 directory must say multilabel=1")
+    ap.add_argument("--weight-decay", type=float, default=None,
+                    help="(extra) the optimizer's weight decay (`Trainer(weight_decay=...)`), decoupled (AdamW) unless "
+                         "--adam-l2; weight matrices only unless --decay-bias")
+    ap.add_argument("--adam-l2", action="store_true",
+                    help="(extra) --weight-decay as an L2 term of the gradient, torch.optim.Adam(weight_decay=)'s form "
+                         "(`Trainer(decoupled_weight_decay=False)`)")
+    ap.add_argument("--decay-bias", action="store_true", help="(extra) decay the bias vectors too (`Trainer(decay_bias=True)`)")
+    ap.add_argument("--clip-grad-norm", type=float, default=None,
+                    help="(extra) clip the gradient's global 2-norm to this value and skip a step whose gradient is not "
+                         "finite (`Trainer(max_grad_norm=...)`); inf: the norm and the guard only")
+    ap.add_argument("--lr-warmup", type=int, default=None, help="(extra) linear learning-rate warm-up over this many steps")
+    ap.add_argument("--lr-schedule", choices=("constant", "cosine"), default=None,
+                    help="(extra) after the warm-up: --lr throughout, or half a cosine down to --lr-min at the last step "
+                         "of the last epoch (`train.lr_schedule`)")
+    ap.add_argument("--lr-min", type=float, default=None, help="(extra) where the cosine schedule ends (default 0)")
     return ap
+
+
+def _optimizer_kw(a, steps_per_epoch):
+    """the Trainer keywords of the optimizer options, each only where its option was given"""
+    kw = {}
+    if a.weight_decay is not None:
+        kw["weight_decay"] = a.weight_decay
+    if a.adam_l2:
+        kw["decoupled_weight_decay"] = False
+    if a.decay_bias:
+        kw["decay_bias"] = True
+    if a.clip_grad_norm is not None:
+        kw["max_grad_norm"] = a.clip_grad_norm
+    if a.lr_warmup is not None or a.lr_schedule is not None or a.lr_min is not None:
+        kw["lr_schedule"] = lr_schedule(a.lr_schedule or "constant", a.lr, warmup=a.lr_warmup or 0,
+                                        total=a.num_epochs * steps_per_epoch, min_lr=a.lr_min or 0.0)
+    return kw
 
 
 def _split(a, n):
@@ -821,12 +911,19 @@ def main(argv=None):
     --no-replace (extra): `Trainer(replace=False)`: a row with at least fan-out edges yields that many DISTINCT edges
     (the default of dgl.sampling.sample_neighbors) instead of independent draws.  Every --fan-out number must then be
     <= 64 (_abi.noreplace_max_fanout()).
+    --weight-decay W [--adam-l2] [--decay-bias] (extra): `Trainer(weight_decay=W)`: AdamW's decoupled decay of the weight
+    matrices; --adam-l2: as an L2 term of the gradient instead; --decay-bias: the bias vectors too.
+    --clip-grad-norm M (extra): `Trainer(max_grad_norm=M)`: the gradient's global norm is clipped to M, and a step whose
+    gradient holds a NaN or an Inf is skipped on the device; the report then ends with the last norm and the skipped count.
+    --lr-warmup K, --lr-schedule {constant,cosine}, --lr-min (extra): `Trainer(lr_schedule=train.lr_schedule(...))` with
+    --lr as the base rate and total = --num-epochs x the minibatches of an epoch (--max-steps where it is smaller).
     --multilabel (extra): `Trainer(multilabel=True)`: a node carries a set of classes; the loss is the mean binary
     cross-entropy with logits and rank 0 prints `Eval F1` (micro-F1) where it prints `Eval Acc`.  `synthetic` and the
     presets train on synthetic_multilabels; an L0 directory must hold packed multi-label words (multilabel=1 in its
     meta.txt, cslicer.l0.write_l0 with a 2-D `labels`).
 
         python -m cslicer.train --graph products-like --multilabel --eval-split holdout --max-steps 50
+        python -m cslicer.train --graph products-like --dropout 0.5 --weight-decay 5e-4 --clip-grad-norm 1 --lr-warmup 100 --lr-schedule cosine
         python -m cslicer.train --graph <L0 dir> --feature-dtype bfloat16 --eval-split holdout
         python -m cslicer.train --graph products-like --model-name gat --feature-dtype bfloat16 --gat-input on"""
     a = _parser().parse_args(argv)
@@ -883,13 +980,16 @@ def main(argv=None):
     fan = tuple(int(x) for x in a.fan_out.split(","))[::-1]          # engine order: layer 0 = hop from the seeds
     if len(fan) != a.num_layers:
         fan = fan[:a.num_layers] if len(fan) > a.num_layers else fan
+    n_train = indptr.shape[0] - 1 if train_nodes is None else train_nodes.shape[0]
+    per_epoch = (n_train + a.batch_size - 1) // a.batch_size           # (Trainer.set_nodes' n_batches)
+    per_epoch = per_epoch if a.max_steps <= 0 else min(a.max_steps, per_epoch)
     kind = "gat" if a.model_name == "gat" else "sage"
     hidden = a.num_hidden // a.num_heads if kind == "gat" else a.num_hidden
     tr = Trainer(indptr, indices, feats, labels, n_classes, rank=rank, world=world, fanouts=fan, batch=a.batch_size,
                  streams=8, hidden=max(4, hidden // 4 * 4), lr=a.lr, device=local, dist=dist, model=kind, heads=a.num_heads,
                  workload=workload, feat_dim=fdim, feature_dtype=fdtype,
                  gat_input={"auto": None, "on": True, "off": False}[a.gat_input], replace=not a.no_replace,
-                 dropout=a.dropout, **({"multilabel": True} if a.multilabel else {}))
+                 dropout=a.dropout, **({"multilabel": True} if a.multilabel else {}), **_optimizer_kw(a, per_epoch))
     if rank == 0 and fdtype != "float32":
         print("feature table: %s, %d bytes on this rank" % (fdtype, tr.feat.numel() * tr.feat.element_size()))
     n = indptr.shape[0] - 1

@@ -16,6 +16,7 @@
 
 #include <type_traits>
 
+#include "adam_dev.h"
 #include "cslicer_aggr.h"
 #include "cslicer_feat16.h"
 #include "cslicer_hip.h"
@@ -1097,17 +1098,7 @@ __global__ __launch_bounds__(BLK) void k_reduce_multi(ReduceJobs jb) {
 // ---- Adam (python/train.py:83 torch.optim.Adam, no weight decay, no amsgrad) over every parameter tensor of the
 // model in ONE launch: the model has six small tensors, the library's for-each form is 1-8 launches of 20-40 us.
 //   m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2;  p -= (lr / (1-b1^t)) * m / (sqrt(v) / sqrt(1-b2^t) + eps)
-constexpr int ADAM_MAX = 24;
-struct AdamArgs {
-  float* p[ADAM_MAX];
-  const float* g[ADAM_MAX];
-  float* m[ADAM_MAX];
-  float* v[ADAM_MAX];
-  long long first_block[ADAM_MAX + 1];  // blocks of ADAM_CHUNK elements, tensors back to back
-  long long n[ADAM_MAX];
-  int count;
-};
-constexpr int ADAM_CHUNK = 1024;
+// ADAM_MAX, ADAM_CHUNK, AdamArgs and the per-element update: adam_dev.h, shared with k_adamw (optim.hip)
 __global__ __launch_bounds__(BLK) void k_adam(AdamArgs a, float b1, float b2, float step_size, float inv_sqrt_bc2,
                                               float eps) {
   int t = 0;
@@ -1117,14 +1108,8 @@ __global__ __launch_bounds__(BLK) void k_adam(AdamArgs a, float b1, float b2, fl
   const float* __restrict__ g = a.g[t];
   float* __restrict__ m = a.m[t];
   float* __restrict__ v = a.v[t];
-  for (long long i = base + threadIdx.x; i < base + ADAM_CHUNK && i < a.n[t]; i += BLK) {
-    const float gi = g[i];
-    const float mi = b1 * m[i] + (1.f - b1) * gi;
-    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-    m[i] = mi;
-    v[i] = vi;
-    p[i] -= step_size * mi / (sqrtf(vi) * inv_sqrt_bc2 + eps);
-  }
+  for (long long i = base + threadIdx.x; i < base + ADAM_CHUNK && i < a.n[t]; i += BLK)
+    adam_update(p[i], g[i], m[i], v[i], b1, b2, step_size, inv_sqrt_bc2, eps);
 }
 
 // ---- GAT attention logits: el[r, h] = <z[r, h, :], a_l[h, :]>, er likewise (DistGATConv.project).  A row-wise
