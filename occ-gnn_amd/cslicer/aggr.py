@@ -21,6 +21,7 @@ GAT_IN16_SYMBOLS = _abi.BOUND["cslicer_gat_in16.h"]   # the attention input laye
 DROPOUT_SYMBOLS = _abi.BOUND["cslicer_dropout.h"]     # dropout between the GraphSAGE layers: the kernel and the native step with it
 MULTILABEL_SYMBOLS = _abi.BOUND["cslicer_multilabel.h"]   # the sigmoid-BCE loss, the micro-F1 head, the native step with that loss
 OPTIM_SYMBOLS = _abi.BOUND["cslicer_optim.h"]             # the optimizer step with weight decay, clipping and the non-finite guard
+LOSS_SYMBOLS = _abi.BOUND["cslicer_loss.h"]               # class weights and label smoothing: the loss pass and the native steps with it
 EXCHANGE_FN, EXCHANGE_WAIT_FN = _abi.EXCHANGE_FN, _abi.EXCHANGE_WAIT_FN
 # element kinds of a 16-bit feature table (CSL_FEAT_F16 / CSL_FEAT_BF16); a float32 table has the fp32 entry points
 FEAT_KINDS = {torch.float16: 1, torch.bfloat16: 2}
@@ -365,6 +366,21 @@ def sage_cat_bwd_t(t_indptr, t_indices, indptr, gcat, y, n_src, n_pad, hub=False
 DropSpec = collections.namedtuple("DropSpec", "p seed step")
 
 
+# The options of the single-label loss (cslicer_loss.h): class_weight a float32 device tensor [C] or None (all ones),
+# label_smoothing in [0, 1).  The loss stays scale * SUM over the rows (F.cross_entropy(weight=, label_smoothing=,
+# reduction="sum")): with scale = 1 / seeds it is not torch's weighted "mean", which divides by sum w[y].
+LossSpec = collections.namedtuple("LossSpec", "class_weight label_smoothing")
+
+
+def _loss_args(loss, C_):
+    """(class_weight pointer, label_smoothing) of a LossSpec for a model of C_ classes, checked"""
+    w = loss.class_weight
+    if w is not None and (not torch.is_tensor(w) or w.dtype != torch.float32 or not w.is_cuda or w.dim() != 1
+                          or w.numel() != C_ or not w.is_contiguous()):
+        raise TypeError("LossSpec.class_weight: a contiguous float32 CUDA tensor [%d] or None expected" % C_)
+    return (C.c_void_p(w.data_ptr()) if w is not None else C.c_void_p(0)), float(loss.label_smoothing)
+
+
 def _i64(v):
     """a Python int as the int64 the C ABI takes (its low 64 bits, signed)"""
     v = int(v) & 0xFFFFFFFFFFFFFFFF
@@ -493,14 +509,18 @@ class SageStep(_SageNative):
     (their storage must not move: an optimizer that updates in place, as aggr.Adam does)."""
     _stem, _workspace, _slice = "sage_fwd_bwd", "csl_sage_fwd_bwd_workspace", SageSlice
 
-    def __call__(self, slices, feat, labels, scale, loss_out, drop=None):
+    def __call__(self, slices, feat, labels, scale, loss_out, drop=None, loss=None):
         """slices: the part's `splitgnn.Slice`s in MODEL order (deepest hop first), from an engine with
         FLAG_TRANSPOSE; feat: resident [N, F] features; labels int64 [N]; loss_out: one-element float32 tensor.
         drop: a DropSpec: dropout on the output of every layer but the last (csl_sage_fwd_bwd_dropout), each layer's
         rows keyed by its out-node ids.
         labels int32 [N, W] (pack_labels: a multi-label trainer's): the sigmoid-BCE loss, csl_sage_fwd_bwd_multilabel,
-        with the DropSpec if there is one."""
+        with the DropSpec if there is one.
+        loss: a LossSpec: class weights and / or label smoothing (csl_sage_fwd_bwd_ce, with the DropSpec if there is one);
+        single-label only: with 2-D labels it is a TypeError."""
         A = _abi
+        if loss is not None and labels.dim() == 2:
+            raise TypeError("a LossSpec belongs to the single-label loss: the sigmoid-BCE loss has no weights")
         for k, s in enumerate(slices):
             # (an EMPTY layer -- a rank's empty share of a short minibatch -- has no row pointers at all)
             if k and s.count(A.T_INDPTR) != s.n_in + 1 and (s.n_in or s.n_out or s.count(A.T_INDPTR)):
@@ -512,14 +532,15 @@ class SageStep(_SageNative):
                       or labels.shape[1] != label_words(self.dims[-1])):
             raise TypeError("multi-label labels: an int32 CUDA matrix [N, %d] of packed words (pack_labels) expected"
                             % label_words(self.dims[-1]))
+        lossw = _loss_args(loss, self.dims[-1]) if loss is not None else ()
         # what every entry point takes, from n_layers to workspace_floats: the table's kind goes after its pointer, the
         # multi-label step takes the packed words with their row stride where the others take the labels
         kind = _table(feat)
         upto_table = (self.L, self._dims, self._sl, self._w, self._b, feat.data_ptr())
         rest = (feat.stride(0), slices[0].ptr(A.IN_NODES), slices[-1].ptr(A.OUT_NODES), labels.data_ptr(),
-                *((labels.stride(0),) if multi else ()), float(scale), self.row_pad, self.n_slabs, self.grads.data_ptr(),
+                *((labels.stride(0),) if multi else lossw), float(scale), self.row_pad, self.n_slabs, self.grads.data_ptr(),
                 loss_out.data_ptr(), self._ws.data_ptr(), self._ws.numel())
-        if not multi and drop is None:
+        if not multi and drop is None and loss is None:
             # a 16-bit table (float16 / bfloat16) goes to the step's _x16 twin: only its deepest layer's forward differs
             _table_call(self._twins, kind, upto_table, rest + (_stream(),), self._chk)
             return
@@ -527,7 +548,8 @@ class SageStep(_SageNative):
         if drop is not None:
             ids = (C.c_void_p * max(self.L - 1, 1))(*[s.ptr(A.OUT_NODES) for s in slices[:self.L - 1]])
             dropped = (ids, float(drop.p), _i64(drop.seed), _i64(drop.step))
-        fn = _lib().csl_sage_fwd_bwd_multilabel if multi else _lib().csl_sage_fwd_bwd_dropout
+        L = _lib()
+        fn = L.csl_sage_fwd_bwd_multilabel if multi else L.csl_sage_fwd_bwd_ce if loss is not None else L.csl_sage_fwd_bwd_dropout
         self._chk(fn(*upto_table, kind or 0, *rest, *dropped, _stream()), fn.__name__)
 
 
@@ -608,10 +630,14 @@ class SageRankStep(_SageNative):
             self._exc = ex
             return -1
 
-    def __call__(self, slices, feat, feat_rows, seed_ids, label_rows, labels, scale, loss_out):
+    def __call__(self, slices, feat, feat_rows, seed_ids, label_rows, labels, scale, loss_out, loss=None):
         """slices: this part's `splitgnn.Slice`s in MODEL order; feat: the rank's resident feature rows; feat_rows
-        int32 [n_in of the deepest slice]: their local rows; seed_ids int32: global ids of the owned seeds."""
+        int32 [n_in of the deepest slice]: their local rows; seed_ids int32: global ids of the owned seeds.
+        loss: a LossSpec: class weights and / or label smoothing (csl_sage_rank_fwd_bwd_ce); with 2-D (multi-label)
+        labels it is a TypeError."""
         A = _abi
+        if loss is not None and labels.dim() == 2:
+            raise TypeError("a LossSpec belongs to the single-label loss: the sigmoid-BCE loss has no weights")
         for k, s in enumerate(slices):
             c = self._sl[k]
             # the part's slice by source, where the engine emitted it (FLAG_TRANSPOSE): the backward gathers over it
@@ -621,6 +647,15 @@ class SageRankStep(_SageNative):
             c.n_owned, c.n_from, c.n_to = s.n_owned, sum(s.from_counts), sum(s.to_counts)
         self._grow(feat.device)
         self._cur, self._exc = slices, None
+        if loss is not None:
+            # (one entry point for every table type: the kind goes after the table's pointer, 0 = float32)
+            fn = _lib().csl_sage_rank_fwd_bwd_ce
+            self._chk(fn(self.L, self._dims, self._sl, self._w, self._b, feat.data_ptr(), _table(feat) or 0, feat.stride(0),
+                         _p(feat_rows), _p(seed_ids), _p(label_rows) if label_rows is not None else None, labels.data_ptr(),
+                         *_loss_args(loss, self.dims[-1]), float(scale), self.row_pad, self.n_slabs, self._cb,
+                         self._cb_wait if self.overlap else EXCHANGE_WAIT_FN(0), None, self.grads.data_ptr(),
+                         loss_out.data_ptr(), self._ws.data_ptr(), self._ws.numel(), _stream()), fn.__name__)
+            return
         # (a 16-bit table: the step's _x16 twin, the same exchanges)
         _table_call(self._twins, _table(feat), (self.L, self._dims, self._sl, self._w, self._b, feat.data_ptr()),
                     (feat.stride(0), _p(feat_rows), _p(seed_ids), _p(label_rows) if label_rows is not None else None,
@@ -637,10 +672,14 @@ class SageRankStep(_SageNative):
 
 class SoftmaxCE(torch.autograd.Function):
     """Cross-entropy summed over the rows and scaled (python/train.py:86), forward and backward in one HIP pass:
-    label of row r = labels[rowmap[ids[r]]] (rowmap None: labels[ids[r]]); returns the scalar loss."""
+    label of row r = labels[rowmap[ids[r]]] (rowmap None: labels[ids[r]]); returns the scalar loss.
+    class_weight (float32 CUDA [C]) and / or label_smoothing in [0, 1): the loss of cslicer_loss.h (csl_softmax_ce_w_f32),
+    scale * F.cross_entropy(logits, y, weight=class_weight, label_smoothing=label_smoothing, reduction="sum") -- a SUM
+    over the rows times the caller's scale, never torch's weighted mean (which divides by sum w[y]).  With both at their
+    defaults the call is csl_softmax_ce_f32's, as before."""
 
     @staticmethod
-    def forward(ctx, logits, ids, labels, scale, rowmap=None):
+    def forward(ctx, logits, ids, labels, scale, rowmap=None, class_weight=None, label_smoothing=0.0):
         logits = _f32(logits)
         n, Cn = logits.shape
         L = _lib()
@@ -648,6 +687,14 @@ class SoftmaxCE(torch.autograd.Function):
         grad = torch.empty((n, Cn), dtype=torch.float32, device=logits.device)
         if labels.dtype != torch.int64:
             raise TypeError("labels must be int64")
+        if class_weight is not None or label_smoothing != 0.0:
+            _chk(L.csl_softmax_ce_w_f32(_p(logits), logits.stride(0), n, Cn, _p(_i32(ids)),
+                                        _p(rowmap) if rowmap is not None else C.c_void_p(0), _p(labels),
+                                        *_loss_args(LossSpec(class_weight, label_smoothing), Cn), float(scale),
+                                        C.c_void_p(buf.data_ptr()), _p(grad), grad.stride(0),
+                                        C.c_void_p(buf.data_ptr() + 4), _stream()), "csl_softmax_ce_w_f32")
+            ctx.save_for_backward(grad)
+            return buf[0]
         _chk(L.csl_softmax_ce_f32(_p(logits), logits.stride(0), n, Cn, _p(_i32(ids)),
                                   _p(rowmap) if rowmap is not None else C.c_void_p(0), _p(labels), float(scale),
                                   C.c_void_p(buf.data_ptr()), _p(grad), grad.stride(0),
@@ -658,7 +705,7 @@ class SoftmaxCE(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         (grad,) = ctx.saved_tensors
-        return grad * g, None, None, None, None
+        return grad * g, None, None, None, None, None, None
 
 
 # Multi-label classification (cslicer_multilabel.h): a node's classes as packed bits, class c = bit c % 32 of word c / 32

@@ -136,7 +136,7 @@ class Trainer(object):
                  model="sage", heads=8, rank_path=None, workload=None, feat_dim=None, rng_seed=5489,
                  feature_dtype="float32", gat_input=None, replace=True, dropout=0.0, dropout_seed=None,
                  multilabel=False, weight_decay=0.0, decoupled_weight_decay=True, decay_bias=False, max_grad_norm=None,
-                 lr_schedule=None):
+                 lr_schedule=None, class_weight=None, label_smoothing=0.0):
         """Part `rank` of `world`.  Ownership = the engine's workload table (`workload` int32 [N], the METIS map of
         python/utils/sampler.py:64-134 / partition_map_opt.bin; None = v % world like pyfrontend.cpp:57): the rank
         keeps the feature and label rows of the nodes it owns, in ascending node order.
@@ -195,6 +195,18 @@ class Trainer(object):
         lr_schedule (default None: `lr` throughout): a callable steps_done -> learning rate, evaluated before every step
         and stored into `self.opt.lr` (lr_schedule() below builds warm-up + constant / cosine ones).
 
+        class_weight (default None), label_smoothing (default 0.0): the options of the single-label loss (DESIGN 4.10,
+        include/cslicer_loss.h).  class_weight: a sequence of n_classes finite numbers >= 0, at least one > 0 (0 with
+        label_smoothing == 0 masks a class: no loss, no gradient; balanced_class_weight() below builds the usual
+        n / (n_classes count_c)); label_smoothing in [0, 1).  The training loss of a minibatch is then
+        F.cross_entropy(logits, y, weight=class_weight, label_smoothing=label_smoothing, reduction="sum") / seeds: the SUM
+        over the seeds divided by their count, NOT torch's weighted "mean" (which divides by the sum of w[y]), so that the
+        loss of a minibatch split over ranks is still the sum of the ranks' shares.  Every path computes it: the native steps
+        (csl_sage_fwd_bwd_ce, csl_sage_rank_fwd_bwd_ce), aggr.SoftmaxCE on the autograd paths, torch's own loss for the
+        attention model.  The options do not choose the path (step_plan does not see them).  With both at their defaults
+        `self.loss_spec` is None and no new code runs.  evaluate()["loss"] stays the plain mean cross-entropy whatever
+        the options.  multilabel=True refuses both: the sigmoid-BCE loss has no weights yet.
+
         `self.plan` is the StepPlan of the configuration (step_plan above): which step the trainer runs, decided here
         once; `self.native` / `self.native_rank` are the native stepper of that path, None on every other path."""
         # -- 1. the arguments (before any device call: a request that cannot be served is an error, never a quiet fall-back)
@@ -230,6 +242,18 @@ class Trainer(object):
         if lr_schedule is not None and not callable(lr_schedule):
             raise ValueError("lr_schedule must be None or a callable steps_done -> lr, not %r" % (lr_schedule,))
         self.lr_schedule = lr_schedule
+        label_smoothing = float(label_smoothing)
+        if not 0.0 <= label_smoothing < 1.0:     # (a NaN compares false)
+            raise ValueError("label_smoothing must be in [0, 1), not %r" % (label_smoothing,))
+        if class_weight is not None:
+            class_weight = np.asarray(class_weight, dtype=np.float64).reshape(-1) if np.ndim(class_weight) == 1 else None
+            if class_weight is None or class_weight.shape[0] != self.n_classes:
+                raise ValueError("class_weight must be a sequence of n_classes = %d numbers" % self.n_classes)
+            if not np.isfinite(class_weight).all() or (class_weight < 0).any() or not (class_weight > 0).any():
+                raise ValueError("class_weight: finite numbers >= 0 with at least one > 0 expected")
+        if self.multilabel and (class_weight is not None or label_smoothing != 0.0):
+            raise ValueError("multilabel=True: class_weight / label_smoothing belong to the single-label loss; the "
+                             "sigmoid-BCE loss has no weights yet")
         if not replace and max(fanouts) > _abi.noreplace_max_fanout():
             raise ValueError("replace=False: fanouts %r exceed the limit of %d neighbours per row"
                              % (tuple(fanouts), _abi.noreplace_max_fanout()))
@@ -314,6 +338,11 @@ class Trainer(object):
             self.feat = f_own.to(self.dev)
         self.labels = torch.from_numpy(l_own).to(self.dev)
         del f_own, l_own
+        # the single-label loss's options (None: the plain cross-entropy, the calls as they have always been)
+        self.loss_spec = None
+        if class_weight is not None or label_smoothing != 0.0:
+            self.loss_spec = aggr.LossSpec(None if class_weight is None else
+                                           torch.from_numpy(class_weight.astype(np.float32)).to(self.dev), label_smoothing)
         # global node id -> local row of the owner (-1 elsewhere); a single part holds every node at its own id
         self.local_row = None
         if self.P > 1:
@@ -393,6 +422,15 @@ class Trainer(object):
         mean over elements"""
         return 1.0 / (den * self.n_classes) if self.multilabel else 1.0 / den
 
+    def _loss_kw(self):
+        """the native steppers' `loss` keyword: absent without loss options, so that their call is the one it has been"""
+        return {} if self.loss_spec is None else {"loss": self.loss_spec}
+
+    def _loss_tail(self):
+        """what follows `scale` in aggr.SoftmaxCE.apply with loss options (rowmap, class_weight, label_smoothing): nothing
+        without them"""
+        return () if self.loss_spec is None else (None, self.loss_spec.class_weight, self.loss_spec.label_smoothing)
+
     def _next_loss(self):
         """the loss ring's next element (run() sized the ring for its steps)"""
         loss = self._loss_ring[self._ring_at:self._ring_at + 1]
@@ -407,7 +445,8 @@ class Trainer(object):
         # forward, loss, backward: one native call; the optimizer: a second one on the flat gradient buffer
         _roctx.push("step_native")
         loss = self._next_loss()
-        self.native(layers, self.feat, self.labels, self._scale(self._loss_den(stream, slot, n_seeds)), loss, self._drop())
+        self.native(layers, self.feat, self.labels, self._scale(self._loss_den(stream, slot, n_seeds)), loss, self._drop(),
+                    **self._loss_kw())
         if self.grad_sync is not None:
             self.grad_sync(self.native.grads)             # (data-parallel: sum over the ranks' shares of the minibatch)
         self.opt.step(flat_grads=self.native.grads)
@@ -420,7 +459,7 @@ class Trainer(object):
         top = layers[-1]
         seeds = top.out_nodes[top.owned_out_nodes.long()]              # the seeds this rank owns, frontier order
         self.native_rank(layers, self.feat, self._input_rows(layers[0]), seeds, self.local_row, self.labels,
-                         1.0 / max(n_seeds, 1), loss)
+                         1.0 / max(n_seeds, 1), loss, **self._loss_kw())
         self.dist.all_reduce(self.native_rank.grads)                   # replicated weights: sum of the ranks' shares
         self.opt.step(flat_grads=self.native_rank.grads)
         _roctx.pop()
@@ -433,7 +472,7 @@ class Trainer(object):
         _roctx.push("forward")
         logits = self.model.forward_local(slices, self.feat, drop=self._drop())
         loss_fn = aggr.SigmoidBCE if self.multilabel else aggr.SoftmaxCE
-        loss = loss_fn.apply(logits, layers[-1].out_nodes, self.labels, self._scale(max(n_seeds, 1)))
+        loss = loss_fn.apply(logits, layers[-1].out_nodes, self.labels, self._scale(max(n_seeds, 1)), *self._loss_tail())
         _roctx.pop()
         self.t_forward += time.perf_counter() - t1
         return self._backward_and_update(loss)
@@ -467,12 +506,15 @@ class Trainer(object):
             den = max(n_seeds, 1) if self.rank_path else self._loss_den(stream, slot, n_seeds)   # (data-parallel: global)
             loss = aggr.SigmoidBCE.apply(logits, seeds, self.labels, self._scale(den), self.local_row)
         elif self.kind == "sage" and logits.shape[0] > 0:
-            loss = aggr.SoftmaxCE.apply(logits, seeds, self.labels, 1.0 / max(n_seeds, 1), self.local_row)
+            loss = aggr.SoftmaxCE.apply(logits, seeds, self.labels, 1.0 / max(n_seeds, 1), self.local_row,
+                                        *self._loss_tail()[1:])
         else:
             seeds = seeds.long()
             y = self.labels[seeds if self.P == 1 else self.local_row[seeds].long()]
             den = max(n_seeds, 1) if self.rank_path else self._loss_den(stream, slot, n_seeds)   # (data-parallel: global)
-            loss = torch.nn.functional.cross_entropy(logits, y, reduction="sum") / den
+            kw = {} if self.loss_spec is None else {"weight": self.loss_spec.class_weight,
+                                                    "label_smoothing": self.loss_spec.label_smoothing}
+            loss = torch.nn.functional.cross_entropy(logits, y, reduction="sum", **kw) / den
         _roctx.pop()
         self.t_forward += time.perf_counter() - t1
         return self._backward_and_update(loss)
@@ -652,7 +694,8 @@ class Trainer(object):
 
     def evaluate(self, nodes, chunk_rows=None):
         """{"accuracy", "loss", "n"} of the current weights on `nodes` (argmax accuracy, mean cross-entropy against the
-        trainer's labels) by full-neighbour inference; see predict().  Rank path: collective, the same dict on every
+        trainer's labels -- the PLAIN one: class_weight / label_smoothing shape the training loss only) by full-neighbour
+        inference; see predict().  Rank path: collective, the same dict on every
         rank (cslicer.infer.evaluate_parts).  A multi-label trainer: {"micro_f1", "loss", "n", "tp", "fp", "fn"}
         (micro-F1 of logits > 0, mean binary cross-entropy per element)."""
         from . import infer
@@ -710,6 +753,18 @@ class DataParallelTrainer(Trainer):
 
     def _loss_den(self, stream, slot, n_seeds):
         return self._den[(stream, slot)]
+
+
+def balanced_class_weight(labels, n_classes):
+    """float32 [n_classes]: n / (n_classes * count_c), the "balanced" class weights (sklearn's compute_class_weight) of the
+    int labels given, computed in float64; a class no node carries gets 0.  For Trainer(class_weight=...)."""
+    labels = np.asarray(labels).reshape(-1)
+    if labels.size and (labels.min() < 0 or labels.max() >= n_classes):
+        raise ValueError("labels must be in [0, n_classes = %d)" % n_classes)
+    count = np.bincount(labels.astype(np.int64), minlength=n_classes).astype(np.float64)
+    w = np.zeros(n_classes, dtype=np.float64)
+    w[count > 0] = labels.size / (n_classes * count[count > 0])
+    return w.astype(np.float32)
 
 
 def lr_schedule(kind, base_lr, warmup=0, total=0, min_lr=0.0):
@@ -847,6 +902,12 @@ def _parser():
                     help="(extra) after the warm-up: --lr throughout, or half a cosine down to --lr-min at the last step "
                          "of the last epoch (`train.lr_schedule`)")
     ap.add_argument("--lr-min", type=float, default=None, help="(extra) where the cosine schedule ends (default 0)")
+    ap.add_argument("--label-smoothing", type=float, default=None, metavar="EPS",
+                    help="(extra) label smoothing of the softmax cross-entropy, in [0, 1) (`Trainer(label_smoothing=EPS)`)")
+    ap.add_argument("--class-weight", type=str, default=None, metavar="balanced|FILE",
+                    help="(extra) per-class weights of the softmax cross-entropy (`Trainer(class_weight=...)`): `balanced` = "
+                         "n / (n_classes * count_c) over the training nodes' labels, or a text file of n_classes numbers, "
+                         "one per line")
     return ap
 
 
@@ -864,6 +925,21 @@ def _optimizer_kw(a, steps_per_epoch):
     if a.lr_warmup is not None or a.lr_schedule is not None or a.lr_min is not None:
         kw["lr_schedule"] = lr_schedule(a.lr_schedule or "constant", a.lr, warmup=a.lr_warmup or 0,
                                         total=a.num_epochs * steps_per_epoch, min_lr=a.lr_min or 0.0)
+    return kw
+
+
+def _loss_kw(a, labels, train_nodes, n, n_classes):
+    """the Trainer keywords of --label-smoothing / --class-weight, each only where its option was given.  `balanced`
+    counts the labels of the training nodes of the WHOLE job (labels(ids) serves any id on any rank): every rank gets the
+    same vector."""
+    kw = {}
+    if a.label_smoothing is not None:
+        kw["label_smoothing"] = a.label_smoothing
+    if a.class_weight == "balanced":
+        ids = np.arange(n, dtype=np.int64) if train_nodes is None else np.asarray(train_nodes, dtype=np.int64)
+        kw["class_weight"] = balanced_class_weight(labels(ids), n_classes)
+    elif a.class_weight is not None:
+        kw["class_weight"] = np.loadtxt(a.class_weight, dtype=np.float64, ndmin=1)
     return kw
 
 
@@ -921,13 +997,22 @@ def main(argv=None):
     cross-entropy with logits and rank 0 prints `Eval F1` (micro-F1) where it prints `Eval Acc`.  `synthetic` and the
     presets train on synthetic_multilabels; an L0 directory must hold packed multi-label words (multilabel=1 in its
     meta.txt, cslicer.l0.write_l0 with a 2-D `labels`).
+    --label-smoothing EPS (extra): `Trainer(label_smoothing=EPS)`, EPS in [0, 1).
+    --class-weight balanced|FILE (extra): `Trainer(class_weight=...)`: `balanced` = n / (n_classes * count_c) over the labels
+    of the training nodes (train.balanced_class_weight; a class without a node gets 0), FILE = n_classes numbers, one per
+    line.  The training loss is the weighted, smoothed sum over a minibatch's seeds divided by their count; `Eval Acc`'s
+    loss stays the plain mean cross-entropy.  Neither combines with --multilabel (the sigmoid-BCE loss has no weights yet).
 
+        python -m cslicer.train --graph products-like --class-weight balanced --label-smoothing 0.1 --eval-split holdout --max-steps 50
         python -m cslicer.train --graph products-like --multilabel --eval-split holdout --max-steps 50
         python -m cslicer.train --graph products-like --dropout 0.5 --weight-decay 5e-4 --clip-grad-norm 1 --lr-warmup 100 --lr-schedule cosine
         python -m cslicer.train --graph <L0 dir> --feature-dtype bfloat16 --eval-split holdout
         python -m cslicer.train --graph products-like --model-name gat --feature-dtype bfloat16 --gat-input on"""
     a = _parser().parse_args(argv)
     from . import l0
+    if a.multilabel and (a.label_smoothing is not None or a.class_weight is not None):
+        raise SystemExit("--multilabel: --label-smoothing and --class-weight belong to the single-label loss (the sigmoid-BCE "
+                         "loss has no weights yet)")
     if a.no_replace:     # (before the graph is loaded)
         lim = _abi.noreplace_max_fanout()
         if any(int(x) > lim for x in a.fan_out.split(",")):
@@ -989,7 +1074,8 @@ def main(argv=None):
                  streams=8, hidden=max(4, hidden // 4 * 4), lr=a.lr, device=local, dist=dist, model=kind, heads=a.num_heads,
                  workload=workload, feat_dim=fdim, feature_dtype=fdtype,
                  gat_input={"auto": None, "on": True, "off": False}[a.gat_input], replace=not a.no_replace,
-                 dropout=a.dropout, **({"multilabel": True} if a.multilabel else {}), **_optimizer_kw(a, per_epoch))
+                 dropout=a.dropout, **({"multilabel": True} if a.multilabel else {}), **_optimizer_kw(a, per_epoch),
+                 **_loss_kw(a, labels, train_nodes, indptr.shape[0] - 1, n_classes))
     if rank == 0 and fdtype != "float32":
         print("feature table: %s, %d bytes on this rank" % (fdtype, tr.feat.numel() * tr.feat.element_size()))
     n = indptr.shape[0] - 1

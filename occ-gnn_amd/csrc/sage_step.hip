@@ -1,7 +1,8 @@
 // sage_step.hip -- forward, loss and backward of the GraphSAGE model for one minibatch as ONE call behind the C ABI: the
 // sequence of this library's fused kernels and plain GEMMs that python/train.py:56-88 + python/layers/dist_sageconv.py:42-84
-// amount to, on ONE part that holds every node (cslicer_aggr.h: csl_sage_fwd_bwd_f32, its _x16, _dropout and _multilabel
-// forms) and on one RANK of the split-parallel job (csl_sage_rank_fwd_bwd_f32 / _x16).  No kernels here, only sequencing.
+// amount to, on ONE part that holds every node (cslicer_aggr.h: csl_sage_fwd_bwd_f32, its _x16, _dropout, _multilabel and
+// _ce forms) and on one RANK of the split-parallel job (csl_sage_rank_fwd_bwd_f32 / _x16 / _ce).  No kernels here, only
+// sequencing.
 //
 // Why a native sequencer: the step is ~25 kernel launches and 8 GEMMs of 5-90 us each.  Issued from Python (one ctypes
 // call or torch op each, an autograd graph around them) they cost 0.55-0.75 ms of host time per step, more than the
@@ -9,13 +10,14 @@
 // from here a step is ~0.15 ms of host time and the GPU sets the pace (a rank: the 2 L callbacks plus ~0.25 ms instead of
 // ~1.2 ms of interpreter + autograd work, which is what bounds a rank once the GPU work is split N ways).
 //
-// ONE layout (Layout, lay_out) and ONE body (sage_step) serve both; the six entry points check their own arguments and call
-// it.  Per model layer k (deepest hop first; slice k = the engine's layer n_layers-1-k, graph mode):
+// ONE layout (Layout, lay_out) and ONE body (sage_step) serve both; the eight entry points check their own arguments and
+// call it.  Per model layer k (deepest hop first; slice k = the engine's layer n_layers-1-k, graph mode):
 //   forward   cat_k = [x[self] | mean_{CSR row} x[src]]       csl_sage_cat_f32 (k = 0 reads the resident feature table
 //             y_k   = cat_k W_k^T + b_k (ReLU for k < L-1)     through the slice's in_nodes)      + csl_gemm_f32
 //             (k = 0, widths allowing: both as csl_sage_fwd_mfma_f32); dropout on y_k in place (k < L-1)
-//   loss      csl_softmax_ce_partial_f32 / csl_sigmoid_bce_partial_f32 on y_{L-1} (forward, gradient = the top layer's
-//             padded gy, bias column sums)
+//   loss      csl_softmax_ce_partial_f32 / csl_sigmoid_bce_partial_f32 / csl_softmax_ce_w_partial_f32 (class weights,
+//             label smoothing: the _ce entry points) on y_{L-1} (forward, gradient = the top layer's padded gy, bias
+//             column sums)
 //   backward  gW_k  = gy_k^T cat_k (row slabs)                 csl_gemm_f32 (batched)
 //             gcat  = gy_k W_k                                 csl_gemm_f32
 //             gy_{k-1}, gb_{k-1} = gather of gcat over the slice by source, ReLU mask of y_{k-1}, row padding and
@@ -48,6 +50,7 @@
 #include "cslicer_dropout.h"
 #include "cslicer_feat16.h"
 #include "cslicer_hip.h"
+#include "cslicer_loss.h"
 #include "cslicer_multilabel.h"
 #include "dev_common.h"
 #include "feat_elem.h"
@@ -297,6 +300,12 @@ struct MultiArgs {
   int64_t ldw;
 };
 
+// the options of the single-label loss (csl_sage_fwd_bwd_ce / csl_sage_rank_fwd_bwd_ce, cslicer_loss.h)
+struct LossArgs {
+  const float* class_weight;
+  float label_smoothing;
+};
+
 // a rank's boundary exchange: the caller's callbacks.  `wait` given: `exchange` only STARTS the exchange (on a stream of
 // the caller's) and `wait` makes `stream` wait for it -- called right before the received rows are first used, so the rows
 // that never leave the GPU are aggregated while the boundary rows travel (dist_sageconv.py:57-64 on a side stream)
@@ -348,14 +357,15 @@ int gather_by_source(const Layer& s, bool hub, const int32_t* indptr, const floa
                                 bpart, in, stream);
 }
 
-// The step behind all six entry points.  lv: the slices (lv.rank: of a rank, with `xc` its exchange and `label_rows`);
+// The step behind all eight entry points.  lv: the slices (lv.rank: of a rank, with `xc` its exchange and `label_rows`);
 // kind: the feature table's element kind (0: float32).  Single GPU only: `drop` (csl_sage_fwd_bwd_dropout) and `multi`
-// (sigmoid-BCE on packed labels in place of the softmax cross-entropy: csl_sage_fwd_bwd_multilabel).
+// (sigmoid-BCE on packed labels in place of the softmax cross-entropy: csl_sage_fwd_bwd_multilabel).  Both: `lossw` (the
+// cross-entropy with class weights and label smoothing: the _ce entry points).
 int sage_step(int32_t n_layers, const int32_t* dims, const Layers& lv, const float* const* weights, const float* const* biases,
               const void* feat, int32_t kind, int64_t ldf, const int32_t* feat_rows, const int32_t* seed_ids,
               const int32_t* label_rows, const int64_t* labels, float scale, int64_t row_pad, int32_t n_slabs,
               const Exchange* xc, float* grads, float* loss, float* workspace, int64_t workspace_floats, void* stream,
-              const DropArgs* drop, const MultiArgs* multi) {
+              const DropArgs* drop, const MultiArgs* multi, const LossArgs* lossw = nullptr) {
   s_err[0] = 0;
   Layout o;
   if (!weights || !biases || !grads || !loss || (lv.rank && !xc->exchange) || !lay_out(n_layers, dims, lv, row_pad, n_slabs, o)) {
@@ -433,6 +443,9 @@ int sage_step(int32_t n_layers, const int32_t* dims, const Layers& lv, const flo
     if (multi)
       STEP(t_other, k, csl_sigmoid_bce_partial_f32(ws + o.y[k], C, m, rows, C, seed_ids, label_rows, multi->words, multi->ldw, scale,
                                                    ws + o.g, C, ws + o.lpart, cols, stream));
+    else if (lossw)
+      STEP(t_other, k, csl_softmax_ce_w_partial_f32(ws + o.y[k], C, m, rows, C, seed_ids, label_rows, labels, lossw->class_weight,
+                                                    lossw->label_smoothing, scale, ws + o.g, C, ws + o.lpart, cols, stream));
     else
       STEP(t_other, k, csl_softmax_ce_partial_f32(ws + o.y[k], C, m, rows, C, seed_ids, label_rows, labels, scale, ws + o.g, C,
                                                   ws + o.lpart, cols, stream));
@@ -632,6 +645,61 @@ int csl_sage_rank_fwd_bwd_x16(int32_t n_layers, const int32_t* dims, const csl_s
   const Exchange xc = {exchange, wait, user, stream};
   return sage_step(n_layers, dims, Layers(n_layers, sl), weights, biases, feat, kind, ldf, feat_rows, seed_ids, label_rows, labels,
                    scale, row_pad, n_slabs, &xc, grads, loss, workspace, workspace_floats, stream, nullptr, nullptr);
+}
+
+// what both _ce entry points refuse about the loss options (the other arguments: sage_step's own checks)
+static bool loss_refused(int32_t n_layers, const int32_t* dims, const int64_t* labels, float label_smoothing) {
+  if (!(label_smoothing >= 0.f && label_smoothing < 1.f)) {   // (a NaN compares false)
+    snprintf(s_err, sizeof(s_err), "label_smoothing must be in [0, 1), not %g", (double)label_smoothing);
+    return true;
+  }
+  if (!labels) {
+    snprintf(s_err, sizeof(s_err), "labels: the int64 labels of the nodes expected, not NULL");
+    return true;
+  }
+  if (dims && n_layers >= 1 && n_layers <= CSL_MAX_LAYERS && (dims[n_layers] < 1 || dims[n_layers] > 4096)) {
+    snprintf(s_err, sizeof(s_err), "dims: 1 <= classes <= 4096 expected for the weighted loss, not %d", (int)dims[n_layers]);
+    return true;
+  }
+  return false;
+}
+
+int csl_sage_fwd_bwd_ce(int32_t n_layers, const int32_t* dims, const csl_sage_slice* sl, const float* const* weights,
+                        const float* const* biases, const void* feat, int32_t kind, int64_t ldf, const int32_t* feat_rows,
+                        const int32_t* seed_ids, const int64_t* labels, const float* class_weight, float label_smoothing,
+                        float scale, int64_t row_pad, int32_t n_slabs, float* grads, float* loss, float* workspace,
+                        int64_t workspace_floats, const int32_t* const* out_ids, float p, int64_t seed, int64_t step,
+                        void* stream) {
+  if (kind != 0 && table16_refused(feat, kind, ldf)) return CSL_E_INVALID;
+  if (loss_refused(n_layers, dims, labels, label_smoothing)) return CSL_E_INVALID;
+  const bool plain = p == 0.f && !out_ids;
+  bool ok = n_layers >= 1 && n_layers <= CSL_MAX_LAYERS && sl && (plain || (p > 0.f && p < 1.f && (n_layers == 1 || out_ids)));
+  for (int k = 0; ok && !plain && k + 1 < n_layers; k++) ok = sl[k].n_out <= 0 || out_ids[k];
+  if (!ok) {
+    snprintf(s_err, sizeof(s_err), "dropout (p, out_ids): either p == 0 without out-node ids or 0 < p < 1 with those of every "
+             "layer but the last expected (p = %g)", (double)p);
+    return CSL_E_INVALID;
+  }
+  const DropArgs drop = {out_ids, p, seed, step};
+  const LossArgs lossw = {class_weight, label_smoothing};
+  return sage_step(n_layers, dims, Layers(n_layers, sl), weights, biases, feat, kind, ldf, feat_rows, seed_ids, nullptr, labels,
+                   scale, row_pad, n_slabs, nullptr, grads, loss, workspace, workspace_floats, stream, plain ? nullptr : &drop,
+                   nullptr, &lossw);
+}
+
+int csl_sage_rank_fwd_bwd_ce(int32_t n_layers, const int32_t* dims, const csl_sage_rank_slice* sl,
+                             const float* const* weights, const float* const* biases, const void* feat, int32_t kind,
+                             int64_t ldf, const int32_t* feat_rows, const int32_t* seed_ids, const int32_t* label_rows,
+                             const int64_t* labels, const float* class_weight, float label_smoothing, float scale,
+                             int64_t row_pad, int32_t n_slabs, csl_exchange_fn exchange, csl_exchange_wait_fn wait,
+                             void* user, float* grads, float* loss, float* workspace, int64_t workspace_floats,
+                             void* stream) {
+  if (kind != 0 && table16_refused(feat, kind, ldf)) return CSL_E_INVALID;
+  if (loss_refused(n_layers, dims, labels, label_smoothing)) return CSL_E_INVALID;
+  const Exchange xc = {exchange, wait, user, stream};
+  const LossArgs lossw = {class_weight, label_smoothing};
+  return sage_step(n_layers, dims, Layers(n_layers, sl), weights, biases, feat, kind, ldf, feat_rows, seed_ids, label_rows, labels,
+                   scale, row_pad, n_slabs, &xc, grads, loss, workspace, workspace_floats, stream, nullptr, nullptr, &lossw);
 }
 
 }  // extern "C"
