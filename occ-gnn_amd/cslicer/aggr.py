@@ -21,6 +21,7 @@ GAT_IN16_SYMBOLS = _abi.BOUND["cslicer_gat_in16.h"]   # the attention input laye
 DROPOUT_SYMBOLS = _abi.BOUND["cslicer_dropout.h"]     # dropout between the GraphSAGE layers: the kernel and the native step with it
 MULTILABEL_SYMBOLS = _abi.BOUND["cslicer_multilabel.h"]   # the sigmoid-BCE loss, the micro-F1 head, the native step with that loss
 OPTIM_SYMBOLS = _abi.BOUND["cslicer_optim.h"]             # the optimizer step with weight decay, clipping and the non-finite guard
+GAT_DROPOUT_SYMBOLS = _abi.BOUND["cslicer_gat_dropout.h"]   # attention dropout: the dropped twins of the four aggregation calls
 LOSS_SYMBOLS = _abi.BOUND["cslicer_loss.h"]               # class weights and label smoothing: the loss pass and the native steps with it
 EXCHANGE_FN, EXCHANGE_WAIT_FN = _abi.EXCHANGE_FN, _abi.EXCHANGE_WAIT_FN
 # element kinds of a 16-bit feature table (CSL_FEAT_F16 / CSL_FEAT_BF16); a float32 table has the fp32 entry points
@@ -429,6 +430,65 @@ class Dropout(torch.autograd.Function):
         return dropout(g if g.stride(-1) == 1 else g.contiguous(), ids, *ctx.cfg), None, None, None, None, None
 
 
+# Dropout for the attention model (cslicer_gat_dropout.h): p_f on every hidden layer's output (cslicer_dropout.h's
+# mask), p_a on the normalised attention coefficients (inside the aggregation kernels), the run's seed, the step's counter.
+GatDropSpec = collections.namedtuple("GatDropSpec", "p_f p_a seed step")
+
+
+def gat_drop(drop):
+    """the GatDropSpec if it drops anything, else None (None and both probabilities 0 are the same request: no dropout
+    code at all)"""
+    return drop if drop is not None and (drop.p_f > 0 or drop.p_a > 0) else None
+
+
+def attn_drop(drop, sl, layer):
+    """what a node takes for attention dropout on slice `sl` as model layer `layer`: (source node ids, destination node
+    ids, p_a, seed, layer, step), or None where the spec has none"""
+    if drop is None or not drop.p_a > 0:
+        return None
+    return (_i32(sl.in_nodes), _i32(sl.out_nodes), float(drop.p_a), drop.seed, int(layer), drop.step)
+
+
+def feat_drop(drop, sl, layer):
+    """what the fused single-part layer takes for feature dropout in its epilogue on slice `sl` as model layer `layer`:
+    (out node ids, p_f, seed, layer, step), or None where the spec has none"""
+    if drop is None or not drop.p_f > 0:
+        return None
+    return (_i32(sl.out_nodes), float(drop.p_f), drop.seed, int(layer), drop.step)
+
+
+def _gat_call(stem, attn, *args):
+    """csl_gat_<stem>_f32(*args, stream), or with attention dropout (`attn`: attn_drop's tuple) its dropped twin
+    csl_gat_drop_<stem>_f32, which takes the ids and the counter behind the parent's arguments"""
+    if attn is None:
+        fn = getattr(_lib(), "csl_gat_%s_f32" % stem)
+        return _chk(fn(*args, _stream()), fn.__name__)
+    src_ids, dst_ids, p_a, seed, layer, step = attn
+    fn = getattr(_lib(), "csl_gat_drop_%s_f32" % stem)
+    _chk(fn(*args, _p(src_ids), _p(dst_ids), p_a, _i64(seed), layer, _i64(step), _stream()), fn.__name__)
+
+
+class DropoutRows(torch.autograd.Function):
+    """Dropout of x [n, H] (one node id per row) into a FRESH row-padded buffer (padded_rows: the next fused attention
+    layer's operand, padding rows zero): returns the buffer [pad(n), H].  Backward: the same map on the gradient's first n
+    rows."""
+
+    @staticmethod
+    def forward(ctx, x, ids, p, seed, layer, step, row_pad):
+        n = x.shape[0]
+        ctx.save_for_backward(ids)
+        ctx.cfg = (p, seed, layer, step)
+        y = padded_rows(n, x.shape[1], row_pad, x.device).t
+        dropout(x, ids, p, seed, layer, step, out=y[:n])
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        ids, = ctx.saved_tensors
+        g = g if g.stride(-1) == 1 and g.stride(0) % 4 == 0 else g.contiguous()
+        return dropout(g[:ids.numel()], ids, *ctx.cfg), None, None, None, None, None, None
+
+
 class SageSlice(C.Structure):
     """csl_sage_slice (cslicer_aggr.h)"""
     _fields_ = [("indptr", C.c_void_p), ("indices", C.c_void_p), ("self_ids_in", C.c_void_p),
@@ -821,7 +881,8 @@ class GatAggregate(torch.autograd.Function):
     result n/s does not depend on it)."""
 
     @staticmethod
-    def forward(ctx, el, er, z, indptr, indices, n_rows, H, D, slope):
+    def forward(ctx, el, er, z, indptr, indices, n_rows, H, D, slope, attn=None):
+        """attn: attn_drop()'s tuple: attention dropout (csl_gat_drop_fwd_f32 / csl_gat_drop_bwd_f32); None: none"""
         el, er, z = _f32(el).contiguous(), _f32(er).contiguous(), _f32(z).contiguous()
         indptr, indices = _i32(indptr), _i32(indices)
         if el.shape != (z.shape[0], H) or er.shape != (n_rows, H) or z.shape[1] != H * D:
@@ -830,10 +891,10 @@ class GatAggregate(torch.autograd.Function):
         m = torch.empty((n_rows, H), dtype=torch.float32, device=dev)
         s = torch.empty((n_rows, H), dtype=torch.float32, device=dev)
         n = torch.empty((n_rows, H * D), dtype=torch.float32, device=dev)
-        _chk(_lib().csl_gat_fwd_f32(_p(indptr), _p(indices), n_rows, _p(el), _p(er), _p(z), H, D, slope,
-                                    _p(m), _p(s), _p(n), _stream()), "csl_gat_fwd_f32")
+        _gat_call("fwd", attn, _p(indptr), _p(indices), n_rows, _p(el), _p(er), _p(z), H, D, slope, _p(m), _p(s), _p(n))
         ctx.save_for_backward(el, er, z, indptr, indices, m)
         ctx.cfg = (n_rows, H, D, slope)
+        ctx.attn = attn
         ctx.mark_non_differentiable(m)
         return m, s, n
 
@@ -845,9 +906,9 @@ class GatAggregate(torch.autograd.Function):
         g_el = torch.zeros_like(el)
         g_er = torch.empty_like(er)
         g_z = torch.zeros_like(z)
-        _chk(_lib().csl_gat_bwd_f32(_p(indptr), _p(indices), n_rows, _p(el), _p(er), _p(z), H, D, slope, _p(m),
-                                    _p(gs), _p(gn), _p(g_el), _p(g_er), _p(g_z), _stream()), "csl_gat_bwd_f32")
-        return g_el, g_er, g_z, None, None, None, None, None, None
+        _gat_call("bwd", ctx.attn, _p(indptr), _p(indices), n_rows, _p(el), _p(er), _p(z), H, D, slope, _p(m), _p(gs), _p(gn),
+                  _p(g_el), _p(g_er), _p(g_z))
+        return g_el, g_er, g_z, None, None, None, None, None, None, None
 
 
 class GatLogits(torch.autograd.Function):
@@ -913,9 +974,12 @@ class GatLayerLocal(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, attn_l, attn_r, bias, indptr, indices, self_ids_in, n_out, slope, elu, row_pad,
-                weight_grad, t_indptr=None, t_indices=None, t_max_len=0, n_rows=None, pad_out=False):
+                weight_grad, t_indptr=None, t_indices=None, t_max_len=0, n_rows=None, pad_out=False, attn=None, feat=None):
         """n_rows: x is ALREADY the row-padded buffer of a PaddedRows (its first n_rows rows are the input); pad_out:
-        return the output as the padded buffer [pad(n_out), H*D] (zero rows behind n_out) for the next layer."""
+        return the output as the padded buffer [pad(n_out), H*D] (zero rows behind n_out) for the next layer; attn:
+        attn_drop()'s tuple: attention dropout, the aggregation and its backward are the dropped twins; feat: feat_drop()'s
+        tuple: feature dropout in the epilogue (csl_gat_finish_drop_fwd_f32 writes the undropped output, kept for ELU',
+        and the dropped one, which is returned; csl_gat_finish_drop_bwd_f32 masks the gradient as it loads it)."""
         H, D = attn_l.shape
         Cw = H * D
         n_in, mp = x.shape[0], x.shape[0]
@@ -949,20 +1013,28 @@ class GatLayerLocal(torch.autograd.Function):
         m = torch.empty((n_out, H), dtype=torch.float32, device=dev)
         s = torch.empty((n_out, H), dtype=torch.float32, device=dev)
         n = torch.empty((n_out, Cw), dtype=torch.float32, device=dev)
-        _chk(L.csl_gat_fwd_f32(_p(indptr), _p(indices), n_out, _p(el), _p(er_out), _p(z), H, D, slope, _p(m), _p(s), _p(n),
-                               _stream()), "csl_gat_fwd_f32")
+        _gat_call("fwd", attn, _p(indptr), _p(indices), n_out, _p(el), _p(er_out), _p(z), H, D, slope, _p(m), _p(s), _p(n))
         out = padded_rows(n_out, Cw, row_pad, dev).t if pad_out else torch.empty((n_out, Cw), dtype=torch.float32,
                                                                                   device=dev)
-        _chk(L.csl_gat_finish_fwd_f32(_p(n), _p(s), _p(b), n_out, H, D, 1 if elu else 0, _p(out), _stream()),
-             "csl_gat_finish_fwd_f32")
+        if feat is None:
+            _chk(L.csl_gat_finish_fwd_f32(_p(n), _p(s), _p(b), n_out, H, D, 1 if elu else 0, _p(out), _stream()),
+                 "csl_gat_finish_fwd_f32")
+            ret = out
+        else:
+            ret, out = out, torch.empty((n_out, Cw), dtype=torch.float32, device=dev)
+            ids, p_f, seed, layer, step = feat
+            _chk(L.csl_gat_finish_drop_fwd_f32(_p(n), _p(s), _p(b), n_out, H, D, 1 if elu else 0, _p(out), _p(ret), _p(ids),
+                                               p_f, _i64(seed), layer, _i64(step), _stream()), "csl_gat_finish_drop_fwd_f32")
+        ctx.feat = feat
         ctx.save_for_backward(xp, weight, al, ar, z, el, er_out, m, s, n, out, indptr, indices, self_ids_in)
         ctx.cfg = (n_in, n_out, H, D, slope, bool(elu), weight_grad)
         ctx.x_rows = x.shape[0]
+        ctx.attn = attn
         # the slice by source (engine flags FLAG_TRANSPOSE | FLAG_TRANSPOSE_ALL): the backward then writes the gradient
         # of z row by row instead of scattering it with atomics into a zeroed buffer
         ctx.by_source = ((_i32(t_indptr), _i32(t_indices)) if t_indptr is not None and t_indptr.numel() == n_in + 1
                          and t_max_len <= _abi.T_SORTED_MAX else None)     # (a hub's list: the atomic form)
-        return out
+        return ret
 
     @staticmethod
     def backward(ctx, g):
@@ -980,8 +1052,14 @@ class GatLayerLocal(torch.autograd.Function):
                           device=dev)
         g_bias, g_al, g_ar = buf[:Cw], buf[Cw:2 * Cw].view(H, D), buf[2 * Cw:3 * Cw].view(H, D)
         scratch = C.c_void_p(buf.data_ptr() + 12 * Cw)
-        _chk(L.csl_gat_finish_bwd_f32(_p(g), g.stride(0), _p(out), _p(n), _p(s), n_out, H, D, 1 if elu else 0, _p(g_n),
-                                      _p(g_s), _p(g_bias), scratch, _stream()), "csl_gat_finish_bwd_f32")
+        if ctx.feat is None:
+            _chk(L.csl_gat_finish_bwd_f32(_p(g), g.stride(0), _p(out), _p(n), _p(s), n_out, H, D, 1 if elu else 0, _p(g_n),
+                                          _p(g_s), _p(g_bias), scratch, _stream()), "csl_gat_finish_bwd_f32")
+        else:
+            ids, p_f, seed, layer, step = ctx.feat
+            _chk(L.csl_gat_finish_drop_bwd_f32(_p(g), g.stride(0), _p(out), _p(n), _p(s), n_out, H, D, 1 if elu else 0,
+                                               _p(g_n), _p(g_s), _p(g_bias), scratch, _p(ids), p_f, _i64(seed), layer,
+                                               _i64(step), _stream()), "csl_gat_finish_drop_bwd_f32")
         # ONE gradient buffer for z (padded like the GEMM operand): the aggregation's share, then the logits' share
         if ctx.by_source is not None and not os.environ.get("CSLICER_GAT_NO_FOLD"):
             # by source, with the logits' backward folded in: g_z is written complete in one pass over the source rows
@@ -991,24 +1069,23 @@ class GatLayerLocal(torch.autograd.Function):
             g_er_out = torch.empty((n_out, H), dtype=torch.float32, device=dev)
             fs = torch.empty((max(int(L.csl_gat_bwd_t_fused_scratch(z.shape[0], n_out, H, D)), 4),), dtype=torch.float32,
                              device=dev)
-            _chk(L.csl_gat_bwd_t_fused_f32(_p(tptr), _p(trow), n_in, z.shape[0], _p(el), _p(er_out), _p(z), H, D, slope, _p(m),
-                                           _p(g_s), _p(g_n), _p(al), _p(ar), _p(self_ids_in), n_out, _p(g_er_out), _p(g_z),
-                                           C.c_void_p(g_al.data_ptr()), C.c_void_p(g_ar.data_ptr()), _p(fs), _stream()),
-                 "csl_gat_bwd_t_fused_f32")
+            _gat_call("bwd_t_fused", ctx.attn, _p(tptr), _p(trow), n_in, z.shape[0], _p(el), _p(er_out), _p(z), H, D, slope,
+                      _p(m), _p(g_s), _p(g_n), _p(al), _p(ar), _p(self_ids_in), n_out, _p(g_er_out), _p(g_z),
+                      C.c_void_p(g_al.data_ptr()), C.c_void_p(g_ar.data_ptr()), _p(fs))
         else:
             if ctx.by_source is not None:
                 tptr, trow = ctx.by_source
                 g_z = torch.empty((z.shape[0], Cw), dtype=torch.float32, device=dev)     # every row is written
                 g_el = torch.empty((n_in, H), dtype=torch.float32, device=dev)
                 g_er_out = torch.zeros((n_out, H), dtype=torch.float32, device=dev)
-                _chk(L.csl_gat_bwd_t_f32(_p(tptr), _p(trow), n_in, z.shape[0], _p(el), _p(er_out), _p(z), H, D, slope, _p(m),
-                                         _p(g_s), _p(g_n), _p(g_el), _p(g_er_out), _p(g_z), _stream()), "csl_gat_bwd_t_f32")
+                _gat_call("bwd_t", ctx.attn, _p(tptr), _p(trow), n_in, z.shape[0], _p(el), _p(er_out), _p(z), H, D, slope, _p(m),
+                          _p(g_s), _p(g_n), _p(g_el), _p(g_er_out), _p(g_z))
             else:
                 g_z = torch.zeros((z.shape[0], Cw), dtype=torch.float32, device=dev)
                 g_el = torch.zeros((n_in, H), dtype=torch.float32, device=dev)
                 g_er_out = torch.empty((n_out, H), dtype=torch.float32, device=dev)
-                _chk(L.csl_gat_bwd_f32(_p(indptr), _p(indices), n_out, _p(el), _p(er_out), _p(z), H, D, slope, _p(m), _p(g_s),
-                                       _p(g_n), _p(g_el), _p(g_er_out), _p(g_z), _stream()), "csl_gat_bwd_f32")
+                _gat_call("bwd", ctx.attn, _p(indptr), _p(indices), n_out, _p(el), _p(er_out), _p(z), H, D, slope, _p(m), _p(g_s),
+                          _p(g_n), _p(g_el), _p(g_er_out), _p(g_z))
             g_er = torch.zeros((n_in, H), dtype=torch.float32, device=dev)
             scatter_add_rows_(g_er, self_ids_in, g_er_out)              # (a node is the self source of one destination)
             _chk(L.csl_gat_logits_bwd_acc_f32(_p(z), _p(al), _p(ar), _p(g_el), _p(g_er), n_in, H, D, _p(g_z), 1,
@@ -1020,7 +1097,7 @@ class GatLayerLocal(torch.autograd.Function):
             gx = g_z @ weight if _GAT_TORCH_MM else gemm(g_z, weight)   # rows behind n_in are zero (g_z's are)
             if gx.shape[0] != ctx.x_rows:
                 gx = gx[:ctx.x_rows]
-        return gx, gw, g_al, g_ar, g_bias, None, None, None, None, None, None, None, None, None, None, None, None, None
+        return (gx, gw, g_al, g_ar, g_bias) + (None,) * 15
 
 
 class FeatureRows(object):

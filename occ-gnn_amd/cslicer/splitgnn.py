@@ -510,24 +510,47 @@ class DistGATConv(nn.Module):
         el, er = aggr.GatLogits.apply(z, self.attn_l, self.attn_r)
         return z, el, er
 
-    def forward_parts(self, sl, x, elu=False, pad_out=False):
+    @staticmethod
+    def _feat_drop(drop, sl, x, layer, row_pad=None):
+        """feature dropout of a hidden layer's output rows x (after the ELU) on one part, keyed by the rows' node ids: the
+        out_nodes of the rows the part owns (every row where it is the only part).  row_pad: into a fresh row-padded
+        buffer (aggr.DropoutRows), what the next fused layer takes."""
+        ids = sl.out_nodes if x.shape[0] == sl.n_out and sl.n_parts == 1 else sl.out_nodes[sl.owned_out_nodes.long()]
+        if row_pad is not None:
+            return aggr.DropoutRows.apply(x, ids, drop.p_f, drop.seed, layer, drop.step, row_pad)
+        return aggr.Dropout.apply(x, ids, drop.p_f, drop.seed, layer, drop.step)
+
+    def forward_parts(self, sl, x, elu=False, pad_out=False, drop=None, layer=0):
         """sl[g]: Slice of part g, x[g]: features of sl[g].in_nodes.  Returns per part the [n_owned, H*D]
         output rows of the nodes it owns (frontier order); elu: apply the ELU that follows a hidden layer; pad_out
-        (fused single-part layer only): hand the output on as an aggr.PaddedRows."""
+        (fused single-part layer only): hand the output on as an aggr.PaddedRows.
+        drop: an aggr.GatDropSpec, `layer` this layer's number in the model (0 = the deepest): attention
+        dropout inside the aggregation, feature dropout on the output where an ELU precedes it (a hidden layer).  The
+        single part's fused node (aggr.GatLayerLocal) takes both: its aggregation and backward are the dropped twins, its
+        epilogue writes the undropped output (kept for ELU') and the dropped one.  The aggregate-then-project input layer
+        has no attention dropout -- with p_a > 0 the deepest layer gathers its rows and projects first -- and is followed
+        by the feature dropout out of place.  None or both probabilities 0: attn and feat below are None and every call is
+        the one it has always been."""
+        drop = aggr.gat_drop(drop)
         parts = sorted(sl.keys())
+        feat = drop is not None and drop.p_f > 0 and elu
         if len(parts) == 1 and sl[parts[0]].n_parts == 1 and not _NO_LOCAL_FUSE and (
                 isinstance(x[parts[0]], (aggr.PaddedRows, aggr.FeatureRows)) or x[parts[0]].is_cuda):
             # one part holding every node: the whole layer (+ ELU) as one autograd node.  The layers hand each other
             # row-padded buffers (aggr.PaddedRows), so that none copies its input into a padded GEMM operand again
             g = parts[0]
             xin = x[g]
+            attn = aggr.attn_drop(drop, sl[g], layer)
             if isinstance(xin, aggr.FeatureRows):
                 # the deepest layer on the resident feature table: aggregate the raw rows, project the destinations
-                if (not _NO_GAT_INPUT and not xin.table.requires_grad      # (the layer returns no input gradient)
+                if (attn is None and not _NO_GAT_INPUT and not xin.table.requires_grad      # (the layer returns no input gradient)
                         and aggr.gat_input_ok(self.H, xin.table.shape[1], sl[g].fanout, self.D)):
                     out = aggr.GatInputLayer.apply(xin.table, xin.rows, self.fc.weight, self.attn_l, self.attn_r, self.bias,
                                                    sl[g].indptr, sl[g].indices, sl[g].self_ids_in, sl[g].n_out,
-                                                   sl[g].n_edges, sl[g].fanout, self.slope, bool(elu), ROW_PAD, bool(pad_out))
+                                                   sl[g].n_edges, sl[g].fanout, self.slope, bool(elu), ROW_PAD,
+                                                   bool(pad_out) and not feat)
+                    if feat:     # (into the row-padded buffer the next layer takes, where it takes one)
+                        out = self._feat_drop(drop, sl[g], out, layer, ROW_PAD if pad_out else None)
                     return {g: aggr.PaddedRows(out, sl[g].n_out) if pad_out else out}
                 xp = aggr.padded_rows(xin.rows.numel(), xin.table.shape[1], ROW_PAD, xin.table.device)
                 aggr.gather_rows(xin.table, xin.rows, out=xp.t[:xp.n])
@@ -536,21 +559,29 @@ class DistGATConv(nn.Module):
             out = aggr.GatLayerLocal.apply(xin.t if padded else xin, self.fc.weight, self.attn_l, self.attn_r, self.bias,
                                            sl[g].indptr, sl[g].indices, sl[g].self_ids_in, sl[g].n_out, self.slope,
                                            bool(elu), ROW_PAD, _weight_grad, sl[g].t_indptr, sl[g].t_indices,
-                                           sl[g].t_max_len, xin.n if padded else None, bool(pad_out))
+                                           sl[g].t_max_len, xin.n if padded else None, bool(pad_out), attn,
+                                           aggr.feat_drop(drop, sl[g], layer) if feat else None)
             return {g: aggr.PaddedRows(out, sl[g].n_out) if pad_out else out}
         x = {g: (aggr.gather_rows(v.table, v.rows) if isinstance(v, aggr.FeatureRows) else v) for g, v in x.items()}
-        out = self._forward_parts(sl, {g: (v.t[:v.n] if isinstance(v, aggr.PaddedRows) else v) for g, v in x.items()})
-        return {g: torch.nn.functional.elu(v) for g, v in out.items()} if elu else out
+        out = self._forward_parts(sl, {g: (v.t[:v.n] if isinstance(v, aggr.PaddedRows) else v) for g, v in x.items()},
+                                  {g: aggr.attn_drop(drop, sl[g], layer) for g in parts})
+        if elu:
+            out = {g: torch.nn.functional.elu(v) for g, v in out.items()}
+        return {g: self._feat_drop(drop, sl[g], v, layer) for g, v in out.items()} if feat else out
 
-    def _forward_parts(self, sl, x):
+    def _forward_parts(self, sl, x, attn=None):
+        """attn: per part aggr.attn_drop()'s tuple or None (attention dropout; the partial states merge as without it: only
+        the numerators are dropped); None: none on any part"""
         parts = sorted(sl.keys())
         H, D = self.H, self.D
+        attn = attn if attn is not None else dict.fromkeys(parts)
         if len(parts) == 1 and sl[parts[0]].n_parts == 1:
             # one part holding every node: every out node is owned (owned_out_nodes = 0..n_out-1), nothing to merge
             g = parts[0]
             z, el, er = self.project(x[g])
             er_out = aggr.GatherRows.apply(er, sl[g].self_ids_in)
-            _, S, N = aggr.GatAggregate.apply(el, er_out, z, sl[g].indptr, sl[g].indices, sl[g].n_out, H, D, self.slope)
+            _, S, N = aggr.GatAggregate.apply(el, er_out, z, sl[g].indptr, sl[g].indices, sl[g].n_out, H, D, self.slope,
+                                              attn[g])
             return {g: (N.view(-1, H, D) / S.clamp_min(1e-30).unsqueeze(-1)).reshape(-1, H * D) + self.bias}
         proj = {g: self.project(x[g]) for g in parts}
         # er of the destinations: owned rows from the part's own projection ...
@@ -565,7 +596,7 @@ class DistGATConv(nn.Module):
                 if p != g and sl[g].from_ids[p].numel():
                     er_out[g] = er_out[g].index_copy(0, sl[g].from_ids[p].long(), er_own[p][sl[p].to_ids[g].long()])
         part = {g: aggr.GatAggregate.apply(proj[g][1], er_out[g], proj[g][0], sl[g].indptr, sl[g].indices,
-                                           sl[g].n_out, H, D, self.slope) for g in parts}
+                                           sl[g].n_out, H, D, self.slope, attn[g]) for g in parts}
         out = {}
         for p in parts:
             M, S, N = part[p]
@@ -586,11 +617,13 @@ class DistGATConv(nn.Module):
         return out
 
 
-    def _forward_rank(self, sl, x, comm):
+    def _forward_rank(self, sl, x, comm, attn=None, node_by_node=False):
         """One part per process (DistGATConv.forward_rank): two boundary exchanges per layer.  On the GPU the layer is one
         autograd node (aggr.GatLayerRank: fused kernels, exchanges over the back-to-back per-peer lists);
-        CSLICER_GAT_RANK_AUTOGRAD=1: the node-by-node form below (A/B switch, and what the CPU / gloo tests run)."""
-        if x.is_cuda and not _GAT_RANK_AUTOGRAD:
+        CSLICER_GAT_RANK_AUTOGRAD=1: the node-by-node form below (A/B switch, and what the CPU / gloo tests run).
+        attn: aggr.attn_drop()'s tuple: attention dropout; node_by_node: take the form below whatever the device (a model
+        with dropout: the fused rank node has none, the rule DESIGN 4.6 applies to GraphSAGE's dropout on the rank path)."""
+        if x.is_cuda and not _GAT_RANK_AUTOGRAD and attn is None and not node_by_node:
             return aggr.GatLayerRank.apply(x, self.fc.weight, self.attn_l, self.attn_r, self.bias, sl, comm, self.slope, False)
         g, P, H, D = sl.part, sl.n_parts, self.H, self.D
         z, el, er = self.project(x)
@@ -603,7 +636,7 @@ class DistGATConv(nn.Module):
         for p in range(P):
             if recv[p] is not None:
                 er_out = er_out.index_copy(0, sl.from_ids[p].long(), recv[p])
-        M, S, N = aggr.GatAggregate.apply(el, er_out, z, sl.indptr, sl.indices, sl.n_out, H, D, self.slope)
+        M, S, N = aggr.GatAggregate.apply(el, er_out, z, sl.indptr, sl.indices, sl.n_out, H, D, self.slope, attn)
         # 2) holders -> owners: the partial softmax state (m | s | n) of the boundary rows
         packed = torch.cat([M, S, N], dim=1)
         send = [packed[sl.from_ids[p].long()] if p != g and sl.from_ids[p].numel() else None for p in range(P)]
@@ -638,7 +671,9 @@ class DistGATModel(nn.Module):
         self.heads = heads
         self.convs = nn.ModuleList([DistGATConv(dims[k], outs[k], heads) for k in range(n_layers)])
 
-    def forward_parts(self, slices, feats):
+    def forward_parts(self, slices, feats, drop=None):
+        """drop: an aggr.GatDropSpec: feature dropout on every hidden layer's output, attention dropout in
+        every layer's aggregation, here and in forward_rank; None or both probabilities 0: no dropout code runs"""
         L = len(slices)
         parts = sorted(slices[0].keys())
         x = {g: feats[g] for g in parts}
@@ -646,19 +681,24 @@ class DistGATModel(nn.Module):
                  (isinstance(x[parts[0]], (aggr.PaddedRows, aggr.FeatureRows)) or x[parts[0]].is_cuda))
         for k, conv in enumerate(self.convs):
             last = k + 1 == len(self.convs)
-            x = conv.forward_parts(slices[L - 1 - k], x, elu=not last, pad_out=fused and not last)
+            x = conv.forward_parts(slices[L - 1 - k], x, elu=not last, pad_out=fused and not last, drop=drop, layer=k)
             if last:
                 x = {g: x[g].view(-1, self.heads, conv.D).mean(1)[:, :self.n_classes] for g in parts}
         return x
 
-    def forward_rank(self, slices, feat, rank, comm):
-        """One part per process: `comm` (DistComm) carries the two exchanges of every layer over RCCL."""
+    def forward_rank(self, slices, feat, rank, comm, drop=None):
+        """One part per process: `comm` (DistComm) carries the two exchanges of every layer over RCCL.  drop: as in
+        forward_parts; with it every layer runs node by node (the fused rank node has no dropout)."""
         L = len(slices)
         x = feat
+        drop = aggr.gat_drop(drop)
         for k, conv in enumerate(self.convs):
-            x = conv._forward_rank(slices[L - 1 - k][rank], x, comm)
+            sl = slices[L - 1 - k][rank]
+            x = conv._forward_rank(sl, x, comm, aggr.attn_drop(drop, sl, k), drop is not None)
             if k + 1 < len(self.convs):
                 x = torch.nn.functional.elu(x)
+                if drop is not None and drop.p_f > 0:
+                    x = conv._feat_drop(drop, sl, x, k)
             else:
                 x = x.view(-1, self.heads, conv.D).mean(1)[:, :self.n_classes]
         return x

@@ -79,7 +79,8 @@ def step_plan(kind, world, rank_path, n_layers, F, hidden, n_classes, heads, fan
     loaded (feat_dim, or the shape of a feature matrix; False: callable features without feat_dim); dropout: the
     trainer's probability -- above 0 the rank path runs its autograd step (the native rank sequencer has no dropout), with
     the engine flags that step has always asked for; every other row is what it is at 0.  multilabel: the trainer's --
-    the native rank sequencer has no sigmoid-BCE loss either, so with True its row moves the same way and no other does."""
+    the native rank sequencer has no sigmoid-BCE loss either, so with True its row moves the same way and no other does.
+    (The attention model's dropout: step_plan_gat_drop below.)"""
     sage, gat = kind == "sage", kind == "gat"
     single = not rank_path and world == 1      # one part in one process, no collective
     want = table_f32 if gat_input is None else gat_input     # (None: a 16-bit table keeps the numbers its runs have had)
@@ -125,6 +126,19 @@ def step_plan(kind, world, rank_path, n_layers, F, hidden, n_classes, heads, fan
     return StepPlan(flags, path, gat_in, form)
 
 
+def step_plan_gat_drop(feat_dropout=0.0, attn_dropout=0.0, *, kind, gat_input, **cfg):
+    """step_plan(kind=kind, gat_input=gat_input, **cfg) under the attention model's two dropout probabilities (DESIGN 4.11);
+    at 0, their defaults, it IS step_plan.  attn_dropout > 0 turns the input layer off where gat_input is None
+    (aggr.GatInputLayer has no attention dropout; gat_input=True with it is the constructor's refusal): the plan is
+    gat_input=False's, engine flags and input form included.  Either above 0 moves a rank run of the attention model from the
+    fused rank node to its node-by-node form; that is the model's doing (DistGATModel.forward_rank with a drop spec) -- the
+    plan's fields, flags 0, path "parts", input form "rows", are the same for both forms.  feat_dropout alone changes no plan.
+    (A function of its own: step_plan's parameter list is pinned.)"""
+    if kind == "gat" and attn_dropout > 0 and gat_input is None:
+        gat_input = False
+    return step_plan(kind=kind, gat_input=gat_input, **cfg)
+
+
 class Trainer(object):
     # result slots of the engine: round r lives in slot r % SLOTS.  Three, so that the slot the NEXT round is sliced
     # into was last read two rounds ago: waiting for that round's end event never drains the training stream (with
@@ -136,7 +150,7 @@ class Trainer(object):
                  model="sage", heads=8, rank_path=None, workload=None, feat_dim=None, rng_seed=5489,
                  feature_dtype="float32", gat_input=None, replace=True, dropout=0.0, dropout_seed=None,
                  multilabel=False, weight_decay=0.0, decoupled_weight_decay=True, decay_bias=False, max_grad_norm=None,
-                 lr_schedule=None, class_weight=None, label_smoothing=0.0):
+                 lr_schedule=None, class_weight=None, label_smoothing=0.0, feat_dropout=0.0, attn_dropout=0.0):
         """Part `rank` of `world`.  Ownership = the engine's workload table (`workload` int32 [N], the METIS map of
         python/utils/sampler.py:64-134 / partition_map_opt.bin; None = v % world like pyfrontend.cpp:57): the rank
         keeps the feature and label rows of the nodes it owns, in ascending node order.
@@ -207,6 +221,17 @@ class Trainer(object):
         `self.loss_spec` is None and no new code runs.  evaluate()["loss"] stays the plain mean cross-entropy whatever
         the options.  multilabel=True refuses both: the sigmoid-BCE loss has no weights yet.
 
+        feat_dropout, attn_dropout (default 0.0 both): the attention model's dropout (include/
+        cslicer_gat_dropout.h), two independent probabilities in [0, 1), model="gat" only.  feat_dropout drops each element of
+        every hidden layer's output after its ELU (the input of every layer but the deepest; the feature table is never
+        dropped); attn_dropout drops each normalised attention coefficient alpha_h(u -> v) of every layer, inside the fused
+        aggregation kernels (the softmax's numerator only).  Both masks are Philox4x32-10 of (dropout_seed, steps_done,
+        layer, ...): the feature mask keyed by (node id, column) as `dropout`'s, the attention mask by (source node id,
+        destination node id, head) -- so two sampled copies of one edge share a draw, and a run is the same on one GPU and
+        on any number of parts.  attn_dropout > 0 takes the deepest layer off aggr.GatInputLayer (gat_input=None: off;
+        gat_input=True: a ValueError); either above 0 runs a rank's layers node by node (the fused rank node has neither).
+        At 0 / 0 no dropout code runs; evaluate() / predict() never drop.
+
         `self.plan` is the StepPlan of the configuration (step_plan above): which step the trainer runs, decided here
         once; `self.native` / `self.native_rank` are the native stepper of that path, None on every other path."""
         # -- 1. the arguments (before any device call: a request that cannot be served is an error, never a quiet fall-back)
@@ -231,6 +256,16 @@ class Trainer(object):
         if dropout > 0 and hidden % 4 != 0:
             raise ValueError("dropout > 0: hidden must be a multiple of 4 (the kernel moves float4 columns), not %d" % hidden)
         self.dropout, self.dropout_seed = dropout, int(seed if dropout_seed is None else dropout_seed)
+        feat_dropout, attn_dropout = float(feat_dropout), float(attn_dropout)
+        for name, v in (("feat_dropout", feat_dropout), ("attn_dropout", attn_dropout)):
+            if not 0.0 <= v < 1.0:      # (a NaN compares false)
+                raise ValueError("%s must be in [0, 1), not %r" % (name, v))
+            if v > 0 and model == "sage":
+                raise ValueError("%s > 0: GraphSAGE has `dropout`; feat_dropout / attn_dropout belong to model='gat'" % name)
+        if attn_dropout > 0 and gat_input is True:
+            raise ValueError("attn_dropout > 0 with gat_input=True: the aggregate-then-project input layer has no attention "
+                             "dropout (gat_input=None turns it off)")
+        self.feat_dropout, self.attn_dropout = feat_dropout, attn_dropout
         weight_decay = float(weight_decay)
         if not weight_decay >= 0.0:      # (a NaN compares false)
             raise ValueError("weight_decay must be >= 0, not %r" % (weight_decay,))
@@ -316,9 +351,11 @@ class Trainer(object):
         F = f_own.shape[1] if feat_dim is None else feat_dim
         # -- 3. how this configuration trains, 4. the engine it needs.  One process per part: only this rank's slices are
         # materialised (the sampling itself is replicated)
-        self.plan = step_plan(model, world, self.rank_path, self.L, F, hidden, n_classes, heads, fanouts[-1],
-                              fdt == torch.float32, gat_input, replace, sw, width_known=F_early is not None,
-                              dropout=dropout, multilabel=self.multilabel)
+        self.plan = step_plan_gat_drop(feat_dropout, attn_dropout, kind=model, world=world, rank_path=self.rank_path,
+                                       n_layers=self.L, F=F, hidden=hidden, n_classes=n_classes, heads=heads,
+                                       fanout=fanouts[-1], table_f32=fdt == torch.float32, gat_input=gat_input,
+                                       replace=replace, sw=sw, width_known=F_early is not None, dropout=dropout,
+                                       multilabel=self.multilabel)
         self.gat_input, self.replace = self.plan.gat_input, bool(replace)
         self.eng = _abi.Engine(indptr, indices, n_parts=self.P, fanouts=fanouts, max_batch=batch,
                                n_streams=streams, n_slots=self.SLOTS, device=device, mode=_abi.MODE_GRAPH,
@@ -417,6 +454,13 @@ class Trainer(object):
         """the DropSpec of the step about to run (its counter: the steps done so far), None without dropout"""
         return aggr.DropSpec(self.dropout, self.dropout_seed, self.steps_done) if self.dropout > 0 else None
 
+    def _gat_drop(self):
+        """the attention model's keyword for the step about to run: its GatDropSpec (counter: the steps done so far), or
+        nothing without feat_dropout / attn_dropout, so that the call is the one it has been"""
+        if not (self.feat_dropout > 0 or self.attn_dropout > 0):
+            return {}
+        return {"drop": aggr.GatDropSpec(self.feat_dropout, self.attn_dropout, self.dropout_seed, self.steps_done)}
+
     def _scale(self, den):
         """what the summed loss is multiplied by: 1 / seeds, and for the multi-label loss 1 / (seeds * classes), the
         mean over elements"""
@@ -491,12 +535,13 @@ class Trainer(object):
         _roctx.pop()
         t1 = time.perf_counter()
         _roctx.push("forward")
-        # (drop: GraphSAGE only -- the constructor refuses the attention model with dropout > 0, so self._drop() is None there)
-        kw = {"drop": self._drop()} if self.kind == "sage" else {}
+        # (`dropout` is GraphSAGE's -- the constructor refuses the attention model with dropout > 0 -- and feat_dropout /
+        # attn_dropout the attention model's)
+        kw = {"drop": self._drop()} if self.kind == "sage" else self._gat_drop()
         if not self.rank_path:
             logits = self.model.forward_parts(slices, {0: x}, **kw)[0]
         elif self.kind == "gat":
-            logits = self.model.forward_rank(slices, x, self.rank, self.comm)
+            logits = self.model.forward_rank(slices, x, self.rank, self.comm, **kw)
         else:
             logits = self.model.forward_rank(slices, x, self.rank, self.comm, overlap=self.overlap, **kw)
         top = layers[-1]
@@ -865,6 +910,12 @@ def _parser():
     ap.add_argument("--fan-out", type=str, default="10,10,25")
     ap.add_argument("--batch-size", type=int, default=1032)
     ap.add_argument("--dropout", type=float, default=0)
+    ap.add_argument("--feat-dropout", type=float, default=None,
+                    help="(extra) --model-name gat: dropout on every hidden attention layer's output "
+                         "(`Trainer(feat_dropout=...)`)")
+    ap.add_argument("--attn-dropout", type=float, default=None,
+                    help="(extra) --model-name gat: dropout on the normalised attention coefficients "
+                         "(`Trainer(attn_dropout=...)`); --gat-input auto then turns the input layer off")
     ap.add_argument("--max-steps", type=int, default=0, help="(extra) stop an epoch after this many minibatches")
     ap.add_argument("--partition", choices=("mod", "file"), default="mod",
                     help="(extra) node ownership: `mod` = v %% world (pyfrontend.cpp:57), `file` = the L0 directory's "
@@ -972,6 +1023,10 @@ def main(argv=None):
     (cslicer.l0), a preset name (arxiv-like, products-like, papers-like) or `synthetic`.
     --dropout: `Trainer(dropout=...)`, between the GraphSAGE layers as models/factory.py:41 applies it (the default, 0,
     runs none; the attention model refuses a value above 0).
+    --feat-dropout P, --attn-dropout P (extra): `Trainer(feat_dropout=P)`, `Trainer(attn_dropout=P)`, --model-name gat only:
+    dropout on every hidden attention layer's output (after its ELU) and on the normalised attention coefficients (DESIGN
+    4.11); both keyed by the run's seed and the step.  --attn-dropout above 0 takes the deepest layer off the
+    aggregate-then-project input layer (--gat-input auto: off; --gat-input on: an error).
     Accepted and ignored (no counterpart here): --cache-per (features are resident in HBM), --num-workers,
     --debug, --log-every.
     --eval-split (extra): `none` (default) trains on every node and never evaluates; `file` trains on the L0 directory's
@@ -1007,7 +1062,8 @@ def main(argv=None):
         python -m cslicer.train --graph products-like --multilabel --eval-split holdout --max-steps 50
         python -m cslicer.train --graph products-like --dropout 0.5 --weight-decay 5e-4 --clip-grad-norm 1 --lr-warmup 100 --lr-schedule cosine
         python -m cslicer.train --graph <L0 dir> --feature-dtype bfloat16 --eval-split holdout
-        python -m cslicer.train --graph products-like --model-name gat --feature-dtype bfloat16 --gat-input on"""
+        python -m cslicer.train --graph products-like --model-name gat --feature-dtype bfloat16 --gat-input on
+        python -m cslicer.train --graph products-like --model-name gat --feat-dropout 0.6 --attn-dropout 0.6 --eval-split holdout"""
     a = _parser().parse_args(argv)
     from . import l0
     if a.multilabel and (a.label_smoothing is not None or a.class_weight is not None):
@@ -1075,6 +1131,8 @@ def main(argv=None):
                  workload=workload, feat_dim=fdim, feature_dtype=fdtype,
                  gat_input={"auto": None, "on": True, "off": False}[a.gat_input], replace=not a.no_replace,
                  dropout=a.dropout, **({"multilabel": True} if a.multilabel else {}), **_optimizer_kw(a, per_epoch),
+                 **({} if a.feat_dropout is None else {"feat_dropout": a.feat_dropout}),
+                 **({} if a.attn_dropout is None else {"attn_dropout": a.attn_dropout}),
                  **_loss_kw(a, labels, train_nodes, indptr.shape[0] - 1, n_classes))
     if rank == 0 and fdtype != "float32":
         print("feature table: %s, %d bytes on this rank" % (fdtype, tr.feat.numel() * tr.feat.element_size()))

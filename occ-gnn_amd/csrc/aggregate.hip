@@ -22,6 +22,7 @@
 #include "cslicer_hip.h"
 #include "dev_common.h"
 #include "feat_elem.h"
+#include "gat_dev.h"
 #include "table_readers.h"
 
 namespace {
@@ -1846,3 +1847,20 @@ int csl_sage_cat_rows_bwd_f32(const int32_t* self_ids, const int32_t* owned, con
 }
 
 }  // extern "C"
+
+// ---- what gat_dropout.hip runs unchanged (gat_dev.h)
+long long gatx::t_rows(long long n) { return gat_t_rows(n); }
+
+void gatx::logits_bwd_dst(const float* z, const float* attn_r, const int32_t* self_ids_in, const float* g_er_out, int64_t n_out,
+                          int32_t H, int32_t D, float* g_z, float* part_r, long long rows_per_block, void* stream) {
+  const long long blocks = (n_out + rows_per_block - 1) / rows_per_block;
+  hipLaunchKernelGGL(k_gat_logits_bwd_dst, dim3((unsigned)blocks), dim3(BLK), 0, (hipStream_t)stream, z, attn_r, self_ids_in,
+                     g_er_out, (long long)n_out, (int)H, (int)D, g_z, part_r, rows_per_block);
+}
+
+long long gatx::finish_rows(long long n) { return gat_finish_rows(n); }
+
+void gatx::colsum_finish(const float* partial, long long blocks, int32_t C, float* g_bias, void* stream) {
+  hipLaunchKernelGGL(k_colsum_finish, dim3((unsigned)((C + 63) / 64)), dim3(BLK), 0, (hipStream_t)stream, partial, blocks,
+                     (int)C, g_bias);
+}

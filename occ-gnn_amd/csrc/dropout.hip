@@ -7,22 +7,11 @@
 
 #include "cslicer_dropout.h"
 #include "dev_common.h"
+#include "philox_dev.h"
 
 namespace {
 
 constexpr int DBLK = 256;
-
-// one round: (hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0) with (hi0, lo0) = M0 * c0, (hi1, lo1) = M1 * c2; the key moves by
-// its increments between rounds.  Fully unrolled: ten rounds, two 32 x 32 -> 64 multiplies each.
-__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; r++) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c.x, p1 = (uint64_t)0xCD9E8D57u * c.z;
-    c = make_uint4((uint32_t)(p1 >> 32) ^ c.y ^ k0, (uint32_t)p1, (uint32_t)(p0 >> 32) ^ c.w ^ k1, (uint32_t)p0);
-    k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
-  }
-  return c;
-}
 
 // A row is walked by 2^lg lanes (the power of two that covers its H / 4 quads, 64 at the most), 256 >> lg rows per
 // workgroup: the row and the lane come out of shifts, a lane reads its node id once.  x and y may be the same matrix
