@@ -211,6 +211,22 @@ void csl_destroy(csl_engine* e);
  * uploaded once; rounds then take consecutive minibatches from it. */
 int csl_set_nodes(csl_engine* e, const int64_t* host_nodes, int64_t n);
 
+/* Edge-weighted neighbour sampling (the `prob` argument of dgl.sampling.sample_neighbors), graph mode, with replacement.
+ * host_cum[num_edges], in the CSR's own edge order: inside row v (off = indptr[v], deg edges) cum[off + i] =
+ * q_0 + ... + q_i for integer weights q_i >= 0, so a row's values never decrease and its total T = cum[off + deg - 1]
+ * fits 32 bits.  Once set, every round maps the draws of a row with deg >= fanout -- the same fanout words at the same
+ * ring positions; draws, rng_begin/rng_end and CSL_ERR_RNG_WINDOW are unchanged -- to edge positions through the table:
+ * x = ((uint64)r_j * T) >> 32, pick_j = the smallest i in [0, deg) with cum[off + i] > x, candidate slot j + 1 =
+ * indices[off + pick_j].  An edge is picked with probability q_i / T (within 2^-32); an edge with q_i == 0 never.  A row
+ * with T == 0 is drawn as without a table (r_j % deg).  Rows with deg < fanout keep ALL their edges in order, zero-weight
+ * ones included: weights bias the draw, they do not filter the graph.  A picked self loop is dropped as ever; everything
+ * behind the candidate stream is untouched.
+ * Needs CSL_MODE_GRAPH without CSL_FLAG_NO_REPLACE (else CSL_E_INVALID) and must come before the first submitted round
+ * (else CSL_E_STATE).  The table is copied to the device (4 bytes per edge, counted by csl_device_bytes) and checked
+ * there once: a row that decreases returns CSL_E_INVALID and leaves the engine as it was (unweighted).  Any other
+ * malformed table gives wrong picks, never a read outside the row. */
+int csl_set_edge_cdf(csl_engine* e, const uint32_t* host_cum /* [num_edges] */);
+
 /* WorkerPool::run's batch loop + Slicer::run (WorkerPool.cpp:41-50,
  * slicer.cpp:120-140) for n_batches <= S minibatches: minibatch k =
  * nodes[(first_batch+k)*batch : ...] goes to stream k.  Asynchronous. */

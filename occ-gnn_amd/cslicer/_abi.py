@@ -42,7 +42,7 @@ SYMBOLS = [
     "csl_timing_enable", "csl_timing_read", "csl_kernel_name", "csl_rng_peek", "csl_device_bytes",
     "csl_debug_wave_duplicates",
     "csl_fetch_sample", "csl_fetch_sample32", "csl_totals", "csl_arena_info", "csl_copy_candidates",
-    "csl_noreplace_max_fanout",
+    "csl_noreplace_max_fanout", "csl_set_edge_cdf",
 ]
 
 
@@ -166,6 +166,7 @@ def load():
     L.csl_destroy.argtypes = [vp]
     L.csl_destroy.restype = None
     L.csl_set_nodes.argtypes = [vp, p64, C.c_int64]
+    L.csl_set_edge_cdf.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.csl_submit_round.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32]
     L.csl_submit_seeds.argtypes = [vp, p64, p64, C.c_int32, C.c_int32]
     L.csl_sync.argtypes = [vp]
@@ -233,6 +234,7 @@ class Engine:
                         flags=flags, part_mask=part_mask)
         self._log = [] if (frontier_cap is not None and recover) else None   # submissions since creation
         self.recovered = 0
+        self.edge_cdf = None     # set_edge_cdf's table (kept: a recovered engine is given it again)
         self._create(indptr, indices, frontier_cap=frontier_cap, **self._kw)
 
     def _create(self, indptr, indices, n_parts, fanouts, max_batch, n_streams, n_slots, workload, device, rng_seed,
@@ -296,11 +298,24 @@ class Engine:
         log, self._log = self._log, None          # (the replay below must not log again; the worst case cannot overflow)
         self.close()
         self._create(self.indptr, self.indices, frontier_cap=None, **self._kw)
+        if self.edge_cdf is not None:
+            self.set_edge_cdf(self.edge_cdf)
         for what, args in log:
             getattr(self, what)(*args)
         self.recovered += 1
 
     # -- submission
+    def set_edge_cdf(self, cum):
+        """csl_set_edge_cdf: uint32 [num_edges], per row the running sum of the integer edge weights (l0.edge_cdf makes
+        one from float weights).  Graph mode with replacement, before the first round.  A refused table leaves the
+        engine unweighted."""
+        cum = np.ascontiguousarray(cum, dtype=np.uint32)
+        if cum.shape != (self.indices.shape[0],):
+            raise ValueError("edge table has shape %s, the graph %d edges" % (cum.shape, self.indices.shape[0]))
+        buf = cum if cum.shape[0] else np.zeros(1, dtype=np.uint32)
+        _check(load().csl_set_edge_cdf(self._h, buf.ctypes.data_as(C.POINTER(C.c_uint32))))
+        self.edge_cdf = cum
+
     def set_nodes(self, nodes):
         nodes = np.ascontiguousarray(nodes, dtype=np.int64)
         if self._log is not None:

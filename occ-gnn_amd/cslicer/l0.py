@@ -22,6 +22,9 @@ reader cslicer/dataset.cpp:18-113):
     <dir>/train_idx.bin       int64[...]  optional training / evaluation node
     <dir>/val_idx.bin         int64[...]  split, with csum_train / csum_test
                               in meta.txt (convert_dgl_dataset.py:107-112)
+    <dir>/edge_weight.bin     float32[E]  optional (not the reference's): edge
+                              weights in CSR order, for weighted sampling
+                              (write_edge_weight / read_edge_weight)
 
 The reference reader skips a final line that has no trailing newline
 (dataset.cpp:75), so the writer always terminates every line with '\n'.
@@ -366,6 +369,74 @@ def read_splits(path):
             raise ValueError("%s holds node ids outside [0, num_nodes)" % f)
         out.append(idx)
     return out[0], out[1]
+
+
+def check_edge_weights(weights, num_edges):
+    """float64 [num_edges] of a host edge-weight array; ValueError for another length, a negative or a non-finite weight"""
+    w = np.asarray(weights)
+    if w.ndim != 1 or w.shape[0] != int(num_edges):
+        raise ValueError("edge weights have shape %r, the graph has %d edges" % (w.shape, int(num_edges)))
+    if w.dtype.kind not in "fiub":
+        raise ValueError("edge weights must be numbers, not %s" % w.dtype)
+    w = w.astype(np.float64)
+    if w.size and not (np.isfinite(w).all() and (w >= 0).all()):
+        raise ValueError("edge weights must be finite and >= 0")
+    return w
+
+
+def edge_cdf(indptr, weights):
+    """uint32 [E]: the table of csl_set_edge_cdf (include/cslicer_hip.h) for float edge weights in CSR order.  The only
+    float-to-integer step of weighted sampling: with S_v the float64 sum of row v, q_i = floor(w_i / S_v * 2^31), raised to
+    1 where w_i > 0 (so q_i == 0 iff w_i == 0), and the table holds every row's running sum of q (T_v <= 2^31 + deg).  A
+    row whose weights are all zero gets zeros: the engine draws it uniformly.  Weights must be finite and >= 0 and a row
+    may have at most 2^31 - 1 edges, else ValueError."""
+    indptr = np.asarray(indptr, dtype=np.int64)
+    w = check_edge_weights(weights, indptr[-1])
+    deg = np.diff(indptr)
+    if deg.size and int(deg.max()) > 2 ** 31 - 1:
+        raise ValueError("edge_cdf: a row of %d edges (at most 2^31 - 1)" % int(deg.max()))
+    if w.size == 0:
+        return np.zeros(0, dtype=np.uint32)
+    rows = np.repeat(np.arange(deg.shape[0], dtype=np.int64), deg)
+    start = indptr[:-1][deg > 0]
+    S = np.zeros(deg.shape[0], dtype=np.float64)
+    S[deg > 0] = np.add.reduceat(w, start)
+    Se = S[rows]
+    q = np.zeros(w.shape[0], dtype=np.int64)
+    pos = Se > 0
+    q[pos] = np.floor(w[pos] / Se[pos] * 2.0 ** 31).astype(np.int64)
+    q[pos & (w > 0) & (q == 0)] = 1
+    q[w == 0] = 0
+    c = np.cumsum(q)
+    before = np.zeros(deg.shape[0], dtype=np.int64)       # sum of q over the rows before this one
+    before[deg > 0] = c[start] - q[start]
+    cum = c - before[rows]
+    assert int(cum.max()) <= 2 ** 32 - 1
+    return cum.astype(np.uint32)
+
+
+def inv_degree_weights(indptr, indices):
+    """float32 [E]: w(v <- u) = 1 / max(deg(u), 1) for every edge of row v with source u, deg the CSR's row lengths --
+    an importance scheme that keeps hubs from flooding the deeper frontiers"""
+    deg = np.diff(np.asarray(indptr, dtype=np.int64))
+    return (1.0 / np.maximum(deg[np.asarray(indices, dtype=np.int64)], 1)).astype(np.float32)
+
+
+def write_edge_weight(path, weights):
+    """edge_weight.bin of an L0 directory: float32 [num_edges] in CSR order, beside the other files (meta.txt unchanged)"""
+    w = check_edge_weights(weights, read_meta(path)["num_edges"])
+    w.astype("<f4").tofile(os.path.join(path, "edge_weight.bin"))
+
+
+def read_edge_weight(path):
+    """float32 [num_edges] of an L0 directory's edge_weight.bin; ValueError if the file's length is not the graph's"""
+    f = os.path.join(path, "edge_weight.bin")
+    if not os.path.exists(f):
+        raise ValueError("%s has no edge_weight.bin" % path)
+    e = read_meta(path)["num_edges"]
+    if os.path.getsize(f) != 4 * e:
+        raise ValueError("%s holds %d bytes, %d expected (float32 per edge)" % (f, os.path.getsize(f), 4 * e))
+    return np.fromfile(f, dtype="<f4", count=e)
 
 
 def from_edge_list(num_nodes, src, dst, symmetric=False, rows="in"):

@@ -21,7 +21,7 @@ import time
 import numpy as np
 import torch
 
-from . import _abi, _roctx, aggr, shard, splitgnn
+from . import _abi, _roctx, aggr, l0, shard, splitgnn
 
 
 # The A/B switches a trainer is built under.  They are read when the constructor runs (read_switches), never at import:
@@ -150,7 +150,8 @@ class Trainer(object):
                  model="sage", heads=8, rank_path=None, workload=None, feat_dim=None, rng_seed=5489,
                  feature_dtype="float32", gat_input=None, replace=True, dropout=0.0, dropout_seed=None,
                  multilabel=False, weight_decay=0.0, decoupled_weight_decay=True, decay_bias=False, max_grad_norm=None,
-                 lr_schedule=None, class_weight=None, label_smoothing=0.0, feat_dropout=0.0, attn_dropout=0.0):
+                 lr_schedule=None, class_weight=None, label_smoothing=0.0, feat_dropout=0.0, attn_dropout=0.0,
+                 edge_weight=None):
         """Part `rank` of `world`.  Ownership = the engine's workload table (`workload` int32 [N], the METIS map of
         python/utils/sampler.py:64-134 / partition_map_opt.bin; None = v % world like pyfrontend.cpp:57): the rank
         keeps the feature and label rows of the nodes it owns, in ascending node order.
@@ -232,6 +233,17 @@ class Trainer(object):
         gat_input=True: a ValueError); either above 0 runs a rank's layers node by node (the fused rank node has neither).
         At 0 / 0 no dropout code runs; evaluate() / predict() never drop.
 
+        edge_weight (default None: every edge of a row alike): a host float array [num_edges] in the CSR's edge order, finite
+        and >= 0 -- the `prob` argument of dgl.sampling.sample_neighbors.  A row with at least `fanout` edges then draws its
+        `fanout` neighbours, with replacement, with probability proportional to the weights: the weights are
+        quantised once on the host (l0.edge_cdf) and given to the engine (_abi.Engine.set_edge_cdf), which maps the same
+        mt19937 words through the table.  A zero-weight edge of such a row is never drawn; a row with FEWER than `fanout`
+        edges keeps all of them, zero-weight ones included: weights bias the draw, they do not filter the graph.  A row whose
+        weights are all zero is drawn uniformly.  replace=False refuses it (weighted sampling without replacement is not
+        built).  Everything behind the sampler is unchanged: the mean over the sampled neighbours stays a plain mean, and
+        evaluate() / predict() stay full-neighbour and unweighted.  Every rank holds the whole table, as it holds the whole
+        CSR.  None runs no new code.
+
         `self.plan` is the StepPlan of the configuration (step_plan above): which step the trainer runs, decided here
         once; `self.native` / `self.native_rank` are the native stepper of that path, None on every other path."""
         # -- 1. the arguments (before any device call: a request that cannot be served is an error, never a quiet fall-back)
@@ -289,6 +301,11 @@ class Trainer(object):
         if self.multilabel and (class_weight is not None or label_smoothing != 0.0):
             raise ValueError("multilabel=True: class_weight / label_smoothing belong to the single-label loss; the "
                              "sigmoid-BCE loss has no weights yet")
+        if edge_weight is not None:
+            if not replace:
+                raise ValueError("edge_weight with replace=False: weighted sampling draws with replacement (weighted sampling "
+                                 "without replacement is not built)")
+            edge_weight = l0.check_edge_weights(edge_weight, np.shape(indices)[0])
         if not replace and max(fanouts) > _abi.noreplace_max_fanout():
             raise ValueError("replace=False: fanouts %r exceed the limit of %d neighbours per row"
                              % (tuple(fanouts), _abi.noreplace_max_fanout()))
@@ -357,10 +374,16 @@ class Trainer(object):
                                        replace=replace, sw=sw, width_known=F_early is not None, dropout=dropout,
                                        multilabel=self.multilabel)
         self.gat_input, self.replace = self.plan.gat_input, bool(replace)
+        self.edge_weighted = edge_weight is not None
+        cdf = l0.edge_cdf(indptr, edge_weight) if self.edge_weighted else None
+        del edge_weight
         self.eng = _abi.Engine(indptr, indices, n_parts=self.P, fanouts=fanouts, max_batch=batch,
                                n_streams=streams, n_slots=self.SLOTS, device=device, mode=_abi.MODE_GRAPH,
                                workload=workload, part_mask=(1 << rank) if self.rank_path else 0,
                                flags=self.plan.engine_flags, rng_seed=rng_seed)
+        if cdf is not None:
+            self.eng.set_edge_cdf(cdf)
+            del cdf
         # -- 5. the resident table and the model
         # whether self.feat is a view of rows stored zero-padded to a multiple of 4 (what lets inference read it in place)
         self._feat_padded = bool(fdt != torch.float32 and f_own.shape[1] % 4)
@@ -935,6 +958,10 @@ def _parser():
     ap.add_argument("--no-replace", action="store_true",
                     help="(extra) sample rows with at least fan-out edges WITHOUT replacement (`Trainer(replace=False)`), "
                          "as dgl.sampling.sample_neighbors does by default; every fan-out must be <= 64")
+    ap.add_argument("--edge-weight", type=str, default=None, metavar="FILE|l0|inv-degree",
+                    help="(extra) edge-weighted neighbour sampling (`Trainer(edge_weight=...)`): FILE = a float32 binary of "
+                         "num_edges numbers in CSR order, l0 = the L0 directory's edge_weight.bin, inv-degree = "
+                         "1 / max(deg(source), 1) computed from the graph; not with --no-replace")
     ap.add_argument("--multilabel", action="store_true",
                     help="(extra) multi-label classification (`Trainer(multilabel=True)`): sigmoid + binary cross-entropy "
                          "over n_classes targets per node, evaluation by micro-F1; an L0 directory must say multilabel=1")
@@ -1042,6 +1069,12 @@ def main(argv=None):
     --no-replace (extra): `Trainer(replace=False)`: a row with at least fan-out edges yields that many DISTINCT edges
     (the default of dgl.sampling.sample_neighbors) instead of independent draws.  Every --fan-out number must then be
     <= 64 (_abi.noreplace_max_fanout()).
+    --edge-weight FILE|l0|inv-degree (extra): `Trainer(edge_weight=...)`: a row with at least fan-out edges draws its
+    neighbours with probability proportional to the edge weights (with replacement).  FILE = a float32 binary of
+    num_edges numbers in the CSR's edge order, `l0` = the --graph directory's edge_weight.bin (cslicer.l0.write_edge_weight),
+    `inv-degree` = w(v <- u) = 1 / max(deg(u), 1) computed from the graph, which gives `synthetic` and the presets a
+    weighted run without a file.  Weights bias the draw, they do not filter the graph: a shorter row keeps all its edges,
+    zero-weight ones included.  Evaluation stays full-neighbour and unweighted.  Not with --no-replace.
     --weight-decay W [--adam-l2] [--decay-bias] (extra): `Trainer(weight_decay=W)`: AdamW's decoupled decay of the weight
     matrices; --adam-l2: as an L2 term of the gradient instead; --decay-bias: the bias vectors too.
     --clip-grad-norm M (extra): `Trainer(max_grad_norm=M)`: the gradient's global norm is clipped to M, and a step whose
@@ -1060,6 +1093,7 @@ def main(argv=None):
 
         python -m cslicer.train --graph products-like --class-weight balanced --label-smoothing 0.1 --eval-split holdout --max-steps 50
         python -m cslicer.train --graph products-like --multilabel --eval-split holdout --max-steps 50
+        python -m cslicer.train --graph products-like --edge-weight inv-degree --eval-split holdout --max-steps 50
         python -m cslicer.train --graph products-like --dropout 0.5 --weight-decay 5e-4 --clip-grad-norm 1 --lr-warmup 100 --lr-schedule cosine
         python -m cslicer.train --graph <L0 dir> --feature-dtype bfloat16 --eval-split holdout
         python -m cslicer.train --graph products-like --model-name gat --feature-dtype bfloat16 --gat-input on
@@ -1069,6 +1103,9 @@ def main(argv=None):
     if a.multilabel and (a.label_smoothing is not None or a.class_weight is not None):
         raise SystemExit("--multilabel: --label-smoothing and --class-weight belong to the single-label loss (the sigmoid-BCE "
                          "loss has no weights yet)")
+    if a.edge_weight is not None and a.no_replace:     # (before the graph is loaded)
+        raise SystemExit("--edge-weight: weighted sampling draws with replacement and does not combine with --no-replace "
+                         "(weighted sampling without replacement is not built)")
     if a.no_replace:     # (before the graph is loaded)
         lim = _abi.noreplace_max_fanout()
         if any(int(x) > lim for x in a.fan_out.split(",")):
@@ -1117,6 +1154,18 @@ def main(argv=None):
             labels = lambda own: l0.unpack_labels(np.asarray(lmap[own]), n_classes)              # noqa: E731
         if a.partition == "file":
             workload = np.fromfile(os.path.join(a.graph, "partition_map_opt.bin"), dtype=np.int32)
+    edge_weight = None
+    if a.edge_weight == "inv-degree":
+        edge_weight = l0.inv_degree_weights(indptr, indices)
+    elif a.edge_weight == "l0":
+        if a.graph == "synthetic" or a.graph in l0.PRESETS:
+            raise SystemExit("--edge-weight l0 needs an L0 directory")
+        edge_weight = l0.read_edge_weight(a.graph)
+    elif a.edge_weight is not None:
+        if os.path.getsize(a.edge_weight) != 4 * indices.shape[0]:
+            raise SystemExit("--edge-weight %s: %d bytes, the graph's %d edges need %d (float32 each)"
+                             % (a.edge_weight, os.path.getsize(a.edge_weight), indices.shape[0], 4 * indices.shape[0]))
+        edge_weight = np.fromfile(a.edge_weight, dtype="<f4")
     train_nodes, eval_nodes = _split(a, indptr.shape[0] - 1)
     fan = tuple(int(x) for x in a.fan_out.split(","))[::-1]          # engine order: layer 0 = hop from the seeds
     if len(fan) != a.num_layers:
@@ -1133,7 +1182,9 @@ def main(argv=None):
                  dropout=a.dropout, **({"multilabel": True} if a.multilabel else {}), **_optimizer_kw(a, per_epoch),
                  **({} if a.feat_dropout is None else {"feat_dropout": a.feat_dropout}),
                  **({} if a.attn_dropout is None else {"attn_dropout": a.attn_dropout}),
-                 **_loss_kw(a, labels, train_nodes, indptr.shape[0] - 1, n_classes))
+                 **_loss_kw(a, labels, train_nodes, indptr.shape[0] - 1, n_classes),
+                 **({} if edge_weight is None else {"edge_weight": edge_weight}))
+    del edge_weight
     if rank == 0 and fdtype != "float32":
         print("feature table: %s, %d bytes on this rank" % (fdtype, tr.feat.numel() * tr.feat.element_size()))
     n = indptr.shape[0] - 1

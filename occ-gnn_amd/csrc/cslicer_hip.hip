@@ -585,11 +585,45 @@ __device__ __forceinline__ uint32_t floyd_pick(const LArgs& a, uint32_t s, unsig
 
 __global__ CSL_LB256 void k_sample(LArgs a) {
   constexpr bool NOREP = false;
+  constexpr bool WEIGHTED = false;
+  constexpr const uint32_t* cum = nullptr;
 #include "k_sample_body.inc"
 }
 __global__ CSL_LB256 void k_sample_norep(LArgs a) {
   constexpr bool NOREP = true;
+  constexpr bool WEIGHTED = false;
+  constexpr const uint32_t* cum = nullptr;
 #include "k_sample_body.inc"
+}
+// k_sample_weighted (csl_set_edge_cdf): the same body with WEIGHTED set.  `cum` is the engine's per-edge table of
+// cumulative integer weights, indexed like `indices`; it is a kernel parameter and no LArgs field, so no other kernel's
+// argument block changes.  The draws are the parent's; a word maps to an edge position by a binary search over the row's
+// slice of the table (k_sample_body.inc).
+__global__ CSL_LB256 void k_sample_weighted(LArgs a, const uint32_t* __restrict__ cum) {
+  constexpr bool NOREP = false;
+  constexpr bool WEIGHTED = true;
+#include "k_sample_body.inc"
+}
+
+// csl_set_edge_cdf's check: bit 0 of *bad is set if the table decreases inside a row.  One wave per row, lanes striding it.
+__global__ __launch_bounds__(256) void k_check_cdf(const unsigned long long* __restrict__ rowinfo,
+                                                   const uint32_t* __restrict__ off32, const uint32_t* __restrict__ cum,
+                                                   uint32_t N, uint32_t* bad) {
+  const uint32_t waves = gridDim.x * (256u / 64u);
+  for (uint32_t v = blockIdx.x * (256u / 64u) + (threadIdx.x >> 6); v < N; v += waves) {
+    unsigned long long off;
+    uint32_t deg;
+    if (off32) {
+      off = off32[v];
+      deg = off32[v + 1] - off32[v];
+    } else {
+      off = rowinfo[v] >> DEG_BITS;
+      deg = (uint32_t)(rowinfo[v] & DEG_MASK);
+    }
+    bool down = false;
+    for (uint32_t i = 1u + (threadIdx.x & 63u); i < deg; i += 64u) down |= cum[off + i] < cum[off + i - 1u];
+    if (down) atomicOr(bad, 1u);
+  }
 }
 
 // ---- k_scatter: partitions the candidate stream into the dedup buckets.
@@ -1897,6 +1931,7 @@ struct csl_engine {
   uint32_t* off32 = nullptr;
   uint32_t* indices = nullptr;
   uint8_t* wl = nullptr;
+  uint32_t* cum = nullptr;  // csl_set_edge_cdf: [E] cumulative integer edge weights per row, or null (unweighted)
   // node order
   long long* nodes = nullptr;
   int64_t n_nodes = 0;
@@ -2324,6 +2359,8 @@ int run_round(csl_engine* e, const long long* nodes_dev, int32_t n_batches, int3
       static const size_t lds_pad = getenv("CSL_SAMPLE_LDS_PAD") ? (size_t)atol(getenv("CSL_SAMPLE_LDS_PAD")) : 0;
       if (e->cfg.flags & CSL_FLAG_NO_REPLACE)
         hipLaunchKernelGGL(k_sample_norep, grid_sample, blk, lds_hist + lds_pad, st, a);
+      else if (e->cum)
+        hipLaunchKernelGGL(k_sample_weighted, grid_sample, blk, lds_hist + lds_pad, st, a, (const uint32_t*)e->cum);
       else
         hipLaunchKernelGGL(k_sample, grid_sample, blk, lds_hist + lds_pad, st, a);
     }
@@ -2435,7 +2472,7 @@ void csl_destroy(csl_engine* e) {
                   e->rngbase, e->ninfo,   e->hasedge, e->selfpos, e->firstpos, e->cand, e->cflag, e->crank,
                   e->queue,   e->nbk,     e->bcnt,    e->bcur,    e->tcnt,     e->fsize, e->meta, e->desc_dev,
                   e->ecnt,    e->srcpos,  e->tcur, e->tsum, e->acc,     e->dupflag, e->seedrep, e->dupfirst, e->dupout, e->rngend,
-                  e->candk,   e->boff,    e->ticket};
+                  e->candk,   e->boff,    e->ticket,  e->cum};
   for (void* p : ptrs)
     if (p) hipFree(p);
   for (int l = 0; l <= CSL_MAX_LAYERS; l++)
@@ -2733,6 +2770,53 @@ int csl_set_nodes(csl_engine* e, const int64_t* host_nodes, int64_t n) {
   DMALLOC(e->nodes, (size_t)n);
   HIPCHECK(hipMemcpy(e->nodes, host_nodes, sizeof(long long) * (size_t)n, hipMemcpyHostToDevice));
   e->n_nodes = n;
+  return 0;
+}
+
+int csl_set_edge_cdf(csl_engine* e, const uint32_t* host_cum) {
+  if (!e || !host_cum) return fail(CSL_E_INVALID, "null argument");
+  if (e->cfg.mode != CSL_MODE_GRAPH || (e->cfg.flags & CSL_FLAG_NO_REPLACE))
+    return fail(CSL_E_INVALID, "csl_set_edge_cdf needs CSL_MODE_GRAPH without CSL_FLAG_NO_REPLACE (weighted picks are drawn "
+                               "with replacement; strict mode is the reference's uniform sampling)");
+  if (e->rounds_submitted) return fail(CSL_E_STATE, "csl_set_edge_cdf must be called before the first round is submitted");
+  HIPCHECK(hipSetDevice(e->cfg.device));
+  uint32_t* cum = nullptr;
+  uint32_t* bad = nullptr;
+  {
+    size_t bytes = e->E * sizeof(uint32_t);
+    if (bytes == 0) bytes = sizeof(uint32_t);
+    hipError_t r = hipMalloc((void**)&cum, bytes);
+    if (r == hipSuccess) r = hipMalloc((void**)&bad, sizeof(uint32_t));
+    if (r != hipSuccess) {
+      if (cum) hipFree(cum);
+      return fail(CSL_E_NOMEM, "hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(r));
+    }
+  }
+  uint32_t flag = 0;
+  hipError_t er = hipMemset(bad, 0, sizeof(uint32_t));
+  const size_t chunk = (size_t)64 << 20;  // elements per copy, as the indices go up
+  for (size_t o = 0; er == hipSuccess && o < e->E; o += chunk) {
+    const size_t n = e->E - o < chunk ? e->E - o : chunk;
+    er = hipMemcpy(cum + o, host_cum + o, n * sizeof(uint32_t), hipMemcpyHostToDevice);
+  }
+  if (er == hipSuccess) {
+    hipLaunchKernelGGL(k_check_cdf, dim3(2048), dim3(256), 0, e->stream, (const unsigned long long*)e->rowinfo,
+                       (const uint32_t*)e->off32, (const uint32_t*)cum, e->N, bad);
+    er = hipStreamSynchronize(e->stream);
+  }
+  if (er == hipSuccess) er = hipMemcpy(&flag, bad, sizeof(uint32_t), hipMemcpyDeviceToHost);
+  hipFree(bad);
+  if (er != hipSuccess || flag) {
+    hipFree(cum);
+    if (er != hipSuccess) return fail(CSL_E_HIP, "edge table upload failed: %s", hipGetErrorString(er));
+    return fail(CSL_E_INVALID, "edge table decreases inside a row: cum[off + i] must be the running sum of the row's weights");
+  }
+  if (e->cum) {  // (set again before any round: the newer table replaces the older)
+    hipFree(e->cum);
+    e->dev_bytes -= (int64_t)((e->E ? e->E : 1) * sizeof(uint32_t));
+  }
+  e->cum = cum;
+  e->dev_bytes += (int64_t)((e->E ? e->E : 1) * sizeof(uint32_t));
   return 0;
 }
 

@@ -1,7 +1,8 @@
-// k_sample_body.inc -- the body of k_sample and of k_sample_norep (cslicer_hip.hip includes it once in each, after a
-// `constexpr bool NOREP`).  Text, not a function: k_sample stays a plain kernel of that name -- profiles and bench.py's
-// live counters look it up as `k_sample` -- and compiles to the code it had before the second kernel existed; an inlined
-// template body did not (the compiler ordered three scalar instructions of the prologue differently).
+// k_sample_body.inc -- the body of k_sample, of k_sample_norep and of k_sample_weighted (cslicer_hip.hip includes it once
+// in each, after a `constexpr bool NOREP`, a `constexpr bool WEIGHTED` and -- where the kernel has no such parameter -- a
+// null `constexpr const uint32_t* cum`).  Text, not a function: k_sample stays a plain kernel of that name -- profiles and
+// bench.py's live counters look it up as `k_sample` -- and compiles to the code it had before the other kernels existed; an
+// inlined template body did not (the compiler ordered three scalar instructions of the prologue differently).
   extern __shared__ __attribute__((aligned(16))) uint32_t s_bh[];  // [nb] bucket histogram
   uint32_t bx, s;
   if (!xcd_block(a, bx, s)) return;
@@ -117,10 +118,45 @@
           }
         }
       }
+      // csl_set_edge_cdf: word -> edge position through the row's cumulative weights.  x = (r * T) >> 32 lies in [0, T);
+      // the pick is the smallest i in [0, deg) with cum[off + i] > x (an upper bound: a zero-weight edge is never picked).
+      // The SU row totals are requested together, then the SU searches run in lock-step, one probe of each per trip, the
+      // probes of a trip in flight together.  lo <= hi < deg at every step and hi - lo halves: whatever the table holds,
+      // every probe and the gather stay inside the row and a search ends within 24 trips (deg < 2^24).
+      [[maybe_unused]] uint32_t wlo[SU];
+      if constexpr (WEIGHTED) {
+        uint32_t tot[SU], whi[SU], wx[SU], wc[SU];
+#pragma unroll
+        for (int u = 0; u < SU; u++) tot[u] = rq[u] ? cum[addr[u] + (degu[u] - 1u)] : 0u;
+        bool more = false;
+#pragma unroll
+        for (int u = 0; u < SU; u++) {
+          wx[u] = __umulhi(rnd[u], tot[u]);
+          wlo[u] = (rq[u] && !tot[u]) ? rnd[u] % degu[u] : 0u;  // T == 0: the parent's draw (deg >= fanout >= 1)
+          whi[u] = tot[u] ? degu[u] - 1u : wlo[u];
+          more |= wlo[u] < whi[u];
+        }
+        while (more) {
+#pragma unroll
+          for (int u = 0; u < SU; u++) wc[u] = wlo[u] < whi[u] ? cum[addr[u] + ((wlo[u] + whi[u]) >> 1)] : 0u;
+          more = false;
+#pragma unroll
+          for (int u = 0; u < SU; u++) {
+            if (wlo[u] < whi[u]) {
+              const uint32_t mid = (wlo[u] + whi[u]) >> 1;
+              if (wc[u] > wx[u]) whi[u] = mid;
+              else wlo[u] = mid + 1u;
+            }
+            more |= wlo[u] < whi[u];
+          }
+        }
+      }
 #pragma unroll
       for (int u = 0; u < SU; u++) {
         // (non-temporal loads here were measured 5 % slower: picks of one row share lines)
-        if constexpr (NOREP) {
+        if constexpr (WEIGHTED) {
+          if (gat[u]) val[u] = a.indices[addr[u] + wlo[u]];
+        } else if constexpr (NOREP) {
           if (gat[u])
             val[u] = a.indices[addr[u] + (rq[u] ? floyd_pick(a, s, rpos[u] - (slu[u] - 1u), slu[u] - 1u, degu[u] - f, rnd[u]) : 0u)];
         } else {
