@@ -1426,6 +1426,40 @@ class Adam(object):
             _chk(nbytes, "csl_adamw_scratch")
             self._scratch = torch.empty((max(nbytes, 8) // 8,), dtype=torch.float64, device=dev)
 
+    def state_dict(self):
+        """What a checkpoint keeps (cslicer.checkpoint): t, the moments `m` / `v` (CPU copies, in parameter order) and
+        `skipped`, plus the hyperparameters for the record.  Reading the device tensors waits for the stream."""
+        return {"t": int(self.t), "lr": float(self.lr), "betas": list(self.betas), "eps": float(self.eps),
+                "weight_decay": list(self.weight_decay), "decoupled": bool(self.decoupled), "max_grad_norm": self.max_grad_norm,
+                "m": [m.detach().cpu() for m, _ in self.state], "v": [v.detach().cpu() for _, v in self.state],
+                "skipped": int(self.skipped)}
+
+    def check_state_dict(self, d):
+        """ValueError, naming the tensor, unless d holds one `m` and one `v` per parameter, each of the parameter's shape and
+        type; nothing is changed (Trainer.load_checkpoint asks before it fills anything)"""
+        m, v = d["m"], d["v"]
+        if len(m) != len(self.state) or len(v) != len(self.state):
+            raise ValueError("optimizer state: %d / %d moment tensors for %d parameters" % (len(m), len(v), len(self.state)))
+        for k, ((pm, pv), sm, sv) in enumerate(zip(self.state, m, v)):
+            for name, dst, src in (("m", pm, sm), ("v", pv, sv)):
+                if not torch.is_tensor(src) or tuple(src.shape) != tuple(dst.shape) or src.dtype != dst.dtype:
+                    raise ValueError("optimizer state: %s[%d] is %s, parameter %d needs %s %r"
+                                     % (name, k, "%s %r" % (src.dtype, tuple(src.shape)) if torch.is_tensor(src)
+                                        else type(src).__name__, k, dst.dtype, tuple(dst.shape)))
+
+    def load_state_dict(self, d):
+        """Restore t, the moments and `skipped` from a state_dict().  The moments are FILLED (copy_), never replaced: the
+        pointer tables of __init__ alias their storage.  Another number of tensors, another shape or type is a ValueError
+        naming the tensor (check_state_dict), raised before anything is filled.  lr, betas, eps, decay and clipping stay
+        those this optimizer was constructed with (resuming with another learning rate is legitimate): the dict's values are
+        a record only."""
+        self.check_state_dict(d)
+        for (pm, pv), sm, sv in zip(self.state, d["m"], d["v"]):
+            pm.copy_(sm)
+            pv.copy_(sv)
+        self.skipped.fill_(int(d["skipped"]))
+        self.t = int(d["t"])
+
     def zero_grad(self, set_to_none=True):
         for p in self.params:
             if set_to_none:

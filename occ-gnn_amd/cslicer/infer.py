@@ -535,6 +535,17 @@ def _check_model(model, who):
                             "; its head mean stages a row in LDS" if who == "full_inference" else ""))
 
 
+def load_model(path, device=None):
+    """The model of a checkpoint file (cslicer.checkpoint, Trainer.save_checkpoint) on `device` (default: the current
+    GPU): a DistSAGEModel / DistGATModel built from the file's `model` block with the stored weights, ready for
+    full_inference / evaluate / full_inference_parts -- no Trainer, no engine.  ValueError for a file that is no
+    checkpoint."""
+    from . import checkpoint
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    return checkpoint.model_from(checkpoint.read(path), device)
+
+
 def _class_columns(model, h):
     """the last table without a GraphSAGE model's padding columns (the attention model's last layer writes none)"""
     if isinstance(model, splitgnn.DistSAGEModel):

@@ -244,6 +244,11 @@ class Trainer(object):
         evaluate() / predict() stay full-neighbour and unweighted.  Every rank holds the whole table, as it holds the whole
         CSR.  None runs no new code.
 
+        Persistence (DESIGN 4.12): save_checkpoint(path) writes the model, the optimizer state and `steps_done` to one file;
+        load_checkpoint(path) fills them back in place, bitwise; skip(n_steps, first_batch) issues the engine submissions of
+        run(n_steps, first_batch) without training, which is how a resumed run brings the sampler back to where the saved run
+        stood (the engine's state is not in the file).  A trainer that calls none of the three runs no new code.
+
         `self.plan` is the StepPlan of the configuration (step_plan above): which step the trainer runs, decided here
         once; `self.native` / `self.native_rank` are the native stepper of that path, None on every other path."""
         # -- 1. the arguments (before any device call: a request that cannot be served is an error, never a quiet fall-back)
@@ -327,6 +332,9 @@ class Trainer(object):
             if why is not None:
                 raise ValueError("gat_input=True: " + why)
         self.rank, self.world, self.dist = rank, world, dist
+        # (kept for the record a checkpoint holds: checkpoint_fields)
+        self.seed, self.rng_seed, self.feature_dtype = int(seed), int(rng_seed), feature_dtype
+        self.fanouts = tuple(int(f) for f in fanouts)
         self.P = world
         self.dev = torch.device("cuda", device)
         torch.cuda.set_device(self.dev)
@@ -665,6 +673,37 @@ class Trainer(object):
         torch.cuda.synchronize()
         return [float(x) for x in losses]
 
+    def skip(self, n_steps, first_batch=0):
+        """The engine submissions of run(n_steps, first_batch), and nothing else: the same rounds (shard.round_plan) into the
+        same result slots, every stream's meta read (so an engine error or the frontier-overflow recovery surfaces as it
+        does in a step), no minibatch trained, `steps_done` left alone.  What a resumed run calls for the minibatches the
+        interrupted run had trained: a sequence of set_nodes / run calls with some run()s replaced by skip()s
+        leaves the engine's mt19937 positions and the slot rotation where the original sequence does.  The next round is
+        sliced while this one is waited for, as in run().  Returns the number of rounds submitted."""
+        if self._ahead is not None:
+            raise RuntimeError("skip(): run(then=...) has already submitted the round %r; the announced run() must follow"
+                               % (self._ahead,))
+        plan = shard.round_plan(self.n_batches, self.S, first_batch, n_steps)
+        base, done = self._round_base, self._slot_done
+
+        def submit(r):
+            slot = (base + r) % self.SLOTS
+            if done[slot] is not None:
+                done[slot].synchronize()                  # a step of an earlier run() may still read the slot
+                done[slot] = None
+            self._submit(plan[r][0], plan[r][1], slot)
+
+        if plan:
+            submit(0)
+        for r in range(len(plan)):
+            if r + 1 < len(plan):
+                submit(r + 1)
+            slot = (base + r) % self.SLOTS
+            for s in range(plan[r][1]):
+                self.eng.meta(s, slot)                    # waits for the round; raises what _step would
+        self._round_base = (base + len(plan)) % self.SLOTS
+        return len(plan)
+
     def _submit(self, first, n, slot):
         """minibatches [first, first + n) of the node order into result slot `slot`"""
         self.eng.submit_round(first, self.B, n, slot=slot)
@@ -775,6 +814,62 @@ class Trainer(object):
             return infer.evaluate_parts(*args, self.comm, nodes, self.labels, owner=self.owner, **kw)
         return infer.evaluate(*args, labels=self.labels, **kw)
 
+    # -- persistence: one file (cslicer.checkpoint)
+    def checkpoint_fields(self):
+        """the `trainer` block of a checkpoint: where the run stands and what it was built with (plain values only)"""
+        return {"steps_done": int(self.steps_done), "seed": self.seed, "dropout_seed": self.dropout_seed,
+                "rng_seed": self.rng_seed, "fanouts": list(self.fanouts), "batch": int(self.B), "streams": int(self.S),
+                "replace": self.replace, "world": int(self.world), "feature_dtype": self.feature_dtype,
+                "dropout": self.dropout, "feat_dropout": self.feat_dropout, "attn_dropout": self.attn_dropout,
+                "edge_weighted": self.edge_weighted}
+
+    def _checkpoint_peers(self):
+        """(whether this process writes the file, the torch.distributed module to meet the others at, or None)"""
+        return self.rank == 0, (self.dist if self.world > 1 else None)
+
+    def save_checkpoint(self, path, extra=None):
+        """Write the model, the optimizer state and the run's position to `path` (cslicer.checkpoint.write: one file,
+        atomically) after every step enqueued so far has finished.  extra: a dict of plain values kept in the file.  With
+        more than one rank, rank 0 writes -- the weights are replicated -- and every rank returns after a barrier."""
+        from . import checkpoint
+        torch.cuda.synchronize()
+        writer, dist = self._checkpoint_peers()
+        try:
+            if writer:
+                checkpoint.write(path, self.model, optimizer=self.opt, trainer=self.checkpoint_fields(), extra=extra,
+                                 multilabel=self.multilabel)
+        finally:
+            if dist is not None:
+                dist.barrier()
+
+    def load_checkpoint(self, path, optimizer=True):
+        """Load the file save_checkpoint wrote; every rank reads it.  Its `model` block must be this trainer's architecture
+        (ValueError naming the first differing field).  The parameters are filled in place (model.load_state_dict: the native
+        steps and the optimizer alias their storage).  optimizer=True: the moments, opt.t, opt.skipped and `steps_done` --
+        which keys the dropout masks and the learning-rate schedule -- are restored too, every one bitwise; the
+        hyperparameters stay this trainer's.  optimizer=False: the weights only (fine-tuning, inference).  The sampler is
+        not in the file: call set_nodes / skip for what the saved run had trained.
+        Returns the file's (`trainer`, `extra`) dicts."""
+        from . import checkpoint
+        ck = checkpoint.read(path)
+        checkpoint.check_model(ck["model"], checkpoint.model_block(self.model, self.multilabel))
+        if optimizer and (ck["optimizer"] is None or ck["trainer"] is None):
+            raise ValueError("checkpoint: %s holds a bare model, no optimizer state (load it with optimizer=False)" % path)
+        if self._ahead is not None:
+            raise RuntimeError("load_checkpoint(): run(then=...) has a round pending; the announced run() must follow")
+        if optimizer:
+            self.opt.check_state_dict(ck["optimizer"])       # (a refused load changes nothing)
+        torch.cuda.synchronize()
+        try:
+            self.model.load_state_dict(ck["state"])
+        except RuntimeError as ex:
+            raise ValueError("checkpoint: the stored tensors are not this model's: %s" % str(ex).split("\n")[0])
+        if optimizer:
+            self.opt.load_state_dict(ck["optimizer"])
+            self.steps_done = int(ck["trainer"]["steps_done"])
+        torch.cuda.synchronize()
+        return ck["trainer"], ck["extra"]
+
     def close(self):
         from . import infer
         infer.release(self.eng.indptr, self.eng.indices)   # the graph evaluation kept on the device, if any
@@ -821,6 +916,14 @@ class DataParallelTrainer(Trainer):
 
     def _loss_den(self, stream, slot, n_seeds):
         return self._den[(stream, slot)]
+
+    def _checkpoint_peers(self):
+        # replicas: the first one writes (its rng_seed is the one recorded: DESIGN 8)
+        return self.dp_rank == 0, (self.dp_dist if self.dp_world > 1 else None)
+
+    def checkpoint_fields(self):
+        # the job's values, not one replica's: the whole minibatch and the number of replicas
+        return dict(super().checkpoint_fields(), batch=self.global_B, world=self.dp_world)
 
 
 def balanced_class_weight(labels, n_classes):
@@ -986,6 +1089,13 @@ def _parser():
                     help="(extra) per-class weights of the softmax cross-entropy (`Trainer(class_weight=...)`): `balanced` = "
                          "n / (n_classes * count_c) over the training nodes' labels, or a text file of n_classes numbers, "
                          "one per line")
+    ap.add_argument("--save", type=str, default=None, metavar="FILE",
+                    help="(extra) write a checkpoint (`Trainer.save_checkpoint`: model, optimizer state, position) to FILE "
+                         "after every --save-every-th epoch and after the last one")
+    ap.add_argument("--save-every", type=int, default=1, metavar="N", help="(extra) --save after every N-th epoch (default 1)")
+    ap.add_argument("--resume", type=str, default=None, metavar="FILE",
+                    help="(extra) continue the run that wrote FILE with --save: same command line, same --num-epochs; the "
+                         "epochs it had finished are replayed through the slicer only (`Trainer.skip`), not trained")
     return ap
 
 
@@ -1090,7 +1200,21 @@ def main(argv=None):
     of the training nodes (train.balanced_class_weight; a class without a node gets 0), FILE = n_classes numbers, one per
     line.  The training loss is the weighted, smoothed sum over a minibatch's seeds divided by their count; `Eval Acc`'s
     loss stays the plain mean cross-entropy.  Neither combines with --multilabel (the sigmoid-BCE loss has no weights yet).
+    --save FILE [--save-every N] (extra): `Trainer.save_checkpoint(FILE, extra={"epoch": epochs done})` after every N-th
+    epoch (default 1) and after the last one: the model, the optimizer state and the run's position in one file, written
+    atomically by rank 0 (cslicer.checkpoint).  `python -m cslicer.predict --model FILE` applies the model.
+    --resume FILE (extra): continue the run that wrote FILE.  The file is checked before the graph is loaded.  The weights,
+    the moments and the step count come from the file; the sampler is brought back by replaying the finished epochs through
+    the slicer without training them (`Trainer.skip`; an epoch's node order is a function of its number), and the epoch
+    loop continues where the file ends.  Give the command line of the original run, --num-epochs included (it still means
+    the whole run, and it is what --lr-schedule spans): the continuation is then the uninterrupted run's: bit for bit on the
+    native GraphSAGE step where the new process's library GEMMs run the algorithms the old one's ran (csl_gemm_f32 picks one per
+    shape class, from the recorded plans or else by timing: DESIGN 4.12), otherwise equal up to float32 summation order.  Rank 0 prints `resumed from FILE: epoch E, S steps`, and one line for every recorded setting
+    (fan-outs, batch size, --no-replace, ...) the command line changes: such a run continues, but as another run.  A file that already
+    holds --num-epochs epochs is reported (`nothing is left to train`) and not replayed.
 
+        python -m cslicer.train --graph products-like --num-epochs 20 --eval-split holdout --save run.ckpt
+        python -m cslicer.train --graph products-like --num-epochs 20 --eval-split holdout --save run.ckpt --resume run.ckpt
         python -m cslicer.train --graph products-like --class-weight balanced --label-smoothing 0.1 --eval-split holdout --max-steps 50
         python -m cslicer.train --graph products-like --multilabel --eval-split holdout --max-steps 50
         python -m cslicer.train --graph products-like --edge-weight inv-degree --eval-split holdout --max-steps 50
@@ -1110,6 +1234,19 @@ def main(argv=None):
         lim = _abi.noreplace_max_fanout()
         if any(int(x) > lim for x in a.fan_out.split(",")):
             raise SystemExit("--no-replace: --fan-out %s exceeds the limit of %d neighbours per row" % (a.fan_out, lim))
+    if a.save is not None and (a.save_every < 1 or not os.path.isdir(os.path.dirname(os.path.abspath(a.save)))):
+        raise SystemExit("--save %s: --save-every must be >= 1 and the file's directory must exist" % a.save)
+    epochs_done = 0
+    if a.resume is not None:     # (before the graph is loaded)
+        from . import checkpoint
+        if not os.path.isfile(a.resume):
+            raise SystemExit("--resume %s: no such file" % a.resume)
+        try:
+            epochs_done = checkpoint.read(a.resume)["extra"].get("epoch")
+        except ValueError as ex:
+            raise SystemExit("--resume %s: %s" % (a.resume, ex))
+        if not isinstance(epochs_done, int) or isinstance(epochs_done, bool) or epochs_done < 0:
+            raise SystemExit("--resume %s: the file records no finished epochs (it was not written by --save)" % a.resume)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -1188,16 +1325,47 @@ def main(argv=None):
     if rank == 0 and fdtype != "float32":
         print("feature table: %s, %d bytes on this rank" % (fdtype, tr.feat.numel() * tr.feat.element_size()))
     n = indptr.shape[0] - 1
-    for epoch in range(a.num_epochs):
+
+    def start_epoch(epoch):
+        """the epoch's node order (a pure function of its number) into the trainer; returns its minibatches"""
         if train_nodes is None:
             tr.set_nodes(np.random.default_rng(epoch).permutation(n))
         else:
             tr.set_nodes(train_nodes[np.random.default_rng(epoch).permutation(train_nodes.shape[0])])
-        steps = tr.n_batches if a.max_steps <= 0 else min(a.max_steps, tr.n_batches)
+        return tr.n_batches if a.max_steps <= 0 else min(a.max_steps, tr.n_batches)
+
+    if a.resume is not None:
+        try:
+            was, _ = tr.load_checkpoint(a.resume)
+        except ValueError as ex:
+            raise SystemExit("--resume %s: %s" % (a.resume, ex))
+        # the sampler back to its position: the finished epochs through the slicer, nothing trained (DESIGN 4.12)
+        left = epochs_done < a.num_epochs        # (nothing to continue: nothing to replay)
+        replayed = 0
+        for e in range(epochs_done if left else 0):
+            steps = start_epoch(e)
+            tr.skip(steps)
+            replayed += steps
+        if rank == 0:
+            print("resumed from %s: epoch %d, %d steps" % (a.resume, epochs_done, tr.steps_done))
+            now = tr.checkpoint_fields()
+            odd = ["%s was %r, is %r" % (k, was[k], now[k]) for k in sorted(now)
+                   if k not in ("steps_done", "world") and k in was and was[k] != now[k]]
+            if left and replayed != tr.steps_done:
+                odd.append("the file holds %d steps, %d epochs of this command line are %d" % (tr.steps_done, epochs_done, replayed))
+            for line in odd:
+                print("resume: %s: the continuation will not be the uninterrupted run's" % line)
+            if not left:
+                print("resume: the file holds %d epochs and --num-epochs is %d: nothing is left to train"
+                      % (epochs_done, a.num_epochs))
+    for epoch in range(epochs_done, a.num_epochs):
+        steps = start_epoch(epoch)
         t0 = time.time()
         losses = tr.run(steps)
         if rank == 0:
             print("epoch %d: %d minibatches in %.2f s, loss %.4f -> %.4f" % (epoch, steps, time.time() - t0, losses[0], losses[-1]))
+        if a.save is not None and ((epoch + 1) % a.save_every == 0 or epoch + 1 == a.num_epochs):
+            tr.save_checkpoint(a.save, extra={"epoch": epoch + 1})
         if eval_nodes is not None and ((epoch + 1) % max(a.eval_every, 1) == 0 or epoch + 1 == a.num_epochs):
             t0 = time.time()
             ev = tr.evaluate(eval_nodes)
