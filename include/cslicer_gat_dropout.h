@@ -1,4 +1,4 @@
-/* cslicer_gat_dropout.h -- dropout for the attention model (csrc/gat_dropout.hip): feature dropout on the
+/* cslicer_gat_dropout.h -- dropout for the attention model (csrc/aggregate.hip): feature dropout on the
  * output of every attention layer but the last, and attention dropout on the normalised coefficients of the edge softmax
  * (GAT as published drops both).  Two independent probabilities p_f and p_a, one seed, the step's counter; both masks are
  * pure functions of a counter exactly as in cslicer_dropout.h: Philox4x32-10, key = (seed mod 2^32, seed >> 32),

@@ -19,6 +19,7 @@
 #include "adam_dev.h"
 #include "cslicer_aggr.h"
 #include "cslicer_feat16.h"
+#include "cslicer_gat_dropout.h"
 #include "cslicer_hip.h"
 #include "dev_common.h"
 #include "feat_elem.h"
@@ -225,25 +226,32 @@ __global__ __launch_bounds__(BLK) void k_div_rows(float* __restrict__ x, long lo
 // (m, s, n) are the partial softmax state the owner of r merges across parts (log-sum-exp), then out = n / s.
 // One wave per row, a lane owns 4 consecutive feature columns (so D % 4 == 0, D <= 256);
 // rows have <= fanout edges, so both passes stay in cache.  HBM-bound gather of z rows: no MFMA.
+// Every kernel of the aggregation and of its epilogue is a template over its dropout policy DR (gat_dev.h): with NoDrop
+// the statements under `if constexpr (DR::on)` are gone and kp below is p.
 __device__ __forceinline__ float leaky(float x, float slope) { return x > 0.f ? x : slope * x; }
 
+template <class DR>
 __global__ __launch_bounds__(BLK) void k_gat_fwd(const int* __restrict__ indptr, const int* __restrict__ indices,
                                                  long long n_rows, const float* __restrict__ el,
                                                  const float* __restrict__ er, const float* __restrict__ z, int H, int D,
                                                  float slope, float* __restrict__ m_out, float* __restrict__ s_out,
-                                                 float* __restrict__ n_out) {
+                                                 float* __restrict__ n_out, DR d) {
   const int lane = threadIdx.x & 63;
   const long long r = (long long)blockIdx.x * (BLK / 64) + (threadIdx.x >> 6);
   if (r >= n_rows) return;
   const int C = H * D;
   const int lpc = (64 / (D / 4)) * (D / 4);  // lanes per chunk: whole heads only
   const int e0 = indptr[r], e1 = indptr[r + 1];
+  [[maybe_unused]] uint32_t vid = 0;   // the destination's node id
+  if constexpr (DR::on) vid = (uint32_t)d.dst_ids[r];
   constexpr int EK = 16;
   if (e1 - e0 <= EK && C <= lpc * 4) {
     // The common case (a sampled row: <= fanout edges; one chunk of columns): every load of the row is requested before
     // the first is used -- lane j takes edge j's source id, the ids are handed out with shuffles, then the EK logits and
     // the EK z rows are in flight together.  (Edge by edge it was two dependent round trips per edge and pass: 17-21 us
-    // for the 1 k- and 8 k-row layers of config 5's model whatever their size.)
+    // for the 1 k- and 8 k-row layers of config 5's model whatever their size.)  Dropped, lane j also fetches the NODE id
+    // of edge j's source, which travels with the same shuffle; kappa is formed inside the accumulate loop, edge by edge:
+    // the 16 float4 and 16 logits leave no room for 16 more live values.
     const int deg = e1 - e0;
     const int c = lane * 4;
     const bool on = lane < lpc && c < C;
@@ -259,6 +267,8 @@ __global__ __launch_bounds__(BLK) void k_gat_fwd(const int* __restrict__ indptr,
       return;
     }
     const int src_l = indices[e0 + (lane < deg ? lane : 0)];
+    [[maybe_unused]] int uid_l = 0;
+    if constexpr (DR::on) uid_l = d.src_ids[src_l];
     const float erv = er[r * H + h];
     float elv[EK];
     float4 zv[EK];
@@ -279,7 +289,9 @@ __global__ __launch_bounds__(BLK) void k_gat_fwd(const int* __restrict__ indptr,
       if (e < deg) {
         const float p = expf(leaky(elv[e] + erv, slope) - m);
         s += p;
-        acc.x += p * zv[e].x, acc.y += p * zv[e].y, acc.z += p * zv[e].z, acc.w += p * zv[e].w;
+        float kp = p;
+        if constexpr (DR::on) kp = kappa((uint32_t)__shfl(uid_l, e), vid, h, d) * p;
+        acc.x += kp * zv[e].x, acc.y += kp * zv[e].y, acc.z += kp * zv[e].z, acc.w += kp * zv[e].w;
       }
     }
     if (on) {
@@ -306,10 +318,12 @@ __global__ __launch_bounds__(BLK) void k_gat_fwd(const int* __restrict__ indptr,
       s += p;
       if (on) {
         const float4 zv = *reinterpret_cast<const float4*>(z + src * C + c);
-        acc.x += p * zv.x;
-        acc.y += p * zv.y;
-        acc.z += p * zv.z;
-        acc.w += p * zv.w;
+        float kp = p;
+        if constexpr (DR::on) kp = kappa((uint32_t)d.src_ids[src], vid, h, d) * p;
+        acc.x += kp * zv.x;
+        acc.y += kp * zv.y;
+        acc.z += kp * zv.z;
+        acc.w += kp * zv.w;
       }
     }
     if (on) {
@@ -323,13 +337,15 @@ __global__ __launch_bounds__(BLK) void k_gat_fwd(const int* __restrict__ indptr,
 }
 
 // Backward of (s, n) w.r.t. el, er, z (m is a stabiliser: the merged result does not depend on it).
-// g_el and g_z are accumulated with fp32 atomics (caller zeroes them), g_er is written.
+// g_el and g_z are accumulated with fp32 atomics (caller zeroes them), g_er is written.  Dropped: g_z[u] += kappa p g_n
+// and g_logit = (g_s + kappa <g_n, z_u>) p lrelu'.
+template <class DR>
 __global__ __launch_bounds__(BLK) void k_gat_bwd(const int* __restrict__ indptr, const int* __restrict__ indices,
                                                  long long n_rows, const float* __restrict__ el,
                                                  const float* __restrict__ er, const float* __restrict__ z, int H, int D,
                                                  float slope, const float* __restrict__ m_in,
                                                  const float* __restrict__ g_s, const float* __restrict__ g_n,
-                                                 float* g_el, float* __restrict__ g_er, float* g_z) {
+                                                 float* g_el, float* __restrict__ g_er, float* g_z, DR d) {
   const int lane = threadIdx.x & 63;
   const long long r = (long long)blockIdx.x * (BLK / 64) + (threadIdx.x >> 6);
   if (r >= n_rows) return;
@@ -338,6 +354,8 @@ __global__ __launch_bounds__(BLK) void k_gat_bwd(const int* __restrict__ indptr,
   const int lpc = (64 / gsz) * gsz;   // lanes per chunk: whole heads only
   const int gl = lane % gsz;          // position inside the head's lane group
   const int e0 = indptr[r], e1 = indptr[r + 1];
+  [[maybe_unused]] uint32_t vid = 0;
+  if constexpr (DR::on) vid = (uint32_t)d.dst_ids[r];
   for (int c0 = 0; c0 < C; c0 += lpc * 4) {
     const int c = c0 + lane * 4;
     const bool on = lane < lpc && c < C;
@@ -348,7 +366,7 @@ __global__ __launch_bounds__(BLK) void k_gat_bwd(const int* __restrict__ indptr,
     // instruction adds 64 CONSECUTIVE floats (the shape the memory-side float atomics run fastest at; the float4
     // layout above made each instruction touch every fourth float: 1.9 ms of the 7 ms GAT step).  The row's
     // gradient is loaded once more in that layout; the edge's weight p of a column's head comes from a lane of
-    // the float4 layout that owns that head (all lanes of a head hold the same p).
+    // the float4 layout that owns that head (all lanes of a head hold the same p; dropped, the same kappa p).
     const int chunk_end = c0 + lpc * 4 < C ? c0 + lpc * 4 : C;
     float gn2[4];
     int p_lane[4];
@@ -363,6 +381,8 @@ __global__ __launch_bounds__(BLK) void k_gat_bwd(const int* __restrict__ indptr,
       const long long src = indices[e];
       const float raw = el[src * H + h] + erv;
       const float p = expf(leaky(raw, slope) - mh);
+      [[maybe_unused]] float kap = 1.f;
+      if constexpr (DR::on) kap = kappa((uint32_t)d.src_ids[src], vid, h, d);
       float dot = 0.f;
       if (on) {
         const float4 zv = *reinterpret_cast<const float4*>(z + src * C + c);
@@ -374,10 +394,12 @@ __global__ __launch_bounds__(BLK) void k_gat_bwd(const int* __restrict__ indptr,
         if (gl + o < gsz) dot += t;
       }
       dot = __shfl(dot, lane - gl);
+      float kp = p;
+      if constexpr (DR::on) dot = kap * dot, kp = kap * p;
       const float gsc = (gs + dot) * p * (raw > 0.f ? 1.f : slope);
 #pragma unroll
       for (int k = 0; k < 4; k++) {
-        const float pk = __shfl(p, p_lane[k]);
+        const float pk = __shfl(kp, p_lane[k]);
         const int col = c0 + lane + 64 * k;
         if (col < chunk_end) atomicAdd(g_z + src * C + col, pk * gn2[k]);
       }
@@ -393,18 +415,23 @@ __global__ __launch_bounds__(BLK) void k_gat_bwd(const int* __restrict__ indptr,
 // The same backward BY SOURCE (the slicer's CSL_T_INDPTR / CSL_T_INDICES, CSL_FLAG_TRANSPOSE_ALL): one wave per source
 // row u walks the destinations of its edges, so g_z[u, :] and g_el[u, :] are accumulated in registers and WRITTEN once --
 // no zero fill of the 0.7 GB gradient of z, no fp32 atomics on it; what is left to atomics is g_er (H floats per edge
-// instead of H * D; the caller zeroes it).  Rows [n_src, n_pad) of g_z are zeroed (GEMM operand padding).
+// instead of H * D; the caller zeroes it).  Rows [n_src, n_pad) of g_z are zeroed (GEMM operand padding).  Dropped, the
+// source's node id is read once per row.
+template <class DR>
 __global__ __launch_bounds__(BLK) void k_gat_bwd_t(const int* __restrict__ tptr, const int* __restrict__ trow,
                                                    long long n_src, long long n_pad, const float* __restrict__ el,
                                                    const float* __restrict__ er, const float* __restrict__ z, int H, int D,
                                                    float slope, const float* __restrict__ m_in,
                                                    const float* __restrict__ g_s, const float* __restrict__ g_n,
-                                                   float* __restrict__ g_el, float* g_er, float* __restrict__ g_z) {
+                                                   float* __restrict__ g_el, float* g_er, float* __restrict__ g_z,
+                                                   DR d) {
   const int lane = threadIdx.x & 63;
   const long long u = (long long)blockIdx.x * (BLK / 64) + (threadIdx.x >> 6);
   if (u >= n_pad) return;
   const int C = H * D, gsz = D / 4, lpc = (64 / gsz) * gsz, gl = lane % gsz;
   const int j0 = u < n_src ? tptr[u] : 0, j1 = u < n_src ? tptr[u + 1] : 0;
+  [[maybe_unused]] uint32_t uid = 0;
+  if constexpr (DR::on) uid = u < n_src ? (uint32_t)d.src_ids[u] : 0u;
   for (int c0 = 0; c0 < C; c0 += lpc * 4) {
     const int c = c0 + lane * 4;
     const bool on = lane < lpc && c < C;
@@ -420,6 +447,8 @@ __global__ __launch_bounds__(BLK) void k_gat_bwd_t(const int* __restrict__ tptr,
       if (r < 0) continue;    // the node's self entry: attention runs over the sampled edges only
       const float raw = elu + er[(long long)r * H + h];
       const float p = expf(leaky(raw, slope) - m_in[(long long)r * H + h]);
+      [[maybe_unused]] float kap = 1.f;
+      if constexpr (DR::on) kap = kappa(uid, (uint32_t)d.dst_ids[r], h, d);
       float dot = 0.f;
       float4 gn = make_float4(0.f, 0.f, 0.f, 0.f);
       if (on) {
@@ -431,8 +460,10 @@ __global__ __launch_bounds__(BLK) void k_gat_bwd_t(const int* __restrict__ tptr,
         if (gl + o < gsz) dot += t;
       }
       dot = __shfl(dot, lane - gl);
+      float kp = p;
+      if constexpr (DR::on) dot = kap * dot, kp = kap * p;
       const float gsc = (g_s[(long long)r * H + h] + dot) * p * (raw > 0.f ? 1.f : slope);
-      acc.x += p * gn.x, acc.y += p * gn.y, acc.z += p * gn.z, acc.w += p * gn.w;
+      acc.x += kp * gn.x, acc.y += kp * gn.y, acc.z += kp * gn.z, acc.w += kp * gn.w;
       if (on && c % D == 0) {
         gel += gsc;
         atomicAdd(g_er + (long long)r * H + h, gsc);
@@ -451,14 +482,16 @@ __global__ __launch_bounds__(BLK) void k_gat_bwd_t(const int* __restrict__ tptr,
 // its own (k_gat_logits_bwd re-read z and read-modify-wrote all of g_z: 112 us per layer in the config-5 step).  The er
 // half depends on g_er of the DESTINATIONS, complete only when every source row has been walked: it runs afterwards over
 // the destination rows alone (k_gat_logits_bwd_dst: n_out rows, a tenth of the sources).  A workgroup takes
-// rows_per_block source rows, a wave every fourth of them; part_l[block][C] = the block's share of g_attn_l.
+// rows_per_block source rows, a wave every fourth of them; part_l[block][C] = the block's share of g_attn_l.  The second
+// stage knows nothing of dropout (g_er is complete when it runs).
+template <class DR>
 __global__ __launch_bounds__(BLK) void k_gat_bwd_t2(const int* __restrict__ tptr, const int* __restrict__ trow,
                                                     long long n_src, long long n_pad, const float* __restrict__ el,
                                                     const float* __restrict__ er, const float* __restrict__ z, int H, int D,
                                                     float slope, const float* __restrict__ m_in,
                                                     const float* __restrict__ g_s, const float* __restrict__ g_n,
                                                     const float* __restrict__ al, float* g_er, float* __restrict__ g_z,
-                                                    float* __restrict__ part_l, long long rows_per_block) {
+                                                    float* __restrict__ part_l, long long rows_per_block, DR d) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int C = H * D, gsz = D / 4, lpc = (64 / gsz) * gsz, gl = lane % gsz;
   const long long r0 = (long long)blockIdx.x * rows_per_block;
@@ -472,6 +505,8 @@ __global__ __launch_bounds__(BLK) void k_gat_bwd_t2(const int* __restrict__ tptr
     if (on) a4 = *reinterpret_cast<const float4*>(al + c);
     for (long long u = r0 + w; u < r_end; u += BLK / 64) {
       const int j0 = u < n_src ? tptr[u] : 0, j1 = u < n_src ? tptr[u + 1] : 0;
+      [[maybe_unused]] uint32_t uid = 0;
+      if constexpr (DR::on) uid = u < n_src ? (uint32_t)d.src_ids[u] : 0u;
       float4 acc = make_float4(0.f, 0.f, 0.f, 0.f), zv = acc;
       float elu = 0.f, gel = 0.f;
       if (u < n_src) {
@@ -483,6 +518,8 @@ __global__ __launch_bounds__(BLK) void k_gat_bwd_t2(const int* __restrict__ tptr
         if (r < 0) continue;    // the node's self entry: attention runs over the sampled edges only
         const float raw = elu + er[(long long)r * H + h];
         const float p = expf(leaky(raw, slope) - m_in[(long long)r * H + h]);
+        [[maybe_unused]] float kap = 1.f;
+        if constexpr (DR::on) kap = kappa(uid, (uint32_t)d.dst_ids[r], h, d);
         float dot = 0.f;
         float4 gn = make_float4(0.f, 0.f, 0.f, 0.f);
         if (on) {
@@ -494,8 +531,10 @@ __global__ __launch_bounds__(BLK) void k_gat_bwd_t2(const int* __restrict__ tptr
           if (gl + o < gsz) dot += t;
         }
         dot = __shfl(dot, lane - gl);
+        float kp = p;
+        if constexpr (DR::on) dot = kap * dot, kp = kap * p;
         const float gsc = (g_s[(long long)r * H + h] + dot) * p * (raw > 0.f ? 1.f : slope);
-        acc.x += p * gn.x, acc.y += p * gn.y, acc.z += p * gn.z, acc.w += p * gn.w;
+        acc.x += kp * gn.x, acc.y += kp * gn.y, acc.z += kp * gn.z, acc.w += kp * gn.w;
         gel += gsc;   // (every lane of the head's group carries the same value)
         if (on && c % D == 0) atomicAdd(g_er + (long long)r * H + h, gsc);
       }
@@ -1195,14 +1234,18 @@ __global__ __launch_bounds__(BLK) void k_gat_logits_bwd(const float* __restrict_
 // ---- GAT layer epilogue: out = act(n / s + bias) from the aggregation's (s, n) (DistGATConv: out[v] = sum_u alpha z[u]
 // + bias; ELU between layers), and its backward -- with torch ops this was a division, an add, an ELU and their
 // autograd nodes with broadcasts and reductions (a dozen launches per layer).  One wave per row, a lane owns 4
-// consecutive columns, heads are groups of D / 4 lanes (the layout of k_gat_logits_*).
+// consecutive columns, heads are groups of D / 4 lanes (the layout of k_gat_logits_*).  With feature dropout (FeatDrop)
+// out is kept for ELU' and y = the dropped out leaves in the same pass: one more store, no more load.
+template <class DR>
 __global__ __launch_bounds__(BLK) void k_gat_finish_fwd(const float* __restrict__ nsum, const float* __restrict__ ssum,
                                                         const float* __restrict__ bias, long long n, int H, int D,
-                                                        int elu, float* __restrict__ out) {
+                                                        int elu, float* __restrict__ out, float* __restrict__ y, DR d) {
   const int lane = threadIdx.x & 63;
   const long long r = (long long)blockIdx.x * (BLK / 64) + (threadIdx.x >> 6);
   if (r >= n) return;
   const int C = H * D, gsz = D / 4, lpc = (64 / gsz) * gsz;
+  [[maybe_unused]] uint32_t vid = 0;
+  if constexpr (DR::on) vid = (uint32_t)d.ids[r];
   for (int c0 = 0; c0 < C; c0 += lpc * 4) {
     const int c = c0 + lane * 4;
     if (lane >= lpc || c >= C) continue;
@@ -1212,15 +1255,18 @@ __global__ __launch_bounds__(BLK) void k_gat_finish_fwd(const float* __restrict_
     v.x = v.x * inv + b.x, v.y = v.y * inv + b.y, v.z = v.z * inv + b.z, v.w = v.w * inv + b.w;
     if (elu) v.x = v.x > 0.f ? v.x : expm1f(v.x), v.y = v.y > 0.f ? v.y : expm1f(v.y), v.z = v.z > 0.f ? v.z : expm1f(v.z), v.w = v.w > 0.f ? v.w : expm1f(v.w);
     *reinterpret_cast<float4*>(out + r * C + c) = v;
+    if constexpr (DR::on) *reinterpret_cast<float4*>(y + r * C + c) = feat_mask(v, c, vid, d);
   }
 }
 // backward: p = g .* act'(out) (ELU: out > 0 ? 1 : out + 1);  g_n = p / s;  g_s[r, h] = -sum_d g_n n / s;
-// per-block column sums of p (the bias gradient's first stage) to part[block][C]
+// per-block column sums of p (the bias gradient's first stage) to part[block][C].  With feature dropout the mask is
+// applied to g as it is loaded.
+template <class DR>
 __global__ __launch_bounds__(BLK) void k_gat_finish_bwd(const float* __restrict__ g, long long ldg,
                                                         const float* __restrict__ out, const float* __restrict__ nsum,
                                                         const float* __restrict__ ssum, long long n, int H, int D, int elu,
                                                         float* __restrict__ g_n, float* __restrict__ g_s,
-                                                        float* __restrict__ part, long long rows_per_block) {
+                                                        float* __restrict__ part, long long rows_per_block, DR d) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int C = H * D, gsz = D / 4, lpc = (64 / gsz) * gsz, gl = lane % gsz;
   const long long r0 = (long long)blockIdx.x * rows_per_block;
@@ -1235,6 +1281,7 @@ __global__ __launch_bounds__(BLK) void k_gat_finish_bwd(const float* __restrict_
       float dot = 0.f;
       if (on) {
         float4 p = *reinterpret_cast<const float4*>(g + r * ldg + c);
+        if constexpr (DR::on) p = feat_mask(p, c, (uint32_t)d.ids[r], d);
         if (elu) {
           const float4 o = *reinterpret_cast<const float4*>(out + r * C + c);
           p.x *= o.x > 0.f ? 1.f : o.x + 1.f, p.y *= o.y > 0.f ? 1.f : o.y + 1.f;
@@ -1342,6 +1389,152 @@ int rd::sage_cat(const int32_t* indptr, const int32_t* indices, const int32_t* s
   return done();
 }
 
+// ---- the attention aggregation and its epilogue (cslicer_aggr.h, cslicer_gat_dropout.h): one host path per entry point
+// and its dropped twin.  The body checks, sizes the grid and launches its kernel with the policy it is given: NoDrop{} from
+// the plain entry point, the packed AttnDrop / FeatDrop from the dropped one, whose wrapper first refuses what its packer
+// and drop_shape_ok refuse.
+namespace {
+
+// (a head is at most one wave of float4 lanes)
+bool gat_shape_ok(int32_t H, int32_t D) { return H >= 1 && D >= 4 && D % 4 == 0 && D <= 256; }
+// (the dropped kernels' head quad shares the counter's third word with the layer)
+bool drop_shape_ok(int32_t H, int32_t D) { return gat_shape_ok(H, D) && H <= (1 << 24); }
+
+int gat_args_ok(const void* a, const void* b, const void* c, int32_t H, int32_t D) {
+  return gat_shape_ok(H, D) && aligned16(a) && aligned16(b) && aligned16(c);
+}
+
+long long gat_t_rows(long long n) {   // source rows per workgroup of k_gat_bwd_t2: at most ~2048 workgroups
+  long long r = 16;                        // (each leaves a row of partial sums for the second stage to read)
+  // (CSL_GAT_T_BLOCKS: measurement knob; 1024 / 2048 / 4096 workgroups: 32.7 / 26.5 / 26.9 us for the 62 k-row layer, the
+  // second stage 9.5 / 11.2 / 14.6)
+  static const long long cap = getenv("CSL_GAT_T_BLOCKS") ? atoll(getenv("CSL_GAT_T_BLOCKS")) : 2048;
+  while ((n + r - 1) / r > cap) r *= 2;
+  return r;
+}
+
+
+// rows per workgroup of k_gat_finish_bwd: a wave walks its rows one after the other (a dependent shuffle chain per row), so a
+// small layer wants MANY small workgroups: with rb_rows' 128 the 8 k-row and 1 k-row layers of config 5's model ran on 64
+// and 8 workgroups, 31-41 us each whatever their size (profiles/r3_gat_in)
+long long gat_finish_rows(long long n) {
+  long long r = (n + 1023) / 1024;
+  r = (r + 3) / 4 * 4;
+  return r < 4 ? 4 : (r > 128 ? rb_rows(n) : r);
+}
+
+
+template <class DR>
+int gat_fwd(const int32_t* indptr, const int32_t* indices, int64_t n_rows, const float* el, const float* er, const float* z,
+            int32_t H, int32_t D, float slope, float* m_out, float* s_out, float* n_out, DR d, void* stream) {
+  if (n_rows == 0) return CSL_OK;
+  if (n_rows < 0 || !indptr || !er || !m_out || !s_out || !n_out || !d.ids_ok() || !gat_args_ok(z, n_out, n_out, H, D))
+    return CSL_E_INVALID;
+  hipLaunchKernelGGL(k_gat_fwd<DR>, row_grid<64>(n_rows), dim3(BLK), 0, (hipStream_t)stream, indptr, indices,
+                     (long long)n_rows, el, er, z, (int)H, (int)D, slope, m_out, s_out, n_out, d);
+  return done();
+}
+
+template <class DR>
+int gat_bwd(const int32_t* indptr, const int32_t* indices, int64_t n_rows, const float* el, const float* er, const float* z,
+            int32_t H, int32_t D, float slope, const float* m_in, const float* g_s, const float* g_n, float* g_el,
+            float* g_er, float* g_z, DR d, void* stream) {
+  if (n_rows == 0) return CSL_OK;
+  if (n_rows < 0 || !indptr || !er || !m_in || !g_s || !g_n || !g_er || !d.ids_ok() || !gat_args_ok(z, g_n, g_z, H, D))
+    return CSL_E_INVALID;
+  hipLaunchKernelGGL(k_gat_bwd<DR>, row_grid<64>(n_rows), dim3(BLK), 0, (hipStream_t)stream, indptr, indices,
+                     (long long)n_rows, el, er, z, (int)H, (int)D, slope, m_in, g_s, g_n, g_el, g_er, g_z, d);
+  return done();
+}
+
+template <class DR>
+int gat_bwd_t(const int32_t* t_indptr, const int32_t* t_indices, int64_t n_src, int64_t n_pad, const float* el,
+              const float* er, const float* z, int32_t H, int32_t D, float slope, const float* m_in, const float* g_s,
+              const float* g_n, float* g_el, float* g_er, float* g_z, DR d, void* stream) {
+  if (n_src < 0 || n_pad < n_src || !gat_shape_ok(H, D)) return CSL_E_INVALID;
+  if (n_pad == 0) return CSL_OK;
+  if (!g_z || !aligned16(g_z) || (n_src > 0 && (!t_indptr || !el || !z || !g_el || !aligned16(z)))) return CSL_E_INVALID;
+  if (n_src > 0 && (!er || !m_in || !g_s || !g_n || !g_er || !aligned16(g_n) || !d.ids_ok())) return CSL_E_INVALID;
+  hipLaunchKernelGGL(k_gat_bwd_t<DR>, row_grid<64>(n_pad), dim3(BLK), 0, (hipStream_t)stream, t_indptr, t_indices,
+                     (long long)n_src, (long long)n_pad, el, er, z, (int)H, (int)D, slope, m_in, g_s, g_n, g_el, g_er, g_z, d);
+  return done();
+}
+
+// Every refusal comes before the first HIP call, the second stage's included.  (The dropped form also refuses a second
+// stage without the buffers that only its first stage's checks name: the plain one never did, and keeps its answer.)
+template <class DR>
+int gat_bwd_t_fused(const int32_t* t_indptr, const int32_t* t_indices, int64_t n_src, int64_t n_pad, const float* el,
+                    const float* er_out, const float* z, int32_t H, int32_t D, float slope, const float* m_in,
+                    const float* g_s, const float* g_n, const float* attn_l, const float* attn_r,
+                    const int32_t* self_ids_in, int64_t n_out, float* g_er_out, float* g_z, float* g_attn_l,
+                    float* g_attn_r, float* scratch, DR d, void* stream) {
+  if (n_src < 0 || n_pad < n_src || n_out < 0 || !gat_shape_ok(H, D) || !g_attn_l || !g_attn_r) return CSL_E_INVALID;
+  hipStream_t st = (hipStream_t)stream;
+  const int C = H * D;
+  const long long r1 = gat_t_rows(n_pad), r2 = gat_t_rows(n_out);
+  const long long b1 = (n_pad + r1 - 1) / r1, b2 = (n_out + r2 - 1) / r2;
+  if (b1 > 0) {
+    if (!g_z || !aligned16(g_z) || !scratch || !aligned16(scratch) || !attn_l || !aligned16(attn_l)) return CSL_E_INVALID;
+    if (n_src > 0 && (!t_indptr || !el || !z || !aligned16(z) || !er_out || !m_in || !g_s || !g_n || !aligned16(g_n) ||
+                      !g_er_out || !d.ids_ok()))
+      return CSL_E_INVALID;
+  }
+  if (b2 > 0) {
+    if (!attn_r || !aligned16(attn_r) || !self_ids_in) return CSL_E_INVALID;
+    if (DR::on && (!scratch || !g_er_out || !z || !g_z)) return CSL_E_INVALID;
+  }
+  if (b1 > 0) {
+    if (n_out > 0 && hipMemsetAsync(g_er_out, 0, sizeof(float) * (size_t)n_out * H, st) != hipSuccess) return CSL_E_HIP;
+    hipLaunchKernelGGL(k_gat_bwd_t2<DR>, dim3((unsigned)b1), dim3(BLK), 0, st, t_indptr, t_indices, (long long)n_src,
+                       (long long)n_pad, el, er_out, z, (int)H, (int)D, slope, m_in, g_s, g_n, attn_l, g_er_out, g_z, scratch,
+                       r1, d);
+  }
+  if (b2 > 0)
+    hipLaunchKernelGGL(k_gat_logits_bwd_dst, dim3((unsigned)b2), dim3(BLK), 0, st, z, attn_r, self_ids_in, g_er_out,
+                       (long long)n_out, (int)H, (int)D, g_z, scratch + b1 * C, r2);
+  // both second stages in one launch
+  const float* src[2] = {scratch, scratch + b1 * C};
+  const int64_t nb[2] = {b1, b2};
+  const int32_t hh[2] = {C, C};
+  float* dst[2] = {g_attn_l, g_attn_r};
+  return csl_reduce_multi_f32(2, src, nb, hh, dst, stream);
+}
+
+// (y: the dropped output, the dropped form's alone)
+template <class DR>
+int gat_finish_fwd(const float* n_in, const float* s_in, const float* bias, int64_t n, int32_t H, int32_t D, int32_t elu,
+                   float* out, float* y, DR d, void* stream) {
+  if (n < 0 || !gat_shape_ok(H, D)) return CSL_E_INVALID;
+  if (n == 0) return CSL_OK;
+  if (!n_in || !s_in || !bias || !out || !aligned16(n_in) || !aligned16(bias) || !aligned16(out)) return CSL_E_INVALID;
+  if (DR::on && (!y || !aligned16(y) || !d.ids_ok())) return CSL_E_INVALID;
+  hipLaunchKernelGGL(k_gat_finish_fwd<DR>, row_grid<64>(n), dim3(BLK), 0, (hipStream_t)stream, n_in, s_in, bias,
+                     (long long)n, (int)H, (int)D, (int)(elu != 0), out, y, d);
+  return done();
+}
+
+template <class DR>
+int gat_finish_bwd(const float* g, int64_t ldg, const float* out, const float* n_in, const float* s_in, int64_t n,
+                   int32_t H, int32_t D, int32_t elu, float* g_n, float* g_s, float* g_bias, float* scratch, DR d,
+                   void* stream) {
+  if (n < 0 || !gat_shape_ok(H, D) || !g_bias) return CSL_E_INVALID;
+  hipStream_t st = (hipStream_t)stream;
+  const int C = H * D;
+  const long long rpb = gat_finish_rows(n);
+  const long long blocks = (n + rpb - 1) / rpb;
+  if (blocks > 0) {
+    if (!g || ldg < C || ldg % 4 != 0 || !n_in || !s_in || !g_n || !g_s || !scratch || !d.ids_ok() || (elu && !out) ||
+        !aligned16(g) || !aligned16(n_in) || !aligned16(g_n) || !aligned16(scratch) || (out && !aligned16(out)))
+      return CSL_E_INVALID;
+    hipLaunchKernelGGL(k_gat_finish_bwd<DR>, dim3((unsigned)blocks), dim3(BLK), 0, st, g, (long long)ldg, out, n_in, s_in,
+                       (long long)n, (int)H, (int)D, (int)(elu != 0), g_n, g_s, scratch, rpb, d);
+  }
+  hipLaunchKernelGGL(k_colsum_finish, dim3((unsigned)((C + 63) / 64)), dim3(BLK), 0, st, scratch, blocks, C, g_bias);
+  return done();
+}
+
+}  // namespace
+
 extern "C" {
 
 int csl_spmm_sum_map_f32(const int32_t* indptr, const int32_t* indices, const int32_t* rows, int64_t n_rows, const float* x,
@@ -1369,23 +1562,17 @@ int csl_spmm_sum_compact_f32(const int32_t* indptr, const int32_t* indices, cons
 int csl_gat_bwd_t_f32(const int32_t* t_indptr, const int32_t* t_indices, int64_t n_src, int64_t n_pad, const float* el,
                       const float* er, const float* z, int32_t H, int32_t D, float slope, const float* m_in,
                       const float* g_s, const float* g_n, float* g_el, float* g_er, float* g_z, void* stream) {
-  if (n_src < 0 || n_pad < n_src || H < 1 || D < 4 || D % 4 != 0 || D > 256) return CSL_E_INVALID;
-  if (n_pad == 0) return CSL_OK;
-  if (!g_z || !aligned16(g_z) || (n_src > 0 && (!t_indptr || !el || !z || !g_el || !aligned16(z)))) return CSL_E_INVALID;
-  if (n_src > 0 && (!er || !m_in || !g_s || !g_n || !g_er || !aligned16(g_n))) return CSL_E_INVALID;
-  hipLaunchKernelGGL(k_gat_bwd_t, dim3((unsigned)((n_pad + BLK / 64 - 1) / (BLK / 64))), dim3(BLK), 0, (hipStream_t)stream,
-                     t_indptr, t_indices, (long long)n_src, (long long)n_pad, el, er, z, (int)H, (int)D, slope, m_in, g_s,
-                     g_n, g_el, g_er, g_z);
-  return done();
+  return gat_bwd_t(t_indptr, t_indices, n_src, n_pad, el, er, z, H, D, slope, m_in, g_s, g_n, g_el, g_er, g_z, NoDrop{}, stream);
 }
 
-static long long gat_t_rows(long long n) {   // source rows per workgroup of k_gat_bwd_t2: at most ~2048 workgroups
-  long long r = 16;                        // (each leaves a row of partial sums for the second stage to read)
-  // (CSL_GAT_T_BLOCKS: measurement knob; 1024 / 2048 / 4096 workgroups: 32.7 / 26.5 / 26.9 us for the 62 k-row layer, the
-  // second stage 9.5 / 11.2 / 14.6)
-  static const long long cap = getenv("CSL_GAT_T_BLOCKS") ? atoll(getenv("CSL_GAT_T_BLOCKS")) : 2048;
-  while ((n + r - 1) / r > cap) r *= 2;
-  return r;
+int csl_gat_drop_bwd_t_f32(const int32_t* t_indptr, const int32_t* t_indices, int64_t n_src, int64_t n_pad,
+                           const float* el, const float* er, const float* z, int32_t H, int32_t D, float slope,
+                           const float* m_in, const float* g_s, const float* g_n, float* g_el, float* g_er, float* g_z,
+                           const int32_t* src_ids, const int32_t* dst_ids, float p_a, int64_t seed, int32_t layer,
+                           int64_t step, void* stream) {
+  AttnDrop d;
+  if (!attn_drop(src_ids, dst_ids, p_a, seed, layer, step, &d) || !drop_shape_ok(H, D)) return CSL_E_INVALID;
+  return gat_bwd_t(t_indptr, t_indices, n_src, n_pad, el, er, z, H, D, slope, m_in, g_s, g_n, g_el, g_er, g_z, d, stream);
 }
 
 int64_t csl_gat_bwd_t_fused_scratch(int64_t n_pad, int64_t n_out, int32_t H, int32_t D) {
@@ -1399,52 +1586,34 @@ int csl_gat_bwd_t_fused_f32(const int32_t* t_indptr, const int32_t* t_indices, i
                             const float* g_s, const float* g_n, const float* attn_l, const float* attn_r,
                             const int32_t* self_ids_in, int64_t n_out, float* g_er_out, float* g_z, float* g_attn_l,
                             float* g_attn_r, float* scratch, void* stream) {
-  if (n_src < 0 || n_pad < n_src || n_out < 0 || H < 1 || D < 4 || D % 4 != 0 || D > 256 || !g_attn_l || !g_attn_r)
-    return CSL_E_INVALID;
-  hipStream_t st = (hipStream_t)stream;
-  const int C = H * D;
-  const long long r1 = gat_t_rows(n_pad), r2 = gat_t_rows(n_out);
-  const long long b1 = (n_pad + r1 - 1) / r1, b2 = (n_out + r2 - 1) / r2;
-  if (b1 > 0) {
-    if (!g_z || !aligned16(g_z) || !scratch || !aligned16(scratch) || !attn_l || !aligned16(attn_l)) return CSL_E_INVALID;
-    if (n_src > 0 && (!t_indptr || !el || !z || !aligned16(z) || !er_out || !m_in || !g_s || !g_n || !aligned16(g_n) || !g_er_out))
-      return CSL_E_INVALID;
-    if (n_out > 0 && hipMemsetAsync(g_er_out, 0, sizeof(float) * (size_t)n_out * H, st) != hipSuccess) return CSL_E_HIP;
-    hipLaunchKernelGGL(k_gat_bwd_t2, dim3((unsigned)b1), dim3(BLK), 0, st, t_indptr, t_indices, (long long)n_src,
-                       (long long)n_pad, el, er_out, z, (int)H, (int)D, slope, m_in, g_s, g_n, attn_l, g_er_out, g_z, scratch, r1);
-  }
-  if (b2 > 0) {
-    if (!attn_r || !aligned16(attn_r) || !self_ids_in) return CSL_E_INVALID;
-    hipLaunchKernelGGL(k_gat_logits_bwd_dst, dim3((unsigned)b2), dim3(BLK), 0, st, z, attn_r, self_ids_in, g_er_out,
-                       (long long)n_out, (int)H, (int)D, g_z, scratch + b1 * C, r2);
-  }
-  {
-    // both second stages in one launch
-    const float* src[2] = {scratch, scratch + b1 * C};
-    const int64_t nb[2] = {b1, b2};
-    const int32_t hh[2] = {C, C};
-    float* dst[2] = {g_attn_l, g_attn_r};
-    return csl_reduce_multi_f32(2, src, nb, hh, dst, stream);
-  }
+  return gat_bwd_t_fused(t_indptr, t_indices, n_src, n_pad, el, er_out, z, H, D, slope, m_in, g_s, g_n, attn_l, attn_r,
+                         self_ids_in, n_out, g_er_out, g_z, g_attn_l, g_attn_r, scratch, NoDrop{}, stream);
+}
+
+int csl_gat_drop_bwd_t_fused_f32(const int32_t* t_indptr, const int32_t* t_indices, int64_t n_src, int64_t n_pad,
+                                 const float* el, const float* er_out, const float* z, int32_t H, int32_t D, float slope,
+                                 const float* m_in, const float* g_s, const float* g_n, const float* attn_l,
+                                 const float* attn_r, const int32_t* self_ids_in, int64_t n_out, float* g_er_out,
+                                 float* g_z, float* g_attn_l, float* g_attn_r, float* scratch, const int32_t* src_ids,
+                                 const int32_t* dst_ids, float p_a, int64_t seed, int32_t layer, int64_t step,
+                                 void* stream) {
+  AttnDrop d;
+  if (!attn_drop(src_ids, dst_ids, p_a, seed, layer, step, &d) || !drop_shape_ok(H, D)) return CSL_E_INVALID;
+  return gat_bwd_t_fused(t_indptr, t_indices, n_src, n_pad, el, er_out, z, H, D, slope, m_in, g_s, g_n, attn_l, attn_r,
+                         self_ids_in, n_out, g_er_out, g_z, g_attn_l, g_attn_r, scratch, d, stream);
 }
 
 int csl_gat_finish_fwd_f32(const float* n_in, const float* s_in, const float* bias, int64_t n, int32_t H, int32_t D,
                            int32_t elu, float* out, void* stream) {
-  if (n < 0 || H < 1 || D < 4 || D % 4 != 0 || D > 256) return CSL_E_INVALID;
-  if (n == 0) return CSL_OK;
-  if (!n_in || !s_in || !bias || !out || !aligned16(n_in) || !aligned16(bias) || !aligned16(out)) return CSL_E_INVALID;
-  hipLaunchKernelGGL(k_gat_finish_fwd, dim3((unsigned)((n + BLK / 64 - 1) / (BLK / 64))), dim3(BLK), 0, (hipStream_t)stream,
-                     n_in, s_in, bias, (long long)n, (int)H, (int)D, (int)(elu != 0), out);
-  return done();
+  return gat_finish_fwd(n_in, s_in, bias, n, H, D, elu, out, nullptr, NoDrop{}, stream);
 }
 
-// rows per workgroup of k_gat_finish_bwd: a wave walks its rows one after the other (a dependent shuffle chain per row), so a
-// small layer wants MANY small workgroups: with rb_rows' 128 the 8 k-row and 1 k-row layers of config 5's model ran on 64
-// and 8 workgroups, 31-41 us each whatever their size (profiles/r3_gat_in)
-static long long gat_finish_rows(long long n) {
-  long long r = (n + 1023) / 1024;
-  r = (r + 3) / 4 * 4;
-  return r < 4 ? 4 : (r > 128 ? rb_rows(n) : r);
+int csl_gat_finish_drop_fwd_f32(const float* n_in, const float* s_in, const float* bias, int64_t n, int32_t H, int32_t D,
+                                int32_t elu, float* out, float* y, const int32_t* out_ids, float p_f, int64_t seed,
+                                int32_t layer, int64_t step, void* stream) {
+  FeatDrop d;
+  if (!feat_drop(out_ids, p_f, seed, layer, step, &d) || !drop_shape_ok(H, D)) return CSL_E_INVALID;
+  return gat_finish_fwd(n_in, s_in, bias, n, H, D, elu, out, y, d, stream);
 }
 
 int64_t csl_gat_finish_bwd_scratch(int64_t n, int32_t H, int32_t D) {
@@ -1455,20 +1624,16 @@ int64_t csl_gat_finish_bwd_scratch(int64_t n, int32_t H, int32_t D) {
 int csl_gat_finish_bwd_f32(const float* g, int64_t ldg, const float* out, const float* n_in, const float* s_in, int64_t n,
                            int32_t H, int32_t D, int32_t elu, float* g_n, float* g_s, float* g_bias, float* scratch,
                            void* stream) {
-  if (n < 0 || H < 1 || D < 4 || D % 4 != 0 || D > 256 || !g_bias) return CSL_E_INVALID;
-  hipStream_t st = (hipStream_t)stream;
-  const int C = H * D;
-  const long long rpb = gat_finish_rows(n);
-  const long long blocks = (n + rpb - 1) / rpb;
-  if (blocks > 0) {
-    if (!g || ldg < C || ldg % 4 != 0 || !n_in || !s_in || !g_n || !g_s || !scratch || (elu && !out) || !aligned16(g) ||
-        !aligned16(n_in) || !aligned16(g_n) || !aligned16(scratch) || (out && !aligned16(out)))
-      return CSL_E_INVALID;
-    hipLaunchKernelGGL(k_gat_finish_bwd, dim3((unsigned)blocks), dim3(BLK), 0, st, g, (long long)ldg, out, n_in, s_in,
-                       (long long)n, (int)H, (int)D, (int)(elu != 0), g_n, g_s, scratch, rpb);
-  }
-  hipLaunchKernelGGL(k_colsum_finish, dim3((unsigned)((C + 63) / 64)), dim3(BLK), 0, st, scratch, blocks, C, g_bias);
-  return done();
+  return gat_finish_bwd(g, ldg, out, n_in, s_in, n, H, D, elu, g_n, g_s, g_bias, scratch, NoDrop{}, stream);
+}
+
+int csl_gat_finish_drop_bwd_f32(const float* g, int64_t ldg, const float* out, const float* n_in, const float* s_in,
+                                int64_t n, int32_t H, int32_t D, int32_t elu, float* g_n, float* g_s, float* g_bias,
+                                float* scratch, const int32_t* out_ids, float p_f, int64_t seed, int32_t layer,
+                                int64_t step, void* stream) {
+  FeatDrop d;
+  if (!feat_drop(out_ids, p_f, seed, layer, step, &d) || !drop_shape_ok(H, D)) return CSL_E_INVALID;
+  return gat_finish_bwd(g, ldg, out, n_in, s_in, n, H, D, elu, g_n, g_s, g_bias, scratch, d, stream);
 }
 
 int csl_spmm_sum_bwd_f32(const int32_t* indptr, const int32_t* indices, const int32_t* rows, int64_t n_rows,
@@ -1527,33 +1692,35 @@ int csl_div_rows_f32(float* x, int64_t ldx, const int32_t* deg, int64_t n, int32
   return done();
 }
 
-static int gat_args_ok(const void* a, const void* b, const void* c, int32_t H, int32_t D) {
-  if (H < 1 || D < 4 || D % 4 != 0 || D > 256) return 0;  // a head is at most one wave of float4 lanes
-  return aligned16(a) && aligned16(b) && aligned16(c);
-}
-
 int csl_gat_fwd_f32(const int32_t* indptr, const int32_t* indices, int64_t n_rows, const float* el, const float* er,
                     const float* z, int32_t H, int32_t D, float slope, float* m_out, float* s_out, float* n_out,
                     void* stream) {
-  if (n_rows == 0) return CSL_OK;
-  if (n_rows < 0 || !indptr || !er || !m_out || !s_out || !n_out || !gat_args_ok(z, n_out, n_out, H, D))
-    return CSL_E_INVALID;
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_gat_fwd, dim3((unsigned)((n_rows + BLK / 64 - 1) / (BLK / 64))), dim3(BLK), 0, st, indptr,
-                     indices, (long long)n_rows, el, er, z, (int)H, (int)D, slope, m_out, s_out, n_out);
-  return done();
+  return gat_fwd(indptr, indices, n_rows, el, er, z, H, D, slope, m_out, s_out, n_out, NoDrop{}, stream);
+}
+
+// (no rows is CSL_OK above whatever H and D are; the dropped forms refuse a bad shape first)
+int csl_gat_drop_fwd_f32(const int32_t* indptr, const int32_t* indices, int64_t n_rows, const float* el, const float* er,
+                         const float* z, int32_t H, int32_t D, float slope, float* m_out, float* s_out, float* n_out,
+                         const int32_t* src_ids, const int32_t* dst_ids, float p_a, int64_t seed, int32_t layer,
+                         int64_t step, void* stream) {
+  AttnDrop d;
+  if (!attn_drop(src_ids, dst_ids, p_a, seed, layer, step, &d) || n_rows < 0 || !drop_shape_ok(H, D)) return CSL_E_INVALID;
+  return gat_fwd(indptr, indices, n_rows, el, er, z, H, D, slope, m_out, s_out, n_out, d, stream);
 }
 
 int csl_gat_bwd_f32(const int32_t* indptr, const int32_t* indices, int64_t n_rows, const float* el, const float* er,
                     const float* z, int32_t H, int32_t D, float slope, const float* m_in, const float* g_s,
                     const float* g_n, float* g_el, float* g_er, float* g_z, void* stream) {
-  if (n_rows == 0) return CSL_OK;
-  if (n_rows < 0 || !indptr || !er || !m_in || !g_s || !g_n || !g_er || !gat_args_ok(z, g_n, g_z, H, D))
-    return CSL_E_INVALID;
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_gat_bwd, dim3((unsigned)((n_rows + BLK / 64 - 1) / (BLK / 64))), dim3(BLK), 0, st, indptr,
-                     indices, (long long)n_rows, el, er, z, (int)H, (int)D, slope, m_in, g_s, g_n, g_el, g_er, g_z);
-  return done();
+  return gat_bwd(indptr, indices, n_rows, el, er, z, H, D, slope, m_in, g_s, g_n, g_el, g_er, g_z, NoDrop{}, stream);
+}
+
+int csl_gat_drop_bwd_f32(const int32_t* indptr, const int32_t* indices, int64_t n_rows, const float* el, const float* er,
+                         const float* z, int32_t H, int32_t D, float slope, const float* m_in, const float* g_s,
+                         const float* g_n, float* g_el, float* g_er, float* g_z, const int32_t* src_ids,
+                         const int32_t* dst_ids, float p_a, int64_t seed, int32_t layer, int64_t step, void* stream) {
+  AttnDrop d;
+  if (!attn_drop(src_ids, dst_ids, p_a, seed, layer, step, &d) || n_rows < 0 || !drop_shape_ok(H, D)) return CSL_E_INVALID;
+  return gat_bwd(indptr, indices, n_rows, el, er, z, H, D, slope, m_in, g_s, g_n, g_el, g_er, g_z, d, stream);
 }
 
 int csl_sage_cat_f32(const int32_t* indptr, const int32_t* indices, const int32_t* self_ids, const int32_t* owned,
@@ -1847,20 +2014,3 @@ int csl_sage_cat_rows_bwd_f32(const int32_t* self_ids, const int32_t* owned, con
 }
 
 }  // extern "C"
-
-// ---- what gat_dropout.hip runs unchanged (gat_dev.h)
-long long gatx::t_rows(long long n) { return gat_t_rows(n); }
-
-void gatx::logits_bwd_dst(const float* z, const float* attn_r, const int32_t* self_ids_in, const float* g_er_out, int64_t n_out,
-                          int32_t H, int32_t D, float* g_z, float* part_r, long long rows_per_block, void* stream) {
-  const long long blocks = (n_out + rows_per_block - 1) / rows_per_block;
-  hipLaunchKernelGGL(k_gat_logits_bwd_dst, dim3((unsigned)blocks), dim3(BLK), 0, (hipStream_t)stream, z, attn_r, self_ids_in,
-                     g_er_out, (long long)n_out, (int)H, (int)D, g_z, part_r, rows_per_block);
-}
-
-long long gatx::finish_rows(long long n) { return gat_finish_rows(n); }
-
-void gatx::colsum_finish(const float* partial, long long blocks, int32_t C, float* g_bias, void* stream) {
-  hipLaunchKernelGGL(k_colsum_finish, dim3((unsigned)((C + 63) / 64)), dim3(BLK), 0, (hipStream_t)stream, partial, blocks,
-                     (int)C, g_bias);
-}

@@ -25,13 +25,9 @@ __global__ __launch_bounds__(DBLK) void k_dropout(const float* x, long long ldx,
   const float* xr = x + row * ldx;
   float* yr = y + row * ldy;
   for (int q = threadIdx.x & ((1 << lg) - 1); q < hq; q += 1 << lg) {
-    float4 a = *reinterpret_cast<const float4*>(xr + 4 * q);
+    const float4 a = *reinterpret_cast<const float4*>(xr + 4 * q);
     const uint4 w = philox4x32_10(make_uint4((uint32_t)q, v, layer, step), k0, k1);
-    a.x = w.x >= thr ? a.x * s : 0.f;
-    a.y = w.y >= thr ? a.y * s : 0.f;
-    a.z = w.z >= thr ? a.z * s : 0.f;
-    a.w = w.w >= thr ? a.w * s : 0.f;
-    *reinterpret_cast<float4*>(yr + 4 * q) = a;
+    *reinterpret_cast<float4*>(yr + 4 * q) = drop4(a, w, thr, s);
   }
 }
 

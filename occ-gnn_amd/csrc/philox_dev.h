@@ -1,5 +1,6 @@
 // philox_dev.h -- the counter-based generator behind every dropout mask (private to csrc/): Philox4x32-10 as
-// cslicer_dropout.h and cslicer_gat_dropout.h define it, shared by dropout.hip and gat_dropout.hip.
+// cslicer_dropout.h and cslicer_gat_dropout.h define it, shared by dropout.hip and the attention kernels'
+// dropout policies (gat_dev.h).
 #ifndef CSLICER_PHILOX_DEV_H
 #define CSLICER_PHILOX_DEV_H
 
@@ -19,6 +20,15 @@ __device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint32_t k0, uint32_t k1
     k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
   }
   return c;
+}
+
+// the mask on one quad: element j is kept and scaled by s where the quad's word j reaches the threshold
+__device__ __forceinline__ float4 drop4(float4 a, const uint4 w, uint32_t thr, float s) {
+  a.x = w.x >= thr ? a.x * s : 0.f;
+  a.y = w.y >= thr ? a.y * s : 0.f;
+  a.z = w.z >= thr ? a.z * s : 0.f;
+  a.w = w.w >= thr ? a.w * s : 0.f;
+  return a;
 }
 
 }  // namespace

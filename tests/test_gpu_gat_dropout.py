@@ -1,4 +1,4 @@
-"""Dropout for the attention model on the GPU (include/cslicer_gat_dropout.h, csrc/gat_dropout.hip):
+"""Dropout for the attention model on the GPU (include/cslicer_gat_dropout.h, csrc/aggregate.hip):
 
 * the attention mask of csl_gat_drop_fwd_f32 against tests/gat_drop_ref.py, bit for bit (z = 1, el = er = 0: the numerator
   counts the kept edges);
@@ -6,6 +6,8 @@
   groups of 1, 5, 8 and 16 lanes (one chunk of columns and two), 1, 4 and 5 rows, the by-source forms with padding rows
   and self entries, the fused by-source form against the unfused one;
 * the dropped epilogue pair = its parent and csl_dropout_f32, bit for bit, forward and backward;
+* every dropped entry point at p = 2^-33 (no edge dropped, a scale of 1.0f) = its parent, bit for bit: the two are one
+  kernel template and one host path;
 * spec None / both probabilities 0: today's nodes and model, no new call;
 * DistGATModel.forward_parts with both dropouts on one part and on two, against the float64 model with the same masks;
 * trainers: determinism, the seed, 0 / 0, evaluation, the plan;
@@ -289,6 +291,156 @@ def test_dropped_epilogue_is_the_parent_and_the_dropout_kernel_bit_for_bit(H, D,
             res.append((g_n, g_s, g_bias))
         for a, b in zip(*res):
             assert torch.equal(a, b)
+
+
+# ---- the dropped instantiation is its parent ---------------------------------------------------------------------------------
+# p = 2^-33: floor(p 2^32) = 0, so no word is below the threshold and every edge / element is kept, and
+# (float)(1 / (1 - p)) == 1.0f, so kappa = 1.0f and the mask multiplies by 1.0f.  The dropped entry point then computes what
+# its parent computes, operation for operation, and must return the same bits.  Wherever float atomics add (g_z and g_el
+# by destination, g_er by source) no address takes more than two addends onto its zero: either order gives the same sum.
+
+P_KEEP = 2.0 ** -33
+ONE_SHAPES = [(1, 4), (3, 20), (8, 64)]     # a head per lane; head groups of 5 lanes; 16 lanes and two chunks of columns
+
+
+def test_p_keep_keeps_everything_at_scale_one():
+    import dropout_ref
+    assert np.float32(P_KEEP) == P_KEEP and int(np.floor(np.float64(np.float32(P_KEEP)) * 2.0 ** 32)) == 0
+    assert np.float32(1.0 / (1.0 - np.float64(np.float32(P_KEEP)))) == np.float32(1.0)
+    assert dropout_ref.threshold(P_KEEP) == 0 and np.float32(dropout_ref.scale(P_KEEP)) == np.float32(1.0)
+
+
+def _keep_tail(aggr, *ids):
+    return tuple(_p(i) for i in ids) + (P_KEEP, aggr._i64((9 << 32) | 5), 1, aggr._i64((1 << 32) + 2), aggr._stream())
+
+
+@pytest.mark.parametrize("H,D", ONE_SHAPES)
+def test_dropped_aggregation_that_keeps_every_edge_is_the_parent_bit_for_bit(H, D):
+    """csl_gat_drop_fwd_f32 = csl_gat_fwd_f32 (m, s, n) and csl_gat_drop_bwd_f32 = csl_gat_bwd_f32 (g_el, g_er, g_z): 5 rows
+    of 17, 16, 1, 0 and 16 edges (the 16-edge branch, the chunked loop, a second workgroup), node ids up to 2^31 - 1, every
+    source in at most two of the 50 edges"""
+    from cslicer import aggr
+    L = aggr._lib()
+    rng = np.random.default_rng(H * D)
+    n_rows, n_src, Cw = 5, 27, H * D
+    deg = np.array(DEGREES)
+    indptr_np = np.concatenate([[0], np.cumsum(deg)])
+    indices_np = rng.permutation(np.arange(int(deg.sum())) // 2)
+    assert np.bincount(indices_np).max() == 2 and indices_np.max() < n_src
+    indptr, indices = _i32(indptr_np), _i32(indices_np)
+    src_ids, dst_ids = _i32(_ids(n_src, rng, (1 << 31) - 1)), _i32(_ids(n_rows, rng, (1 << 31) - 2))
+    tail = _keep_tail(aggr, src_ids, dst_ids)
+    torch.manual_seed(H + D)
+    el, er, z = torch.randn(n_src, H, device="cuda"), torch.randn(n_rows, H, device="cuda"), torch.randn(n_src, Cw, device="cuda")
+    gs, gn = torch.randn(n_rows, H, device="cuda"), torch.randn(n_rows, Cw, device="cuda")
+    head = (_p(indptr), _p(indices), n_rows, _p(el), _p(er), _p(z), H, D, 0.2)
+    fwd, bwd = [], []
+    for dropped in (False, True):
+        m, s_, n = (torch.full(shape, -7.5, device="cuda") for shape in ((n_rows, H), (n_rows, H), (n_rows, Cw)))
+        if dropped:
+            rc = L.csl_gat_drop_fwd_f32(*head, _p(m), _p(s_), _p(n), *tail)
+        else:
+            rc = L.csl_gat_fwd_f32(*head, _p(m), _p(s_), _p(n), aggr._stream())
+        assert rc == 0
+        g_el, g_z = torch.zeros(n_src, H, device="cuda"), torch.zeros(n_src, Cw, device="cuda")
+        g_er = torch.full((n_rows, H), -7.5, device="cuda")
+        if dropped:
+            rc = L.csl_gat_drop_bwd_f32(*head, _p(m), _p(gs), _p(gn), _p(g_el), _p(g_er), _p(g_z), *tail)
+        else:
+            rc = L.csl_gat_bwd_f32(*head, _p(m), _p(gs), _p(gn), _p(g_el), _p(g_er), _p(g_z), aggr._stream())
+        assert rc == 0
+        torch.cuda.synchronize()
+        fwd.append((m, s_, n))
+        bwd.append((g_el, g_er, g_z))
+    for name, a, b in zip(("m", "s", "n", "g_el", "g_er", "g_z"), fwd[0] + bwd[0], fwd[1] + bwd[1]):
+        assert bool(torch.isfinite(a).all()) and torch.equal(a, b), name
+    assert float(fwd[0][1][3].abs().max()) == 0 and float(fwd[0][1][0].min()) > 0       # the empty row, a full one
+    assert float(bwd[0][2].abs().max()) > 0 and float(bwd[0][0].abs().max()) > 0
+
+
+@pytest.mark.parametrize("H,D", ONE_SHAPES)
+def test_dropped_backward_by_source_that_keeps_every_edge_is_the_parent_bit_for_bit(H, D):
+    """csl_gat_drop_bwd_t_f32 = csl_gat_bwd_t_f32 (g_z, g_el, g_er) and csl_gat_drop_bwd_t_fused_f32 =
+    csl_gat_bwd_t_fused_f32 (g_z, g_er, g_attn_l, g_attn_r): 5 source rows under n_pad = 8, lists of 17, 1, 0, 17 and 1
+    entries, self entries (-1) inside a list, at its end and alone, every destination in at most two edges"""
+    from cslicer import aggr
+    L = aggr._lib()
+    rng = np.random.default_rng(H + D)
+    n_src, n_pad, n_dst, Cw = 5, 8, 20, H * D
+    lists = [list(range(16)) + [-1], [3], [], list(range(4, 12)) + [-1] + list(range(12, 20)), [-1]]
+    assert [len(x) for x in lists] == [17, 1, 0, 17, 1]
+    trow_np = np.concatenate([np.asarray(x, dtype=np.int64) for x in lists])
+    assert np.bincount(trow_np[trow_np >= 0], minlength=n_dst).max() == 2
+    tptr, trow = _i32(np.concatenate([[0], np.cumsum([len(x) for x in lists])])), _i32(trow_np)
+    self_np = np.full(n_dst, -1)
+    self_np[[0, 5, 7]] = [0, 3, 4]               # (a source is the self row of one destination at most)
+    self_ids = _i32(self_np)
+    src_ids, dst_ids = _i32(_ids(n_src, rng, (1 << 31) - 1)), _i32(_ids(n_dst, rng, (1 << 31) - 2))
+    tail = _keep_tail(aggr, src_ids, dst_ids)
+    torch.manual_seed(H * D + 1)
+    el, er, z = torch.randn(n_src, H, device="cuda"), torch.randn(n_dst, H, device="cuda"), torch.randn(n_src, Cw, device="cuda")
+    m = torch.full((n_dst, H), 4.0, device="cuda") + torch.rand(n_dst, H, device="cuda")
+    gs, gn = torch.randn(n_dst, H, device="cuda"), torch.randn(n_dst, Cw, device="cuda")
+    al, ar = torch.randn(Cw, device="cuda"), torch.randn(Cw, device="cuda")
+    head = (_p(tptr), _p(trow), n_src, n_pad, _p(el), _p(er), _p(z), H, D, 0.2, _p(m), _p(gs), _p(gn))
+    words = max(int(L.csl_gat_bwd_t_fused_scratch(n_pad, n_dst, H, D)), 4)
+    plain, fused = [], []
+    for dropped in (False, True):
+        g_el, g_er = torch.full((n_src, H), -7.5, device="cuda"), torch.zeros(n_dst, H, device="cuda")
+        g_z = torch.full((n_pad, Cw), -7.5, device="cuda")
+        if dropped:
+            rc = L.csl_gat_drop_bwd_t_f32(*head, _p(g_el), _p(g_er), _p(g_z), *tail)
+        else:
+            rc = L.csl_gat_bwd_t_f32(*head, _p(g_el), _p(g_er), _p(g_z), aggr._stream())
+        assert rc == 0
+        plain.append((g_z, g_el, g_er))
+        g_er2, g_z2 = torch.full((n_dst, H), -7.5, device="cuda"), torch.full((n_pad, Cw), -7.5, device="cuda")
+        g_al, g_ar = torch.full((Cw,), -7.5, device="cuda"), torch.full((Cw,), -7.5, device="cuda")
+        scratch = torch.empty(words, device="cuda")
+        args = head + (_p(al), _p(ar), _p(self_ids), n_dst, _p(g_er2), _p(g_z2), _p(g_al), _p(g_ar), _p(scratch))
+        rc = L.csl_gat_drop_bwd_t_fused_f32(*args, *tail) if dropped else L.csl_gat_bwd_t_fused_f32(*args, aggr._stream())
+        assert rc == 0
+        torch.cuda.synchronize()
+        fused.append((g_z2, g_er2, g_al, g_ar))
+    for name, a, b in zip(("g_z", "g_el", "g_er", "fused g_z", "fused g_er", "g_attn_l", "g_attn_r"),
+                          plain[0] + fused[0], plain[1] + fused[1]):
+        assert bool(torch.isfinite(a).all()) and torch.equal(a, b), name
+    g_z, g_el, g_er = plain[0]
+    assert float(g_z[n_src:].abs().max()) == 0 and float(g_z[2].abs().max()) == 0 and float(g_z[0].abs().max()) > 0
+    assert float(g_er.abs().max()) > 0 and float(fused[0][3].abs().max()) > 0
+
+
+@pytest.mark.parametrize("n", [1, 5, 130])
+@pytest.mark.parametrize("H,D", ONE_SHAPES)
+def test_dropped_epilogue_that_keeps_every_element_is_the_parent_bit_for_bit(H, D, n):
+    """csl_gat_finish_drop_fwd_f32: out AND y = csl_gat_finish_fwd_f32's out; csl_gat_finish_drop_bwd_f32: g_n, g_s and the
+    bias gradient = csl_gat_finish_bwd_f32's; with the ELU and without"""
+    from cslicer import aggr
+    L = aggr._lib()
+    Cw = H * D
+    ids = _i32(_ids(n, np.random.default_rng(Cw + n), (1 << 31) - 1))
+    tail = _keep_tail(aggr, ids)
+    torch.manual_seed(n + H)
+    nsum, ssum = torch.randn(n, Cw, device="cuda"), torch.rand(n, H, device="cuda") + 0.1
+    bias, g = torch.randn(Cw, device="cuda"), torch.randn(n, Cw, device="cuda")
+    words = max(int(L.csl_gat_finish_bwd_scratch(n, H, D)), 4)
+    for elu in (1, 0):
+        out_p, out_d, y = (torch.full((n, Cw), -7.5, device="cuda") for _ in range(3))
+        assert L.csl_gat_finish_fwd_f32(_p(nsum), _p(ssum), _p(bias), n, H, D, elu, _p(out_p), aggr._stream()) == 0
+        assert L.csl_gat_finish_drop_fwd_f32(_p(nsum), _p(ssum), _p(bias), n, H, D, elu, _p(out_d), _p(y), *tail) == 0
+        torch.cuda.synchronize()
+        assert bool(torch.isfinite(out_p).all()) and torch.equal(out_d, out_p) and torch.equal(y, out_p)
+        res = []
+        for dropped in (False, True):
+            g_n, g_s = torch.full((n, Cw), -7.5, device="cuda"), torch.full((n, H), -7.5, device="cuda")
+            g_bias, scratch = torch.full((Cw,), -7.5, device="cuda"), torch.empty(words, device="cuda")
+            args = (_p(g), g.stride(0), _p(out_p), _p(nsum), _p(ssum), n, H, D, elu, _p(g_n), _p(g_s), _p(g_bias), _p(scratch))
+            rc = L.csl_gat_finish_drop_bwd_f32(*args, *tail) if dropped else L.csl_gat_finish_bwd_f32(*args, aggr._stream())
+            assert rc == 0
+            torch.cuda.synchronize()
+            res.append((g_n, g_s, g_bias))
+        for name, a, b in zip(("g_n", "g_s", "g_bias"), *res):
+            assert bool(torch.isfinite(a).all()) and torch.equal(a, b), (name, elu)
 
 
 # ---- identities -------------------------------------------------------------------------------------------------------------
