@@ -50,6 +50,26 @@ def test_mask_depends_on_every_part_of_the_counter():
     assert dropout_ref.threshold(0.1) == int(np.floor(float(np.float32(0.1)) * 2.0 ** 32))
 
 
+def test_threshold_and_scale_at_the_two_ends_of_p():
+    """p = 2^-33: threshold 0 and s == 1.0f, nothing is dropped and nothing scaled; p = 1 - 2^-24 (the largest float32
+    below 1): threshold 2^32 - 256 and s == 2^24.  tests/test_gpu_dropout_edges.py runs the kernel and the step there."""
+    lo, hi = 2.0 ** -33, 1.0 - 2.0 ** -24
+    assert float(np.float32(lo)) == lo and float(np.float32(hi)) == hi and 0.0 < lo and hi < 1.0
+    assert dropout_ref.threshold(lo) == 0 and dropout_ref.scale(lo) == np.float32(1.0)
+    assert dropout_ref.scale(lo).view(np.uint32) == np.float32(1.0).view(np.uint32)
+    assert dropout_ref.threshold(hi) == (1 << 32) - 256 and dropout_ref.scale(hi) == np.float32(2.0 ** 24)
+    assert bool(dropout_ref.keep_mask(np.arange(300), 64, lo, 12345, 1, 7).all())
+    # one element in 2^24 is kept: none of these 19,200, and what the map gives is +0.0 whatever the input held
+    assert not dropout_ref.keep_mask(np.arange(300), 64, hi, 12345, 1, 7).any()
+    x = np.array([[1.5, -0.0, np.inf, np.nan]], dtype=np.float32)
+    assert dropout_ref.apply(x, [3], hi, 12345, 1, 7).view(np.uint32).tolist() == [[0, 0, 0, 0]]
+    assert np.array_equal(dropout_ref.apply(x, [3], lo, 12345, 1, 7).view(np.uint32)[0, :3], x.view(np.uint32)[0, :3])
+    # and the wrapper's scale is the reference's
+    from cslicer import aggr
+    for p in (lo, 0.1, 0.3, 0.9, hi):
+        assert np.float32(aggr.dropout_scale(p)) == dropout_ref.scale(p)
+
+
 def test_reference_backward_is_autograd_of_the_masked_model():
     """the hand-written float64 backward of dropout_ref.model_on_layers against torch float64 autograd of the same
     forward, on a small random two- and three-layer model: a wrong restatement cannot hide a wrong kernel"""
