@@ -164,6 +164,17 @@ def read_features(path, meta=None, mmap=True):
     return np.fromfile(f, dtype=dt, count=shape[0] * shape[1]).reshape(shape), meta["feature_dtype"]
 
 
+def feature_rows(rows, feature_dtype):
+    """Rows of features.bin in their stored element type (read_features' map, a selection or a copy of it) as what
+    Trainer(features=...) takes: a numpy array, or for bfloat16 -- numpy has none -- the same words as a torch.bfloat16
+    tensor.  No copy is made beyond np.asarray's."""
+    rows = np.asarray(rows)
+    if feature_dtype != "bfloat16":
+        return rows
+    import torch
+    return torch.from_numpy(rows.view(np.int16)).view(torch.bfloat16)
+
+
 def label_words(num_classes):
     """W = ceil(C / 32): the 32-bit words of a node's packed multi-label row"""
     return (int(num_classes) + 31) // 32

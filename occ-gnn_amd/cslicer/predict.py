@@ -64,10 +64,7 @@ def main(argv=None):
     n = meta["num_nodes"]
     nodes = None if a.nodes is None else read_nodes(a.nodes, n)
     rows, stored = l0.read_features(a.graph, meta)
-    if stored == "bfloat16":        # (numpy has no bfloat16: the words become a torch.bfloat16 tensor)
-        feats = torch.from_numpy(np.array(rows).view(np.int16)).view(torch.bfloat16)
-    else:
-        feats = torch.from_numpy(np.array(rows))        # (a copy: the map is read-only)
+    feats = torch.as_tensor(l0.feature_rows(np.array(rows), stored))        # (np.array: a copy, the map is read-only)
     # converted on the HOST, round to nearest even, as the trainer stores its table
     feats = feats.to(aggr.FEATURE_DTYPES[a.feature_dtype or stored]).contiguous()
     dev = torch.device("cuda", torch.cuda.current_device())

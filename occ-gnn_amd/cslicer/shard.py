@@ -58,6 +58,22 @@ def round_plan(n_batches, streams, first_batch, n_steps):
     return plan
 
 
+def round_walk(plan, nxt, base, ahead, slots):
+    """What a trainer does with the engine rounds `plan` (round_plan's), in order: ("submit", entry, slot) -- slice the
+    round `entry` into result slot `slot` -- and ("use", entry, slot) -- consume it there.  Round r of the plan lives in
+    slot (base + r) % slots (`base`: the rounds of all earlier calls, so the rotation goes on from call to call).  Round 0
+    is submitted first, unless an earlier call announced and submitted it (`ahead`: that round, else None); before round r
+    is used the round after it is submitted, which after the last round is nxt[0], the first round of the call that will
+    follow (`nxt`: a list, empty where none is announced).  Pure: no engine, no device."""
+    rounds = list(plan) + list(nxt[:1])
+    if plan and ahead is None:
+        yield "submit", rounds[0], base % slots
+    for r in range(len(plan)):
+        if r + 1 < len(rounds):
+            yield "submit", rounds[r + 1], (base + r + 1) % slots
+        yield "use", rounds[r], (base + r) % slots
+
+
 def dp_chunk(batch_index, global_batch, n_nodes, rank, world):
     """Data-parallel dealing of ONE minibatch: positions [lo, hi) of the node order that rank `rank` of `world` trains
     of minibatch `batch_index` (contiguous chunks of ceil(global_batch / world); the last minibatch of the order may

@@ -139,6 +139,174 @@ def step_plan_gat_drop(feat_dropout=0.0, attn_dropout=0.0, *, kind, gat_input, *
     return step_plan(kind=kind, gat_input=gat_input, **cfg)
 
 
+# ---- the stages of Trainer.__init__.  The _check_* functions are its argument checks, one per group of arguments, in the
+# order the constructor calls them (of two bad arguments the earlier group's error is raised): pure -- numpy and
+# _abi.noreplace_max_fanout() only, no device, no engine -- and each returns its arguments normalised.
+
+def _check_labels(labels, multilabel, num_nodes, n_classes):
+    """multilabel as a bool; with it, a host `labels` (a callable's rows are checked when they are loaded) must be a
+    [num_nodes, n_classes] matrix of 0 / 1"""
+    multilabel = bool(multilabel)
+    if multilabel and not callable(labels):
+        shape = np.shape(labels)
+        if len(shape) != 2:
+            raise ValueError("multilabel=True: labels must be a matrix [num_nodes, n_classes] of 0 / 1, not shape %r"
+                             % (shape,))
+        if shape != (num_nodes, n_classes):
+            raise ValueError("multilabel=True: labels must be [num_nodes = %d, n_classes = %d], not %r"
+                             % (num_nodes, n_classes, shape))
+        la = np.asarray(labels)
+        if la.dtype != np.bool_ and (la.dtype.kind not in "iu" or (la.size and not np.isin(la, (0, 1)).all())):
+            raise ValueError("multilabel=True: every label must be 0 or 1 (bool or integer)")
+    return multilabel
+
+
+def _check_dropouts(model, hidden, dropout, feat_dropout, attn_dropout, gat_input):
+    """(dropout, feat_dropout, attn_dropout) as floats in [0, 1): the first GraphSAGE's, the other two the attention model's"""
+    dropout = float(dropout)
+    if not 0.0 <= dropout < 1.0:
+        raise ValueError("dropout must be in [0, 1), not %r" % (dropout,))
+    if dropout > 0 and model == "gat":
+        raise ValueError("dropout > 0: the attention model has no dropout (model='sage' only)")
+    if dropout > 0 and hidden % 4 != 0:
+        raise ValueError("dropout > 0: hidden must be a multiple of 4 (the kernel moves float4 columns), not %d" % hidden)
+    feat_dropout, attn_dropout = float(feat_dropout), float(attn_dropout)
+    for name, v in (("feat_dropout", feat_dropout), ("attn_dropout", attn_dropout)):
+        if not 0.0 <= v < 1.0:      # (a NaN compares false)
+            raise ValueError("%s must be in [0, 1), not %r" % (name, v))
+        if v > 0 and model == "sage":
+            raise ValueError("%s > 0: GraphSAGE has `dropout`; feat_dropout / attn_dropout belong to model='gat'" % name)
+    if attn_dropout > 0 and gat_input is True:
+        raise ValueError("attn_dropout > 0 with gat_input=True: the aggregate-then-project input layer has no attention "
+                         "dropout (gat_input=None turns it off)")
+    return dropout, feat_dropout, attn_dropout
+
+
+def _check_optimizer(weight_decay, max_grad_norm, lr_schedule):
+    """(weight_decay, max_grad_norm) as floats (the latter or None); lr_schedule must be None or a callable"""
+    weight_decay = float(weight_decay)
+    if not weight_decay >= 0.0:      # (a NaN compares false)
+        raise ValueError("weight_decay must be >= 0, not %r" % (weight_decay,))
+    if max_grad_norm is not None:
+        max_grad_norm = float(max_grad_norm)
+        if not max_grad_norm > 0.0:
+            raise ValueError("max_grad_norm must be None or > 0 (float('inf'): the norm and the non-finite guard "
+                             "without clipping), not %r" % (max_grad_norm,))
+    if lr_schedule is not None and not callable(lr_schedule):
+        raise ValueError("lr_schedule must be None or a callable steps_done -> lr, not %r" % (lr_schedule,))
+    return weight_decay, max_grad_norm
+
+
+def _check_loss(label_smoothing, class_weight, n_classes, multilabel):
+    """(label_smoothing as a float, class_weight as float64 [n_classes] or None): the single-label loss's options"""
+    label_smoothing = float(label_smoothing)
+    if not 0.0 <= label_smoothing < 1.0:     # (a NaN compares false)
+        raise ValueError("label_smoothing must be in [0, 1), not %r" % (label_smoothing,))
+    if class_weight is not None:
+        class_weight = np.asarray(class_weight, dtype=np.float64).reshape(-1) if np.ndim(class_weight) == 1 else None
+        if class_weight is None or class_weight.shape[0] != n_classes:
+            raise ValueError("class_weight must be a sequence of n_classes = %d numbers" % n_classes)
+        if not np.isfinite(class_weight).all() or (class_weight < 0).any() or not (class_weight > 0).any():
+            raise ValueError("class_weight: finite numbers >= 0 with at least one > 0 expected")
+    if multilabel and (class_weight is not None or label_smoothing != 0.0):
+        raise ValueError("multilabel=True: class_weight / label_smoothing belong to the single-label loss; the "
+                         "sigmoid-BCE loss has no weights yet")
+    return label_smoothing, class_weight
+
+
+def _check_sampling(edge_weight, replace, fanouts, num_edges):
+    """edge_weight as float64 [num_edges] (l0.check_edge_weights) or None; replace=False goes with neither edge weights nor
+    a fanout above _abi.noreplace_max_fanout()"""
+    if edge_weight is not None:
+        if not replace:
+            raise ValueError("edge_weight with replace=False: weighted sampling draws with replacement (weighted sampling "
+                             "without replacement is not built)")
+        edge_weight = l0.check_edge_weights(edge_weight, num_edges)
+    if not replace and max(fanouts) > _abi.noreplace_max_fanout():
+        raise ValueError("replace=False: fanouts %r exceed the limit of %d neighbours per row"
+                         % (tuple(fanouts), _abi.noreplace_max_fanout()))
+    return edge_weight
+
+
+def _check_table(feature_dtype, gat_input):
+    """the torch dtype of the feature table named `feature_dtype`; gat_input must be one of None, True, False"""
+    if feature_dtype not in aggr.FEATURE_DTYPES:
+        raise ValueError("feature_dtype must be one of %s, not %r" % (", ".join(aggr.FEATURE_DTYPES), feature_dtype))
+    if not any(gat_input is v for v in (None, True, False)):
+        raise ValueError("gat_input must be None, True or False, not %r" % (gat_input,))
+    return aggr.FEATURE_DTYPES[feature_dtype]
+
+
+def _check_gat_input_on(gat_input, *obstacle_args):
+    """gat_input=True where gat_input_obstacle(*obstacle_args) names a reason why the input layer cannot run"""
+    why = gat_input_obstacle(*obstacle_args) if gat_input is True else None
+    if why is not None:
+        raise ValueError("gat_input=True: " + why)
+
+
+def _check_workload(workload, num_nodes, world):
+    """the owner table as contiguous int32 [num_nodes] with values in [0, world), or None (v % world)"""
+    if workload is not None:
+        workload = np.ascontiguousarray(workload, dtype=np.int32)
+        if workload.shape != (num_nodes,) or workload.min() < 0 or workload.max() >= world:
+            raise ValueError("workload must be int32 [num_nodes] with values in [0, world)")
+    return workload
+
+
+def _check_model(model):
+    """the last of the argument checks: every refusal above that names the model has been raised by now"""
+    if model not in ("sage", "gat"):
+        raise ValueError("model must be 'sage' or 'gat'")
+
+
+def _own_nodes(workload, rank, world, num_nodes):
+    """int64 ids of the nodes rank `rank` owns, ascending: the local row of a node is its position among them"""
+    if workload is None:
+        return np.arange(rank, num_nodes, world, dtype=np.int64)       # owner v % P holds v at local row v // P
+    return np.flatnonzero(workload == rank).astype(np.int64)          # ascending: local row = rank among owned
+
+
+def _host_rows(features, labels, own, world, fdt, multilabel, n_classes):
+    """(f_own, l_own) on the host: the feature rows of the nodes `own` as a contiguous tensor of the stored type `fdt`, and
+    their labels as int64 [n_own] or, multi-label, packed int32 words (aggr.pack_labels).  features / labels: callables of
+    `own`, or arrays over all nodes (one part takes them whole)."""
+    take = (lambda a: a(own)) if callable(features) else (lambda a: a[own] if world > 1 else a)
+    f_own = take(features)
+    if not torch.is_tensor(f_own):
+        f_own = np.asarray(f_own)
+        # (host arrays: float32 or float16 as they come, anything else through float32 as before)
+        f_own = torch.from_numpy(np.ascontiguousarray(
+            f_own, dtype=None if f_own.dtype in (np.float32, np.float16) else np.float32))
+    if f_own.dtype not in (torch.float32, torch.float16, torch.bfloat16) or f_own.dim() != 2:
+        raise ValueError("features: a float32, float16 or bfloat16 matrix expected")
+    # converted on the HOST (round to nearest even), so that the device only ever holds the table in its stored type
+    f_own = f_own.to(fdt).contiguous()
+    n_own = own.shape[0]
+    l_own = labels(own) if callable(labels) else (labels[own] if world > 1 else labels)
+    if multilabel:
+        if np.shape(l_own) != (n_own, n_classes):
+            raise ValueError("multilabel=True: the rank's label rows must be [%d, %d], not %r"
+                             % (n_own, n_classes, np.shape(l_own)))
+        l_own = aggr.pack_labels(l_own)          # (ValueError for anything but 0 / 1)
+    else:
+        l_own = np.ascontiguousarray(l_own, dtype=np.int64)
+    if f_own.shape[0] != n_own or l_own.shape[0] != n_own:
+        raise ValueError("features / labels do not cover the rank's %d nodes" % n_own)
+    return f_own, l_own
+
+
+def _upload_table(f_own, dev):
+    """(the resident table [n_own, F] on `dev`, whether it is a view of rows stored zero-padded).  The readers of a 16-bit
+    table load whole quads of a row (8 bytes): a width that is no multiple of 4 is stored with its rows padded to one
+    (zeros), which is also what lets inference read it in place."""
+    n_own, F = f_own.shape
+    if f_own.dtype == torch.float32 or F % 4 == 0:
+        return f_own.to(dev), False
+    wide = torch.zeros((n_own, (F + 3) // 4 * 4), dtype=f_own.dtype)
+    wide[:, :F] = f_own
+    return wide.to(dev)[:, :F], True
+
+
 class Trainer(object):
     # result slots of the engine: round r lives in slot r % SLOTS.  Three, so that the slot the NEXT round is sliced
     # into was last read two rounds ago: waiting for that round's end event never drains the training stream (with
@@ -252,73 +420,14 @@ class Trainer(object):
         `self.plan` is the StepPlan of the configuration (step_plan above): which step the trainer runs, decided here
         once; `self.native` / `self.native_rank` are the native stepper of that path, None on every other path."""
         # -- 1. the arguments (before any device call: a request that cannot be served is an error, never a quiet fall-back)
-        self.multilabel, self.n_classes = bool(multilabel), int(n_classes)
-        if not callable(labels):
-            shape = np.shape(labels)
-            if self.multilabel and len(shape) != 2:
-                raise ValueError("multilabel=True: labels must be a matrix [num_nodes, n_classes] of 0 / 1, not shape %r"
-                                 % (shape,))
-            if self.multilabel and shape != (indptr.shape[0] - 1, n_classes):
-                raise ValueError("multilabel=True: labels must be [num_nodes = %d, n_classes = %d], not %r"
-                                 % (indptr.shape[0] - 1, n_classes, shape))
-            if self.multilabel:
-                la = np.asarray(labels)
-                if la.dtype != np.bool_ and (la.dtype.kind not in "iu" or (la.size and not np.isin(la, (0, 1)).all())):
-                    raise ValueError("multilabel=True: every label must be 0 or 1 (bool or integer)")
-        dropout = float(dropout)
-        if not 0.0 <= dropout < 1.0:
-            raise ValueError("dropout must be in [0, 1), not %r" % (dropout,))
-        if dropout > 0 and model == "gat":
-            raise ValueError("dropout > 0: the attention model has no dropout (model='sage' only)")
-        if dropout > 0 and hidden % 4 != 0:
-            raise ValueError("dropout > 0: hidden must be a multiple of 4 (the kernel moves float4 columns), not %d" % hidden)
-        self.dropout, self.dropout_seed = dropout, int(seed if dropout_seed is None else dropout_seed)
-        feat_dropout, attn_dropout = float(feat_dropout), float(attn_dropout)
-        for name, v in (("feat_dropout", feat_dropout), ("attn_dropout", attn_dropout)):
-            if not 0.0 <= v < 1.0:      # (a NaN compares false)
-                raise ValueError("%s must be in [0, 1), not %r" % (name, v))
-            if v > 0 and model == "sage":
-                raise ValueError("%s > 0: GraphSAGE has `dropout`; feat_dropout / attn_dropout belong to model='gat'" % name)
-        if attn_dropout > 0 and gat_input is True:
-            raise ValueError("attn_dropout > 0 with gat_input=True: the aggregate-then-project input layer has no attention "
-                             "dropout (gat_input=None turns it off)")
-        self.feat_dropout, self.attn_dropout = feat_dropout, attn_dropout
-        weight_decay = float(weight_decay)
-        if not weight_decay >= 0.0:      # (a NaN compares false)
-            raise ValueError("weight_decay must be >= 0, not %r" % (weight_decay,))
-        if max_grad_norm is not None:
-            max_grad_norm = float(max_grad_norm)
-            if not max_grad_norm > 0.0:
-                raise ValueError("max_grad_norm must be None or > 0 (float('inf'): the norm and the non-finite guard "
-                                 "without clipping), not %r" % (max_grad_norm,))
-        if lr_schedule is not None and not callable(lr_schedule):
-            raise ValueError("lr_schedule must be None or a callable steps_done -> lr, not %r" % (lr_schedule,))
-        self.lr_schedule = lr_schedule
-        label_smoothing = float(label_smoothing)
-        if not 0.0 <= label_smoothing < 1.0:     # (a NaN compares false)
-            raise ValueError("label_smoothing must be in [0, 1), not %r" % (label_smoothing,))
-        if class_weight is not None:
-            class_weight = np.asarray(class_weight, dtype=np.float64).reshape(-1) if np.ndim(class_weight) == 1 else None
-            if class_weight is None or class_weight.shape[0] != self.n_classes:
-                raise ValueError("class_weight must be a sequence of n_classes = %d numbers" % self.n_classes)
-            if not np.isfinite(class_weight).all() or (class_weight < 0).any() or not (class_weight > 0).any():
-                raise ValueError("class_weight: finite numbers >= 0 with at least one > 0 expected")
-        if self.multilabel and (class_weight is not None or label_smoothing != 0.0):
-            raise ValueError("multilabel=True: class_weight / label_smoothing belong to the single-label loss; the "
-                             "sigmoid-BCE loss has no weights yet")
-        if edge_weight is not None:
-            if not replace:
-                raise ValueError("edge_weight with replace=False: weighted sampling draws with replacement (weighted sampling "
-                                 "without replacement is not built)")
-            edge_weight = l0.check_edge_weights(edge_weight, np.shape(indices)[0])
-        if not replace and max(fanouts) > _abi.noreplace_max_fanout():
-            raise ValueError("replace=False: fanouts %r exceed the limit of %d neighbours per row"
-                             % (tuple(fanouts), _abi.noreplace_max_fanout()))
-        if feature_dtype not in aggr.FEATURE_DTYPES:
-            raise ValueError("feature_dtype must be one of %s, not %r" % (", ".join(aggr.FEATURE_DTYPES), feature_dtype))
-        fdt = aggr.FEATURE_DTYPES[feature_dtype]
-        if not any(gat_input is v for v in (None, True, False)):
-            raise ValueError("gat_input must be None, True or False, not %r" % (gat_input,))
+        N = indptr.shape[0] - 1
+        self.n_classes = int(n_classes)
+        self.multilabel = _check_labels(labels, multilabel, N, n_classes)
+        dropout, feat_dropout, attn_dropout = _check_dropouts(model, hidden, dropout, feat_dropout, attn_dropout, gat_input)
+        weight_decay, max_grad_norm = _check_optimizer(weight_decay, max_grad_norm, lr_schedule)
+        label_smoothing, class_weight = _check_loss(label_smoothing, class_weight, self.n_classes, self.multilabel)
+        edge_weight = _check_sampling(edge_weight, replace, fanouts, np.shape(indices)[0])
+        fdt = _check_table(feature_dtype, gat_input)
         # rank_path=True forces the one-process-per-part code (collectives included) even for a single part:
         # a way to run the RCCL calls on a one-GPU box
         self.rank_path = (world > 1) if rank_path is None else bool(rank_path)
@@ -326,53 +435,25 @@ class Trainer(object):
         F_early = None
         if model == "gat":   # (the attention model's input width, known before the rows are loaded)
             F_early = features.shape[1] if feat_dim is None and not callable(features) else feat_dim
-        if gat_input is True:
-            why = gat_input_obstacle(model, world, self.rank_path, len(fanouts), F_early, hidden, n_classes, heads,
-                                     fanouts[-1], sw)
-            if why is not None:
-                raise ValueError("gat_input=True: " + why)
+        _check_gat_input_on(gat_input, model, world, self.rank_path, len(fanouts), F_early, hidden, n_classes, heads,
+                            fanouts[-1], sw)
+        workload = _check_workload(workload, N, world)
+        _check_model(model)
+        self.dropout, self.dropout_seed = dropout, int(seed if dropout_seed is None else dropout_seed)
+        self.feat_dropout, self.attn_dropout, self.lr_schedule = feat_dropout, attn_dropout, lr_schedule
         self.rank, self.world, self.dist = rank, world, dist
         # (kept for the record a checkpoint holds: checkpoint_fields)
         self.seed, self.rng_seed, self.feature_dtype = int(seed), int(rng_seed), feature_dtype
         self.fanouts = tuple(int(f) for f in fanouts)
         self.P = world
+        self.N, self.B, self.S, self.L = N, batch, streams, len(fanouts)
         self.dev = torch.device("cuda", device)
         torch.cuda.set_device(self.dev)
-        N = indptr.shape[0] - 1
-        self.N, self.B, self.S, self.L = N, batch, streams, len(fanouts)
-        if workload is not None:
-            workload = np.ascontiguousarray(workload, dtype=np.int32)
-            if workload.shape != (N,) or workload.min() < 0 or workload.max() >= world:
-                raise ValueError("workload must be int32 [num_nodes] with values in [0, world)")
-        # -- 2. the rank's nodes and their rows, on the host
-        if workload is None:
-            own = np.arange(rank, N, self.P, dtype=np.int64)           # owner v % P holds v at local row v // P
-        else:
-            own = np.flatnonzero(workload == rank).astype(np.int64)   # ascending: local row = rank among owned
-        self.n_own = own.shape[0]
-        # the rank's nodes (ascending) and the owner table (None: v % P), which rank-path evaluation needs
-        self.own, self.owner = own, workload
-        take = (lambda a: a(own)) if callable(features) else (lambda a: a[own] if self.P > 1 else a)
-        f_own = take(features)
-        if not torch.is_tensor(f_own):
-            f_own = np.asarray(f_own)
-            # (host arrays: float32 or float16 as they come, anything else through float32 as before)
-            f_own = torch.from_numpy(np.ascontiguousarray(
-                f_own, dtype=None if f_own.dtype in (np.float32, np.float16) else np.float32))
-        if f_own.dtype not in (torch.float32, torch.float16, torch.bfloat16) or f_own.dim() != 2:
-            raise ValueError("features: a float32, float16 or bfloat16 matrix expected")
-        # converted on the HOST (round to nearest even), so that the device only ever holds the table in its stored type
-        f_own = f_own.to(fdt).contiguous()
-        l_own = labels(own) if callable(labels) else (labels[own] if self.P > 1 else labels)
-        if self.multilabel:
-            if np.shape(l_own) != (self.n_own, n_classes):
-                raise ValueError("multilabel=True: the rank's label rows must be [%d, %d], not %r"
-                                 % (self.n_own, n_classes, np.shape(l_own)))
-            l_own = aggr.pack_labels(l_own)          # (ValueError for anything but 0 / 1)
-        else:
-            l_own = np.ascontiguousarray(l_own, dtype=np.int64)
-        if f_own.shape[0] != self.n_own or l_own.shape[0] != self.n_own:
-            raise ValueError("features / labels do not cover the rank's %d nodes" % self.n_own)
+        # -- 2. the rank's nodes (ascending) and their rows, on the host; the owner table (None: v % P) is what rank-path
+        # evaluation needs
+        own = _own_nodes(workload, rank, world, N)
+        self.own, self.owner, self.n_own = own, workload, own.shape[0]
+        f_own, l_own = _host_rows(features, labels, own, world, fdt, self.multilabel, n_classes)
         F = f_own.shape[1] if feat_dim is None else feat_dim
         # -- 3. how this configuration trains, 4. the engine it needs.  One process per part: only this rank's slices are
         # materialised (the sampling itself is replicated)
@@ -393,17 +474,7 @@ class Trainer(object):
             self.eng.set_edge_cdf(cdf)
             del cdf
         # -- 5. the resident table and the model
-        # whether self.feat is a view of rows stored zero-padded to a multiple of 4 (what lets inference read it in place)
-        self._feat_padded = bool(fdt != torch.float32 and f_own.shape[1] % 4)
-        if self._feat_padded:
-            # the readers of a 16-bit table load whole quads of a row (8 bytes): a width that is no multiple of 4 is stored
-            # with its rows padded to one (zeros), self.feat being the [n_own, F] view of it
-            wide = torch.zeros((self.n_own, (f_own.shape[1] + 3) // 4 * 4), dtype=fdt)
-            wide[:, :f_own.shape[1]] = f_own
-            self.feat = wide.to(self.dev)[:, :f_own.shape[1]]
-            del wide
-        else:
-            self.feat = f_own.to(self.dev)
+        self.feat, self._feat_padded = _upload_table(f_own, self.dev)
         self.labels = torch.from_numpy(l_own).to(self.dev)
         del f_own, l_own
         # the single-label loss's options (None: the plain cross-entropy, the calls as they have always been)
@@ -421,10 +492,8 @@ class Trainer(object):
         self.kind = model
         if model == "sage":
             self.model = splitgnn.DistSAGEModel(F, hidden, n_classes, n_layers=self.L).to(self.dev)
-        elif model == "gat":
-            self.model = splitgnn.DistGATModel(F, hidden, n_classes, heads=heads, n_layers=self.L).to(self.dev)
         else:
-            raise ValueError("model must be 'sage' or 'gat'")
+            self.model = splitgnn.DistGATModel(F, hidden, n_classes, heads=heads, n_layers=self.L).to(self.dev)
         # -- 6. torch.optim.Adam's update in one HIP launch per step (the library's for-each form is eight small
         # launches, ~0.1 ms of GPU time per step; its fused form one of 42 us for these six small tensors)
         params = list(self.model.parameters())
@@ -641,35 +710,22 @@ class Trainer(object):
             if self._loss_ring.numel() < n_steps:
                 self._loss_ring = torch.zeros((n_steps,), dtype=torch.float32, device=self.dev)
             self._ring_at = 0
-        base = self._round_base        # rounds keep rotating through the result slots from call to call
-        done = self._slot_done         # per slot: event behind the last step that read the slot
-
-        def submit(r, entry):
-            slot = (base + r) % self.SLOTS
-            ev = done[slot]
-            if ev is not None:
-                ev.synchronize()                          # the slot's previous consumer has finished
-            self._submit(entry[0], entry[1], slot)
-
         ahead, self._ahead = self._ahead, None
         if ahead is not None and ahead != plan[0]:
             raise RuntimeError("run(then=...) announced the round %r, this call starts with %r" % (ahead, plan[0]))
-        if ahead is None:
-            submit(0, plan[0])
         nxt = shard.round_plan(self.n_batches, self.S, then[0], then[1])[:1] if then else []
-        for r in range(len(plan)):
-            if r + 1 < len(plan):
-                submit(r + 1, plan[r + 1])
-            elif nxt:
-                submit(r + 1, nxt[0])
-                self._ahead = nxt[0]
-            slot = (base + r) % self.SLOTS
-            for s in range(plan[r][1]):
+        # rounds keep rotating through the result slots from call to call (shard.round_walk)
+        for what, entry, slot in shard.round_walk(plan, nxt, self._round_base, ahead, self.SLOTS):
+            if what == "submit":
+                self._submit_when_free(entry, slot)
+                continue
+            for s in range(entry[1]):
                 losses.append(self._step(s, slot))
-            ev = torch.cuda.Event()
+            ev = torch.cuda.Event()                       # behind the last step that reads the slot
             ev.record()
-            done[slot] = ev
-        self._round_base = (base + len(plan)) % self.SLOTS
+            self._slot_done[slot] = ev
+        self._ahead = nxt[0] if nxt else None
+        self._round_base = (self._round_base + len(plan)) % self.SLOTS
         torch.cuda.synchronize()
         return [float(x) for x in losses]
 
@@ -684,25 +740,23 @@ class Trainer(object):
             raise RuntimeError("skip(): run(then=...) has already submitted the round %r; the announced run() must follow"
                                % (self._ahead,))
         plan = shard.round_plan(self.n_batches, self.S, first_batch, n_steps)
-        base, done = self._round_base, self._slot_done
-
-        def submit(r):
-            slot = (base + r) % self.SLOTS
-            if done[slot] is not None:
-                done[slot].synchronize()                  # a step of an earlier run() may still read the slot
-                done[slot] = None
-            self._submit(plan[r][0], plan[r][1], slot)
-
-        if plan:
-            submit(0)
-        for r in range(len(plan)):
-            if r + 1 < len(plan):
-                submit(r + 1)
-            slot = (base + r) % self.SLOTS
-            for s in range(plan[r][1]):
+        for what, entry, slot in shard.round_walk(plan, [], self._round_base, None, self.SLOTS):
+            if what == "submit":
+                self._submit_when_free(entry, slot)
+                continue
+            for s in range(entry[1]):
                 self.eng.meta(s, slot)                    # waits for the round; raises what _step would
-        self._round_base = (base + len(plan)) % self.SLOTS
+        self._round_base = (self._round_base + len(plan)) % self.SLOTS
         return len(plan)
+
+    def _submit_when_free(self, entry, slot):
+        """the round `entry` = (first minibatch, count) into result slot `slot`, once the last step that read the slot (a
+        run()'s, recorded in _slot_done) has finished"""
+        ev = self._slot_done[slot]
+        if ev is not None:
+            ev.synchronize()
+            self._slot_done[slot] = None
+        self._submit(entry[0], entry[1], slot)
 
     def _submit(self, first, n, slot):
         """minibatches [first, first + n) of the node order into result slot `slot`"""
@@ -1148,6 +1202,181 @@ def _split(a, n):
     return np.sort(perm[:cut]), np.sort(perm[cut:])
 
 
+# ---- the stages of main(), in the order it calls them
+
+def _refuse_early(a):
+    """the refusals that need the command line only, before anything is loaded"""
+    if a.multilabel and (a.label_smoothing is not None or a.class_weight is not None):
+        raise SystemExit("--multilabel: --label-smoothing and --class-weight belong to the single-label loss (the sigmoid-BCE "
+                         "loss has no weights yet)")
+    if a.edge_weight is not None and a.no_replace:
+        raise SystemExit("--edge-weight: weighted sampling draws with replacement and does not combine with --no-replace "
+                         "(weighted sampling without replacement is not built)")
+    if a.no_replace:
+        lim = _abi.noreplace_max_fanout()
+        if any(int(x) > lim for x in a.fan_out.split(",")):
+            raise SystemExit("--no-replace: --fan-out %s exceeds the limit of %d neighbours per row" % (a.fan_out, lim))
+    if a.save is not None and (a.save_every < 1 or not os.path.isdir(os.path.dirname(os.path.abspath(a.save)))):
+        raise SystemExit("--save %s: --save-every must be >= 1 and the file's directory must exist" % a.save)
+
+
+def _resume_epochs(a):
+    """the finished epochs that --resume's file records (0 without --resume): the file is checked before the graph is loaded"""
+    if a.resume is None:
+        return 0
+    from . import checkpoint
+    if not os.path.isfile(a.resume):
+        raise SystemExit("--resume %s: no such file" % a.resume)
+    try:
+        epochs_done = checkpoint.read(a.resume)["extra"].get("epoch")
+    except ValueError as ex:
+        raise SystemExit("--resume %s: %s" % (a.resume, ex))
+    if not isinstance(epochs_done, int) or isinstance(epochs_done, bool) or epochs_done < 0:
+        raise SystemExit("--resume %s: the file records no finished epochs (it was not written by --save)" % a.resume)
+    return epochs_done
+
+
+def _process_group():
+    """(rank, world, local rank, torch.distributed or None) of the torchrun environment; with more than one process the
+    group is initialised here"""
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    rank = int(os.environ.get("RANK", "0"))
+    local = int(os.environ.get("LOCAL_RANK", "0"))
+    dist = None
+    if world > 1:
+        import torch.distributed as dist
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        torch.cuda.set_device(local)
+        dist.init_process_group(backend=os.environ.get("CSLICER_DIST_BACKEND", "nccl"))
+    return rank, world, local, dist
+
+
+# what --graph names: feats / labels are callables own ids -> rows, so that every rank generates or reads (memory-mapped)
+# only the rows of the nodes it owns; fdim, fdtype: the table's width and the element type it is kept in; workload: the
+# owner table of --partition file, else None
+_Graph = collections.namedtuple("_Graph", "indptr indices feats labels n_classes fdim fdtype workload")
+
+
+def _load_graph(a):
+    """the _Graph of --graph: `synthetic` or a preset (generated), or an L0 directory (read)"""
+    if a.graph == "synthetic" or a.graph in l0.PRESETS:
+        n, d, fdim, n_classes = (200_000, 20.0, 128, 40) if a.graph == "synthetic" else l0.PRESETS[a.graph]
+        indptr, indices = l0.synth_graph(n, d, seed=0)
+        feats = lambda own: synthetic_node_data(n, fdim, n_classes, seed=0, rows=own)[0]    # noqa: E731
+        labels = lambda own: synthetic_node_data(n, 1, n_classes, seed=0, rows=own)[1]      # noqa: E731
+        if a.multilabel:
+            labels = lambda own: synthetic_multilabels(n, n_classes, seed=0, rows=own, feat_dim=fdim)   # noqa: E731
+        if a.partition == "file":
+            raise SystemExit("--partition file needs an L0 directory")
+        return _Graph(indptr, indices, feats, labels, n_classes, fdim, a.feature_dtype or "float32", None)
+    indptr, indices, meta = l0.read_l0(a.graph, mmap=False)
+    n, n_classes = meta["num_nodes"], meta["num_classes"]
+    fmap, stored = l0.read_features(a.graph, meta)          # (in the stored element type)
+    if bool(meta.get("multilabel")) != bool(a.multilabel):
+        raise SystemExit("--multilabel needs an L0 directory whose meta.txt says multilabel=1 (%s does not)" % a.graph
+                         if a.multilabel else
+                         "%s is a multi-label directory (multilabel=1 in its meta.txt): pass --multilabel" % a.graph)
+    lmap = (l0.read_labels(a.graph, meta) if a.multilabel else
+            np.memmap(os.path.join(a.graph, "labels.bin"), dtype=np.int32, mode="r", shape=(n,)))
+    feats = lambda own: l0.feature_rows(fmap[own], stored)                                # noqa: E731
+    labels = lambda own: np.asarray(lmap[own]).astype(np.int64)                          # noqa: E731
+    if a.multilabel:
+        labels = lambda own: l0.unpack_labels(np.asarray(lmap[own]), n_classes)              # noqa: E731
+    workload = None
+    if a.partition == "file":
+        workload = np.fromfile(os.path.join(a.graph, "partition_map_opt.bin"), dtype=np.int32)
+    return _Graph(indptr, indices, feats, labels, n_classes, meta["feature_dim"], a.feature_dtype or stored, workload)
+
+
+def _edge_weight(a, indptr, indices):
+    """the host edge weights --edge-weight names, None without it"""
+    if a.edge_weight == "inv-degree":
+        return l0.inv_degree_weights(indptr, indices)
+    if a.edge_weight == "l0":
+        if a.graph == "synthetic" or a.graph in l0.PRESETS:
+            raise SystemExit("--edge-weight l0 needs an L0 directory")
+        return l0.read_edge_weight(a.graph)
+    if a.edge_weight is not None:
+        if os.path.getsize(a.edge_weight) != 4 * indices.shape[0]:
+            raise SystemExit("--edge-weight %s: %d bytes, the graph's %d edges need %d (float32 each)"
+                             % (a.edge_weight, os.path.getsize(a.edge_weight), indices.shape[0], 4 * indices.shape[0]))
+        return np.fromfile(a.edge_weight, dtype="<f4")
+    return None
+
+
+def _trainer_kw(a, g, train_nodes, steps_per_epoch, edge_weight):
+    """every optional Trainer keyword of the command line, each only where its option was given: the place where a new
+    option adds its line"""
+    kw = {"multilabel": True} if a.multilabel else {}
+    kw.update(_optimizer_kw(a, steps_per_epoch))
+    if a.feat_dropout is not None:
+        kw["feat_dropout"] = a.feat_dropout
+    if a.attn_dropout is not None:
+        kw["attn_dropout"] = a.attn_dropout
+    kw.update(_loss_kw(a, g.labels, train_nodes, g.indptr.shape[0] - 1, g.n_classes))
+    if edge_weight is not None:
+        kw["edge_weight"] = edge_weight
+    return kw
+
+
+def _start_epoch(a, tr, train_nodes, epoch):
+    """the epoch's node order (a pure function of its number) into the trainer; returns its minibatches"""
+    if train_nodes is None:
+        tr.set_nodes(np.random.default_rng(epoch).permutation(tr.N))
+    else:
+        tr.set_nodes(train_nodes[np.random.default_rng(epoch).permutation(train_nodes.shape[0])])
+    return tr.n_batches if a.max_steps <= 0 else min(a.max_steps, tr.n_batches)
+
+
+def _resume(a, tr, epochs_done, train_nodes, rank):
+    """--resume: the file into the trainer, the sampler back to its position -- the finished epochs through the slicer,
+    nothing trained -- and rank 0's report"""
+    try:
+        was, _ = tr.load_checkpoint(a.resume)
+    except ValueError as ex:
+        raise SystemExit("--resume %s: %s" % (a.resume, ex))
+    left = epochs_done < a.num_epochs        # (nothing to continue: nothing to replay)
+    replayed = 0
+    for e in range(epochs_done if left else 0):
+        steps = _start_epoch(a, tr, train_nodes, e)
+        tr.skip(steps)
+        replayed += steps
+    if rank != 0:
+        return
+    print("resumed from %s: epoch %d, %d steps" % (a.resume, epochs_done, tr.steps_done))
+    now = tr.checkpoint_fields()
+    odd = ["%s was %r, is %r" % (k, was[k], now[k]) for k in sorted(now)
+           if k not in ("steps_done", "world") and k in was and was[k] != now[k]]
+    if left and replayed != tr.steps_done:
+        odd.append("the file holds %d steps, %d epochs of this command line are %d" % (tr.steps_done, epochs_done, replayed))
+    for line in odd:
+        print("resume: %s: the continuation will not be the uninterrupted run's" % line)
+    if not left:
+        print("resume: the file holds %d epochs and --num-epochs is %d: nothing is left to train"
+              % (epochs_done, a.num_epochs))
+
+
+def _train_epochs(a, tr, first_epoch, train_nodes, eval_nodes, rank):
+    """epochs first_epoch .. --num-epochs - 1: train, --save and evaluate where they are due"""
+    for epoch in range(first_epoch, a.num_epochs):
+        steps = _start_epoch(a, tr, train_nodes, epoch)
+        t0 = time.time()
+        losses = tr.run(steps)
+        if rank == 0:
+            print("epoch %d: %d minibatches in %.2f s, loss %.4f -> %.4f" % (epoch, steps, time.time() - t0, losses[0], losses[-1]))
+        if a.save is not None and ((epoch + 1) % a.save_every == 0 or epoch + 1 == a.num_epochs):
+            tr.save_checkpoint(a.save, extra={"epoch": epoch + 1})
+        if eval_nodes is not None and ((epoch + 1) % max(a.eval_every, 1) == 0 or epoch + 1 == a.num_epochs):
+            t0 = time.time()
+            ev = tr.evaluate(eval_nodes)
+            if rank == 0:
+                # the key of the reference's trainers (pa_cache_multi_gpu.py:252)
+                if a.multilabel:
+                    print("Eval F1 %.4f | loss %.4f | %d nodes in %.2f s" % (ev["micro_f1"], ev["loss"], ev["n"], time.time() - t0))
+                else:
+                    print("Eval Acc %.4f | loss %.4f | %d nodes in %.2f s" % (ev["accuracy"], ev["loss"], ev["n"], time.time() - t0))
+
+
 def main(argv=None):
     """Command line with the argument names of the reference's python/train.py:109-131 (same spelling, same
     defaults where they apply); one process per GPU under torchrun, or a single process.
@@ -1223,158 +1452,32 @@ def main(argv=None):
         python -m cslicer.train --graph products-like --model-name gat --feature-dtype bfloat16 --gat-input on
         python -m cslicer.train --graph products-like --model-name gat --feat-dropout 0.6 --attn-dropout 0.6 --eval-split holdout"""
     a = _parser().parse_args(argv)
-    from . import l0
-    if a.multilabel and (a.label_smoothing is not None or a.class_weight is not None):
-        raise SystemExit("--multilabel: --label-smoothing and --class-weight belong to the single-label loss (the sigmoid-BCE "
-                         "loss has no weights yet)")
-    if a.edge_weight is not None and a.no_replace:     # (before the graph is loaded)
-        raise SystemExit("--edge-weight: weighted sampling draws with replacement and does not combine with --no-replace "
-                         "(weighted sampling without replacement is not built)")
-    if a.no_replace:     # (before the graph is loaded)
-        lim = _abi.noreplace_max_fanout()
-        if any(int(x) > lim for x in a.fan_out.split(",")):
-            raise SystemExit("--no-replace: --fan-out %s exceeds the limit of %d neighbours per row" % (a.fan_out, lim))
-    if a.save is not None and (a.save_every < 1 or not os.path.isdir(os.path.dirname(os.path.abspath(a.save)))):
-        raise SystemExit("--save %s: --save-every must be >= 1 and the file's directory must exist" % a.save)
-    epochs_done = 0
-    if a.resume is not None:     # (before the graph is loaded)
-        from . import checkpoint
-        if not os.path.isfile(a.resume):
-            raise SystemExit("--resume %s: no such file" % a.resume)
-        try:
-            epochs_done = checkpoint.read(a.resume)["extra"].get("epoch")
-        except ValueError as ex:
-            raise SystemExit("--resume %s: %s" % (a.resume, ex))
-        if not isinstance(epochs_done, int) or isinstance(epochs_done, bool) or epochs_done < 0:
-            raise SystemExit("--resume %s: the file records no finished epochs (it was not written by --save)" % a.resume)
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    rank = int(os.environ.get("RANK", "0"))
-    local = int(os.environ.get("LOCAL_RANK", "0"))
-    dist = None
-    if world > 1:
-        import torch.distributed as dist_
-        dist = dist_
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        torch.cuda.set_device(local)
-        dist.init_process_group(backend=os.environ.get("CSLICER_DIST_BACKEND", "nccl"))
-    workload, fdim = None, None
-    fdtype = a.feature_dtype or "float32"
-    if a.graph == "synthetic" or a.graph in l0.PRESETS:
-        n, d, fdim, n_classes = (200_000, 20.0, 128, 40) if a.graph == "synthetic" else l0.PRESETS[a.graph]
-        indptr, indices = l0.synth_graph(n, d, seed=0)
-        # every rank generates only the rows of the nodes it owns
-        feats = lambda own: synthetic_node_data(n, fdim, n_classes, seed=0, rows=own)[0]    # noqa: E731
-        labels = lambda own: synthetic_node_data(n, 1, n_classes, seed=0, rows=own)[1]      # noqa: E731
-        if a.multilabel:
-            labels = lambda own: synthetic_multilabels(n, n_classes, seed=0, rows=own, feat_dim=fdim)   # noqa: E731
-        if a.partition == "file":
-            raise SystemExit("--partition file needs an L0 directory")
-    else:
-        indptr, indices, meta = l0.read_l0(a.graph, mmap=False)
-        n, fdim = meta["num_nodes"], meta["feature_dim"]
-        # memory-mapped: a rank touches only the rows it owns
-        fmap, stored = l0.read_features(a.graph, meta)          # (in the stored element type)
-        if bool(meta.get("multilabel")) != bool(a.multilabel):
-            raise SystemExit("--multilabel needs an L0 directory whose meta.txt says multilabel=1 (%s does not)" % a.graph
-                             if a.multilabel else
-                             "%s is a multi-label directory (multilabel=1 in its meta.txt): pass --multilabel" % a.graph)
-        lmap = (l0.read_labels(a.graph, meta) if a.multilabel else
-                np.memmap(os.path.join(a.graph, "labels.bin"), dtype=np.int32, mode="r", shape=(n,)))
-        if stored == "bfloat16":    # (numpy has no bfloat16: the rank's words become a torch.bfloat16 tensor)
-            feats = lambda own: torch.from_numpy(np.asarray(fmap[own]).view(np.int16)).view(torch.bfloat16)   # noqa: E731
-        else:
-            feats = lambda own: np.asarray(fmap[own])                                        # noqa: E731
-        fdtype = a.feature_dtype or stored
-        labels = lambda own: np.asarray(lmap[own]).astype(np.int64)                          # noqa: E731
-        n_classes = meta["num_classes"]
-        if a.multilabel:
-            labels = lambda own: l0.unpack_labels(np.asarray(lmap[own]), n_classes)              # noqa: E731
-        if a.partition == "file":
-            workload = np.fromfile(os.path.join(a.graph, "partition_map_opt.bin"), dtype=np.int32)
-    edge_weight = None
-    if a.edge_weight == "inv-degree":
-        edge_weight = l0.inv_degree_weights(indptr, indices)
-    elif a.edge_weight == "l0":
-        if a.graph == "synthetic" or a.graph in l0.PRESETS:
-            raise SystemExit("--edge-weight l0 needs an L0 directory")
-        edge_weight = l0.read_edge_weight(a.graph)
-    elif a.edge_weight is not None:
-        if os.path.getsize(a.edge_weight) != 4 * indices.shape[0]:
-            raise SystemExit("--edge-weight %s: %d bytes, the graph's %d edges need %d (float32 each)"
-                             % (a.edge_weight, os.path.getsize(a.edge_weight), indices.shape[0], 4 * indices.shape[0]))
-        edge_weight = np.fromfile(a.edge_weight, dtype="<f4")
-    train_nodes, eval_nodes = _split(a, indptr.shape[0] - 1)
+    _refuse_early(a)
+    epochs_done = _resume_epochs(a)
+    rank, world, local, dist = _process_group()
+    g = _load_graph(a)
+    edge_weight = _edge_weight(a, g.indptr, g.indices)
+    n = g.indptr.shape[0] - 1
+    train_nodes, eval_nodes = _split(a, n)
     fan = tuple(int(x) for x in a.fan_out.split(","))[::-1]          # engine order: layer 0 = hop from the seeds
     if len(fan) != a.num_layers:
         fan = fan[:a.num_layers] if len(fan) > a.num_layers else fan
-    n_train = indptr.shape[0] - 1 if train_nodes is None else train_nodes.shape[0]
+    n_train = n if train_nodes is None else train_nodes.shape[0]
     per_epoch = (n_train + a.batch_size - 1) // a.batch_size           # (Trainer.set_nodes' n_batches)
     per_epoch = per_epoch if a.max_steps <= 0 else min(a.max_steps, per_epoch)
     kind = "gat" if a.model_name == "gat" else "sage"
     hidden = a.num_hidden // a.num_heads if kind == "gat" else a.num_hidden
-    tr = Trainer(indptr, indices, feats, labels, n_classes, rank=rank, world=world, fanouts=fan, batch=a.batch_size,
-                 streams=8, hidden=max(4, hidden // 4 * 4), lr=a.lr, device=local, dist=dist, model=kind, heads=a.num_heads,
-                 workload=workload, feat_dim=fdim, feature_dtype=fdtype,
+    tr = Trainer(g.indptr, g.indices, g.feats, g.labels, g.n_classes, rank=rank, world=world, fanouts=fan,
+                 batch=a.batch_size, streams=8, hidden=max(4, hidden // 4 * 4), lr=a.lr, device=local, dist=dist, model=kind,
+                 heads=a.num_heads, workload=g.workload, feat_dim=g.fdim, feature_dtype=g.fdtype,
                  gat_input={"auto": None, "on": True, "off": False}[a.gat_input], replace=not a.no_replace,
-                 dropout=a.dropout, **({"multilabel": True} if a.multilabel else {}), **_optimizer_kw(a, per_epoch),
-                 **({} if a.feat_dropout is None else {"feat_dropout": a.feat_dropout}),
-                 **({} if a.attn_dropout is None else {"attn_dropout": a.attn_dropout}),
-                 **_loss_kw(a, labels, train_nodes, indptr.shape[0] - 1, n_classes),
-                 **({} if edge_weight is None else {"edge_weight": edge_weight}))
+                 dropout=a.dropout, **_trainer_kw(a, g, train_nodes, per_epoch, edge_weight))
     del edge_weight
-    if rank == 0 and fdtype != "float32":
-        print("feature table: %s, %d bytes on this rank" % (fdtype, tr.feat.numel() * tr.feat.element_size()))
-    n = indptr.shape[0] - 1
-
-    def start_epoch(epoch):
-        """the epoch's node order (a pure function of its number) into the trainer; returns its minibatches"""
-        if train_nodes is None:
-            tr.set_nodes(np.random.default_rng(epoch).permutation(n))
-        else:
-            tr.set_nodes(train_nodes[np.random.default_rng(epoch).permutation(train_nodes.shape[0])])
-        return tr.n_batches if a.max_steps <= 0 else min(a.max_steps, tr.n_batches)
-
+    if rank == 0 and g.fdtype != "float32":
+        print("feature table: %s, %d bytes on this rank" % (g.fdtype, tr.feat.numel() * tr.feat.element_size()))
     if a.resume is not None:
-        try:
-            was, _ = tr.load_checkpoint(a.resume)
-        except ValueError as ex:
-            raise SystemExit("--resume %s: %s" % (a.resume, ex))
-        # the sampler back to its position: the finished epochs through the slicer, nothing trained (DESIGN 4.12)
-        left = epochs_done < a.num_epochs        # (nothing to continue: nothing to replay)
-        replayed = 0
-        for e in range(epochs_done if left else 0):
-            steps = start_epoch(e)
-            tr.skip(steps)
-            replayed += steps
-        if rank == 0:
-            print("resumed from %s: epoch %d, %d steps" % (a.resume, epochs_done, tr.steps_done))
-            now = tr.checkpoint_fields()
-            odd = ["%s was %r, is %r" % (k, was[k], now[k]) for k in sorted(now)
-                   if k not in ("steps_done", "world") and k in was and was[k] != now[k]]
-            if left and replayed != tr.steps_done:
-                odd.append("the file holds %d steps, %d epochs of this command line are %d" % (tr.steps_done, epochs_done, replayed))
-            for line in odd:
-                print("resume: %s: the continuation will not be the uninterrupted run's" % line)
-            if not left:
-                print("resume: the file holds %d epochs and --num-epochs is %d: nothing is left to train"
-                      % (epochs_done, a.num_epochs))
-    for epoch in range(epochs_done, a.num_epochs):
-        steps = start_epoch(epoch)
-        t0 = time.time()
-        losses = tr.run(steps)
-        if rank == 0:
-            print("epoch %d: %d minibatches in %.2f s, loss %.4f -> %.4f" % (epoch, steps, time.time() - t0, losses[0], losses[-1]))
-        if a.save is not None and ((epoch + 1) % a.save_every == 0 or epoch + 1 == a.num_epochs):
-            tr.save_checkpoint(a.save, extra={"epoch": epoch + 1})
-        if eval_nodes is not None and ((epoch + 1) % max(a.eval_every, 1) == 0 or epoch + 1 == a.num_epochs):
-            t0 = time.time()
-            ev = tr.evaluate(eval_nodes)
-            if rank == 0:
-                # the key of the reference's trainers (pa_cache_multi_gpu.py:252)
-                if a.multilabel:
-                    print("Eval F1 %.4f | loss %.4f | %d nodes in %.2f s" % (ev["micro_f1"], ev["loss"], ev["n"], time.time() - t0))
-                else:
-                    print("Eval Acc %.4f | loss %.4f | %d nodes in %.2f s" % (ev["accuracy"], ev["loss"], ev["n"], time.time() - t0))
+        _resume(a, tr, epochs_done, train_nodes, rank)
+    _train_epochs(a, tr, epochs_done, train_nodes, eval_nodes, rank)
     if rank == 0:
         print(tr.report())
     tr.close()
