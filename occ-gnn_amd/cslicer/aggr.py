@@ -23,6 +23,7 @@ MULTILABEL_SYMBOLS = _abi.BOUND["cslicer_multilabel.h"]   # the sigmoid-BCE loss
 OPTIM_SYMBOLS = _abi.BOUND["cslicer_optim.h"]             # the optimizer step with weight decay, clipping and the non-finite guard
 GAT_DROPOUT_SYMBOLS = _abi.BOUND["cslicer_gat_dropout.h"]   # attention dropout: the dropped twins of the four aggregation calls
 LOSS_SYMBOLS = _abi.BOUND["cslicer_loss.h"]               # class weights and label smoothing: the loss pass and the native steps with it
+LAYERNORM_SYMBOLS = _abi.BOUND["cslicer_layernorm.h"]     # layer normalisation: the two row kernels and the native step with them
 EXCHANGE_FN, EXCHANGE_WAIT_FN = _abi.EXCHANGE_FN, _abi.EXCHANGE_WAIT_FN
 # element kinds of a 16-bit feature table (CSL_FEAT_F16 / CSL_FEAT_BF16); a float32 table has the fp32 entry points
 FEAT_KINDS = {torch.float16: 1, torch.bfloat16: 2}
@@ -430,6 +431,84 @@ class Dropout(torch.autograd.Function):
         return dropout(g if g.stride(-1) == 1 else g.contiguous(), ids, *ctx.cfg), None, None, None, None, None
 
 
+# Layer normalisation between the GraphSAGE layers (cslicer_layernorm.h): gamma and beta of every layer but
+# the last (float32 device tensors [hidden]) and eps.  None wherever a NormSpec is taken: no norm code runs.
+NormSpec = collections.namedtuple("NormSpec", "gammas betas eps")
+
+
+def _rows_f32(x, what):
+    if x.dtype != torch.float32 or not x.is_cuda or x.dim() != 2 or x.stride(1) != 1:
+        raise TypeError("%s: a float32 CUDA matrix with unit column stride expected" % what)
+    return x
+
+
+def layernorm_relu(z, gamma, beta, eps, relu=True, out=None, store=True):
+    """(y, xhat, rstd) = csl_layernorm_relu_fwd_f32: y = relu(gamma * xhat + beta) of the rows of z [n, H] (relu=False: no
+    ReLU), xhat = (z - mean) * rstd, rstd = 1 / sqrt(biased variance + eps).  out: the destination, z itself for the
+    in-place form (default: a fresh matrix).  store=False: the forward-only form of inference, xhat and rstd are None."""
+    z = _rows_f32(z, "z")
+    n, H = z.shape
+    y = torch.empty((n, H), dtype=torch.float32, device=z.device) if out is None else _rows_f32(out, "out")
+    if y.shape != z.shape or y.device != z.device:
+        raise ValueError("out must be a float32 matrix of z's shape with unit column stride")
+    xhat = torch.empty((n, H), dtype=torch.float32, device=z.device) if store else None
+    rstd = torch.empty((n,), dtype=torch.float32, device=z.device) if store else None
+    none = C.c_void_p(0)
+    _chk(_lib().csl_layernorm_relu_fwd_f32(_p(z), z.stride(0), _p(gamma), _p(beta), float(eps), n, H, _p(y), y.stride(0),
+                                           C.c_void_p(xhat.data_ptr()) if store else none, H,
+                                           C.c_void_p(rstd.data_ptr()) if store else none, 1 if relu else 0, _stream()),
+         "csl_layernorm_relu_fwd_f32")
+    return y, xhat, rstd
+
+
+def reduce_blocks(jobs):
+    """csl_reduce_multi_f32: for every (partial [blocks, H], dst [H]) of `jobs`, dst = the sum of partial's rows, in one
+    launch (the second stage of the two-stage column sums)"""
+    k = len(jobs)
+    src = (C.c_void_p * k)(*[p.data_ptr() for p, _ in jobs])
+    dst = (C.c_void_p * k)(*[d.data_ptr() for _, d in jobs])
+    nblk = (C.c_int64 * k)(*[p.shape[0] for p, _ in jobs])
+    H = (C.c_int32 * k)(*[p.shape[1] for p, _ in jobs])
+    _chk(_lib().csl_reduce_multi_f32(k, src, nblk, H, dst, _stream()), "csl_reduce_multi_f32")
+
+
+def layernorm_bwd(dn, xhat, rstd, gamma, n):
+    """csl_layernorm_bwd_f32 in place on dn [n_pad, H] (rows [n, n_pad) stay the zeros they are): rows < n become dz;
+    returns (dgamma [H], column sums of dz [H]), both stages of the two-stage sums run."""
+    dn = _rows_f32(dn, "dn")
+    n_pad, H = dn.shape
+    L = _lib()
+    blocks = max(int(L.csl_layernorm_bwd_scratch(n_pad, H)), 0) // H
+    part = torch.empty((2, max(blocks, 1), H), dtype=torch.float32, device=dn.device)
+    _chk(L.csl_layernorm_bwd_f32(_p(dn), dn.stride(0), _p(xhat), H, _p(rstd), _p(gamma), n, n_pad, H,
+                                 C.c_void_p(part[0].data_ptr()), C.c_void_p(part[1].data_ptr()), _stream()),
+         "csl_layernorm_bwd_f32")
+    sums = torch.zeros((2, H), dtype=torch.float32, device=dn.device)
+    if blocks:
+        reduce_blocks([(part[0, :blocks], sums[0]), (part[1, :blocks], sums[1])])
+    return sums[0], sums[1]
+
+
+class LayerNormRelu(torch.autograd.Function):
+    """relu(layer_norm(z) * gamma + beta) (relu=False: without the ReLU) as an autograd node over the two kernels.  Saved:
+    xhat, rstd, gamma and (for the mask) y.  The backward masks the gradient by y > 0 and takes its column sums (dbeta) in
+    csl_relu_bwd_colsum_f32's pass, then csl_layernorm_bwd_f32 turns it into dz in place and leaves dgamma."""
+
+    @staticmethod
+    def forward(ctx, z, gamma, beta, eps, relu=True):
+        y, xhat, rstd = layernorm_relu(z if z.stride(-1) == 1 else z.contiguous(), gamma, beta, eps, relu)
+        ctx.save_for_backward(xhat, rstd, gamma, y if relu else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        xhat, rstd, gamma, y = ctx.saved_tensors
+        n = xhat.shape[0]
+        dn, dbeta = relu_bwd_colsum(g, y, n, n)
+        dgamma, _ = layernorm_bwd(dn, xhat, rstd, gamma, n)
+        return dn, dgamma, dbeta, None, None
+
+
 # Dropout for the attention model (cslicer_gat_dropout.h; DESIGN 4.11): p_f on every hidden layer's output (cslicer_dropout.h's
 # mask), p_a on the normalised attention coefficients (inside the aggregation kernels), the run's seed, the step's counter.
 GatDropSpec = collections.namedtuple("GatDropSpec", "p_f p_a seed step")
@@ -535,6 +614,24 @@ class _SageNative(object):
         self.grads = torch.empty((n_grad,), dtype=torch.float32, device=ws[0].device)
         self._ws = None
         self._twins, self._need = _twins(self._stem), getattr(_lib(), self._workspace)
+        # a normalised model (DistSAGEModel(norm="layer")): gamma and beta of every layer but the last, their gradients behind
+        # the layers' own in the flat buffer -- the order of model.parameters()
+        self.norm = None
+        norms = getattr(model, "norms", None)
+        if norms is not None:
+            if self._stem != "sage_fwd_bwd":
+                raise TypeError("the native rank step has no layer normalisation")
+            gs, be = [m.gamma for m in norms], [m.beta for m in norms]
+            for k, t in enumerate(gs + be):
+                if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != (self.dims[k % len(gs) + 1],):
+                    raise TypeError("contiguous float32 CUDA gamma / beta [hidden] expected")
+            self.norm = NormSpec(gs, be, float(model.norm_eps))
+            self._gamma = (C.c_void_p * max(len(gs), 1))(*[t.data_ptr() for t in gs])     # (one layer: nothing to normalise)
+            self._beta = (C.c_void_p * max(len(be), 1))(*[t.data_ptr() for t in be])
+            self._params += gs + be
+            n_grad += sum(t.numel() for t in gs + be)
+            self.grads = torch.empty((n_grad,), dtype=torch.float32, device=ws[0].device)
+            self._need = _lib().csl_sage_fwd_bwd_norm_workspace
         gemm_load_plans()
 
     @staticmethod
@@ -600,6 +697,19 @@ class SageStep(_SageNative):
         rest = (feat.stride(0), slices[0].ptr(A.IN_NODES), slices[-1].ptr(A.OUT_NODES), labels.data_ptr(),
                 *((labels.stride(0),) if multi else lossw), float(scale), self.row_pad, self.n_slabs, self.grads.data_ptr(),
                 loss_out.data_ptr(), self._ws.data_ptr(), self._ws.numel())
+        if self.norm is not None:
+            # csl_sage_fwd_bwd_norm: csl_sage_fwd_bwd_ce's arguments, then the packed label words (multi-label), gamma, beta, eps
+            ids = None
+            if drop is not None:
+                ids = (C.c_void_p * max(self.L - 1, 1))(*[s.ptr(A.OUT_NODES) for s in slices[:self.L - 1]])
+            fn = _lib().csl_sage_fwd_bwd_norm
+            self._chk(fn(*upto_table, kind or 0, feat.stride(0), slices[0].ptr(A.IN_NODES), slices[-1].ptr(A.OUT_NODES),
+                         None if multi else labels.data_ptr(), *(lossw or (None, 0.0)), float(scale), self.row_pad, self.n_slabs,
+                         self.grads.data_ptr(), loss_out.data_ptr(), self._ws.data_ptr(), self._ws.numel(), ids,
+                         float(drop.p) if drop is not None else 0.0, _i64(drop.seed) if drop is not None else 0,
+                         _i64(drop.step) if drop is not None else 0, labels.data_ptr() if multi else None,
+                         labels.stride(0) if multi else 0, self._gamma, self._beta, self.norm.eps, _stream()), fn.__name__)
+            return
         if not multi and drop is None and loss is None:
             # a 16-bit table (float16 / bfloat16) goes to the step's _x16 twin: only its deepest layer's forward differs
             _table_call(self._twins, kind, upto_table, rest + (_stream(),), self._chk)

@@ -6,13 +6,14 @@ lr_schedule is not stored) -- so reading one never runs code of the file's:
 
     format      "cslicer-checkpoint"
     version     1
-    model       kind ("sage" / "gat"), in_feats, hidden, n_classes, heads, n_layers, multilabel: what build_model needs
+    model       kind ("sage" / "gat"), in_feats, hidden, n_classes, heads, n_layers, multilabel: what build_model needs;
+                a normalised GraphSAGE model adds norm ("layer") and norm_eps, any other has neither key
     state       model.state_dict(), on the CPU
     optimizer   aggr.Adam.state_dict(): t, lr, betas, eps, weight_decay (per tensor), decoupled, max_grad_norm, the two
                 moments per parameter (m, v: lists in parameter order), skipped; None for a file written from a bare model
     trainer     what the run was built with and where it stands (Trainer.checkpoint_fields): steps_done, seed, dropout_seed,
                 rng_seed, fanouts, batch, streams, replace, world, feature_dtype, dropout, feat_dropout, attn_dropout,
-                edge_weighted; None for a bare model
+                edge_weighted, and norm where the model is normalised; None for a bare model
     extra       the caller's own plain values (the command line stores {"epoch": epochs done})
 
 Nothing in it depends on the number of ranks: the weights are replicated on every path, so a file written by rank 0 of 4
@@ -31,6 +32,7 @@ from . import splitgnn
 FORMAT, VERSION = "cslicer-checkpoint", 1
 # the `model` block, in the order a mismatch is reported
 MODEL_FIELDS = ("kind", "in_feats", "hidden", "n_classes", "heads", "n_layers", "multilabel")
+NORM_FIELDS = ("norm", "norm_eps")      # a normalised model's; absent from every other block
 _PLAIN = (type(None), bool, int, float, str)
 
 
@@ -40,8 +42,11 @@ def model_block(model, multilabel=False):
     L = len(model.convs)
     first = model.convs[0]
     if isinstance(model, splitgnn.DistSAGEModel):
-        return {"kind": "sage", "in_feats": first.fc.in_features // 2, "hidden": first.fc.out_features if L > 1 else 0,
-                "n_classes": model.convs[-1].fc.out_features, "heads": 0, "n_layers": L, "multilabel": bool(multilabel)}
+        block = {"kind": "sage", "in_feats": first.fc.in_features // 2, "hidden": first.fc.out_features if L > 1 else 0,
+                 "n_classes": model.convs[-1].fc.out_features, "heads": 0, "n_layers": L, "multilabel": bool(multilabel)}
+        if model.norm is not None:       # (a model without norm keeps exactly the keys it has always had)
+            block.update(norm=model.norm, norm_eps=float(model.norm_eps))
+        return block
     if isinstance(model, splitgnn.DistGATModel):
         return {"kind": "gat", "in_feats": first.fc.in_features, "hidden": first.D if L > 1 else 0,
                 "n_classes": int(model.n_classes), "heads": int(model.heads), "n_layers": L, "multilabel": bool(multilabel)}
@@ -51,7 +56,9 @@ def model_block(model, multilabel=False):
 def build_model(block):
     """a fresh model (CPU, its own initial weights) of the architecture a `model` block records"""
     if block["kind"] == "sage":
-        return splitgnn.DistSAGEModel(block["in_feats"], block["hidden"], block["n_classes"], n_layers=block["n_layers"])
+        # (a one-layer model records hidden = 0: nothing is normalised there, whatever `norm` says)
+        return splitgnn.DistSAGEModel(block["in_feats"], block["hidden"], block["n_classes"], n_layers=block["n_layers"],
+                                      norm=block.get("norm"), norm_eps=block.get("norm_eps", 1e-5))
     if block["kind"] == "gat":
         return splitgnn.DistGATModel(block["in_feats"], block["hidden"], block["n_classes"], heads=block["heads"],
                                      n_layers=block["n_layers"])
@@ -59,10 +66,11 @@ def build_model(block):
 
 
 def check_model(block, own, what="the trainer"):
-    """ValueError naming the first field of MODEL_FIELDS in which the file's `model` block differs from `own`"""
-    for k in MODEL_FIELDS:
-        if block[k] != own[k]:
-            raise ValueError("checkpoint: the file's model has %s = %r, %s has %r" % (k, block[k], what, own[k]))
+    """ValueError naming the first field of MODEL_FIELDS -- then norm, norm_eps (absent: None) -- in which the file's `model`
+    block differs from `own`"""
+    for k in MODEL_FIELDS + NORM_FIELDS:
+        if block.get(k) != own.get(k):
+            raise ValueError("checkpoint: the file's model has %s = %r, %s has %r" % (k, block.get(k), what, own.get(k)))
 
 
 def _check_plain(v, where):

@@ -330,27 +330,49 @@ def _sage_operands(conv, hp, dev):
     return False, wp, bp
 
 
-def _sage_layer(g, dplan, h, conv, relu, chunk_rows):
+def _layer_norm(model, k):
+    """(gamma, beta, eps) of a normalised GraphSAGE model's layer k, None for every other layer and model"""
+    if getattr(model, "norm", None) is None or k + 1 >= len(model.convs):
+        return None
+    m = model.norms[k]
+    return m.gamma.detach(), m.beta.detach(), model.norm_eps
+
+
+def _norm_rows(y, norm):
+    """a finished chunk of a normalised layer's rows: relu(gamma * layer_norm(y) + beta) in place, forward-only
+    (csl_layernorm_relu_fwd_f32 without xhat / rstd).  The layer's own kernels ran with their ReLU off."""
+    if norm is not None and y.shape[0]:
+        aggr.layernorm_relu(y, norm[0], norm[1], norm[2], relu=True, out=y, store=False)
+
+
+def _sage_layer(g, dplan, h, conv, relu, chunk_rows, norm=None):
     """One DistSageConv over the rows of `dplan`; h: [N, hp] table (hp % 4 == 0, padding columns zero; float32, or the
     first layer's feature table in its stored 16-bit type, row stride h.stride(0)).  Aggregate first when out >= in,
-    project first otherwise.  Returns the [rows, round4(out)] float32 table (padding columns zero)."""
+    project first otherwise.  norm: _layer_norm's tuple: the layer's kernels run without their ReLU and every finished
+    chunk of rows is normalised in place (a normalised width is a multiple of 4: no padding columns).
+    Returns the [rows, round4(out)] float32 table (padding columns zero)."""
     dev = h.device
     agg_first, w, b = _sage_operands(conv, h.shape[1], dev)
     out_w = conv.fc.weight.shape[0]
     hp, op = h.shape[1], _r4(out_w)
     n_rows = dplan.plan["n"]
+    relu = relu and norm is None
     if agg_first:
         # (a) [h[v] | mean h[u]] chunk by chunk, then the Linear with its bias / ReLU epilogue into the output table
         y = torch.zeros((n_rows, op), dtype=torch.float32, device=dev)
         cat = torch.empty((min(chunk_rows, max(n_rows, 1)), 2 * hp), dtype=torch.float32, device=dev)
-        sage_rows(g, dplan, h, h.stride(0), hp, False, None, False, lambda k0, k1: cat[:k1 - k0], chunk_rows,
-                  scratch=lambda k0, k1, c: _gemm_into(y[k0:k1, :out_w], c, w, b, relu))
+
+        def finish(k0, k1, c):
+            _gemm_into(y[k0:k1, :out_w], c, w, b, relu)
+            _norm_rows(y[k0:k1], norm)
+        sage_rows(g, dplan, h, h.stride(0), hp, False, None, False, lambda k0, k1: cat[:k1 - k0], chunk_rows, scratch=finish)
         return y
     # (b) P = h . [W_self; W_neigh]^T once for every node, then act(P[v, :out] + mean P[u, out:] + b) in one pass
     P = torch.empty((g.N, 2 * op), dtype=torch.float32, device=dev)
     _project_rows(h, w, P, chunk_rows)
     y = torch.empty((n_rows, op), dtype=torch.float32, device=dev)
-    sage_rows(g, dplan, P, 2 * op, op, True, b, relu, y, chunk_rows)
+    sage_rows(g, dplan, P, 2 * op, op, True, b, relu, y, chunk_rows,
+              scratch=None if norm is None else (lambda k0, k1, dst: _norm_rows(dst, norm)))
     return y
 
 
@@ -601,7 +623,7 @@ def full_inference(model, indptr, indices, features, nodes=None, chunk_rows=CHUN
             last = k + 1 == L
             dplan = dlast if last else g.all_rows
             if isinstance(model, splitgnn.DistSAGEModel):
-                h = _sage_layer(g, dplan, h, conv, not last, chunk_rows)
+                h = _sage_layer(g, dplan, h, conv, not last, chunk_rows, _layer_norm(model, k))
             else:
                 h, in_map = _gat_layer(g, dplan, h, in_map, conv, last, model.n_classes, chunk_rows)
         return _class_columns(model, h)
@@ -877,11 +899,13 @@ def _buffer_rows(pp):
             max([c.n_parts for c in ch] + [1]))
 
 
-def _sage_layer_parts(pp, dp, h, conv, relu, comm):
+def _sage_layer_parts(pp, dp, h, conv, relu, comm, norm=None):
     """One DistSageConv over the rank's destinations of `pp`; h: [n_own, hp] own rows (float32, or the first layer's
     feature rows in their stored 16-bit type: the aggregate-first kernels read them in place, the projection through
-    _RowChunks).  Returns [m, round4(out)]."""
+    _RowChunks).  norm: as _sage_layer's, over the rank's own rows (the norm is row-wise: any partition gives the same
+    numbers).  Returns [m, round4(out)]."""
     L, st, dev, kind = _lib(), aggr._stream(), h.device, _kind(h)
+    relu = relu and norm is None
     part_twins, merge_twins = aggr._twins("infer_sage_part"), aggr._twins("infer_sage_merge")
     agg_first, w, b = _sage_operands(conv, h.shape[1], dev)
     out_w = conv.fc.weight.shape[0]
@@ -914,6 +938,7 @@ def _sage_layer_parts(pp, dp, h, conv, relu, comm):
         else:
             _chk(L.csl_infer_sage_merge_f32(*merge, _ptr(Y), 2 * op, op, 1, _ptr(b), int(relu), _ptr(y, c.o0 * op), op, st),
                  "csl_infer_sage_merge_f32")
+        _norm_rows(y[c.o0:c.o1], norm)
     return y
 
 
@@ -1047,7 +1072,7 @@ def full_inference_parts(model, indptr, indices, features_own, comm, owner=None,
             if gat:
                 h, in_map = _gat_layer_parts(pp, dp, h, in_map, conv, last, model.n_classes, comm)
             else:
-                h = _sage_layer_parts(pp, dp, h, conv, not last, comm)
+                h = _sage_layer_parts(pp, dp, h, conv, not last, comm, _layer_norm(model, k))
         return _class_columns(model, h)
 
 

@@ -290,34 +290,41 @@ class _SageModelLocal(torch.autograd.Function):
     GEMM and the fused gather for k > 0).  The deepest layer reads the resident feature table through its slice's
     in_nodes.  Arguments: feat table, n_layers, drop (an aggr.DropSpec or None), then per layer (weight, bias, Slice) in
     model order (deepest first).  With drop, every hidden y is dropped in place by its out-node ids (aggr.dropout): the
-    saved y then carries relu' * mask, and the backward multiplies what it hands down by s = 1 / (1 - p) per layer."""
+    saved y then carries relu' * mask, and the backward multiplies what it hands down by s = 1 / (1 - p) per layer.
+    A normalised model passes its eps as `norm_eps` (else None) and, behind the layers' arguments, gamma_k and
+    beta_k of every layer but the last: the hidden GEMMs run without their ReLU, aggr.layernorm_relu runs in place on y and
+    the backward's aggr.layernorm_bwd turns the masked gradient into the GEMM's, as the native step does."""
 
     @staticmethod
-    def forward(ctx, feat, n_layers, drop, *args):
-        ws, bs, sls = args[0::3], args[1::3], args[2::3]
+    def forward(ctx, feat, n_layers, drop, norm_eps, *args):
+        ws, bs, sls = args[0:3 * n_layers:3], args[1:3 * n_layers:3], args[2:3 * n_layers:3]
+        gbs = args[3 * n_layers:]
         x, rowmap = feat, sls[0].in_nodes
-        cats, ys = [], []
+        cats, ys, stats = [], [], []
         for k in range(n_layers):
             sl = sls[k]
             m, mp = sl.n_out, _pad_rows(sl.n_out)
             cat = aggr.sage_cat(x, sl.self_ids_in, m, mp, indptr=sl.indptr, indices=sl.indices, rowmap=rowmap)
-            y = _linear_act(bs[k], cat, ws[k], k + 1 < n_layers)
+            y = _linear_act(bs[k], cat, ws[k], k + 1 < n_layers and norm_eps is None)
+            if norm_eps is not None and k + 1 < n_layers:
+                stats += aggr.layernorm_relu(y[:m], gbs[2 * k], gbs[2 * k + 1], norm_eps, out=y[:m])[1:]
             if drop is not None and k + 1 < n_layers:
                 aggr.dropout(y[:m], sl.out_nodes, drop.p, drop.seed, k, drop.step, out=y[:m])
             cats.append(cat)
             ys.append(y)
             x, rowmap = y[:m], None
-        ctx.n_layers, ctx.sls = n_layers, sls
+        ctx.n_layers, ctx.sls, ctx.normed = n_layers, sls, norm_eps is not None
         ctx.drop_scale = None if drop is None else aggr.dropout_scale(drop.p)
-        ctx.save_for_backward(*ws, *cats, *ys)
+        ctx.save_for_backward(*ws, *cats, *ys, *gbs[0::2], *stats)
         return x
 
     @staticmethod
     def backward(ctx, g):
         L, sls = ctx.n_layers, ctx.sls
         t = ctx.saved_tensors
-        ws, cats, ys = t[:L], t[L:2 * L], t[2 * L:]
-        grads = [None] * (3 * L)
+        ws, cats, ys = t[:L], t[L:2 * L], t[2 * L:3 * L]
+        gammas, stats = t[3 * L:4 * L - 1], t[4 * L - 1:]          # (a normalised model's; else empty)
+        grads = [None] * (3 * L + (2 * (L - 1) if ctx.normed else 0))
         top = sls[L - 1]
         gyp, gb = aggr.relu_bwd_colsum(g, None, top.n_out, cats[L - 1].shape[0])   # padding + bias sums (no mask)
         for k in range(L - 1, -1, -1):
@@ -331,7 +338,12 @@ class _SageModelLocal(torch.autograd.Function):
                                           cats[k - 1].shape[0], hub=sl.t_max_len > _abi.T_SORTED_MAX)
             if ctx.drop_scale is not None:
                 gyp, gb = gyp.mul_(ctx.drop_scale), gb * ctx.drop_scale
-        return (None, None, None) + tuple(grads)
+            if ctx.normed:
+                # gyp is the masked gradient w.r.t. the normalised rows and gb its column sums (dbeta): into dz, in place
+                grads[3 * L + 2 * (k - 1) + 1] = gb
+                grads[3 * L + 2 * (k - 1)], gb = aggr.layernorm_bwd(gyp, stats[2 * (k - 1)], stats[2 * (k - 1) + 1], gammas[k - 1],
+                                                                    sl.n_in)
+        return (None, None, None, None) + tuple(grads)
 
 
 class DistSageConv(nn.Module):
@@ -391,14 +403,43 @@ class DistSageConv(nn.Module):
         return self.fc(cat)
 
 
+class RowNorm(nn.Module):
+    """gamma (ones) and beta (zeros) of one layer normalisation"""
+
+    def __init__(self, width):
+        super().__init__()
+        self.gamma = nn.Parameter(torch.ones(width))
+        self.beta = nn.Parameter(torch.zeros(width))
+
+
 class DistSAGEModel(nn.Module):
     """models/factory.py:7-56: n_layers DistSageConv, ReLU between, weights replicated on every part."""
 
-    def __init__(self, in_feats, hidden, n_classes, n_layers=3):
+    def __init__(self, in_feats, hidden, n_classes, n_layers=3, norm=None, norm_eps=1e-5):
+        """norm: None, or "layer": layer normalisation of every layer's result but the last, before its ReLU (SAGEConv's
+        `norm`).  gamma_k and beta_k are registered behind the layers' own parameters, so that the order of
+        parameters() is the native step's gradient layout W_0, b_0, ..., gamma_0, beta_0, gamma_1, ..."""
         super().__init__()
+        if norm not in (None, "layer"):
+            raise ValueError("norm must be None or 'layer', not %r" % (norm,))
+        if norm is not None and not float(norm_eps) > 0:
+            raise ValueError("norm_eps must be > 0, not %r" % (norm_eps,))
+        if norm is not None and n_layers > 1 and hidden % 4 != 0:
+            raise ValueError("norm: hidden must be a multiple of 4 (the kernels move float4 columns), not %d" % hidden)
         dims = [in_feats] + [hidden] * (n_layers - 1) + [n_classes]
         # convs[k] consumes engine layer n_layers-1-k (the deepest hop first)
         self.convs = nn.ModuleList([DistSageConv(dims[k], dims[k + 1]) for k in range(n_layers)])
+        self.norm, self.norm_eps = norm, float(norm_eps)
+        if norm is not None:      # (a model without norm has no such attribute: its parameters and state keys are unchanged)
+            self.norms = nn.ModuleList([RowNorm(hidden) for _ in range(n_layers - 1)])
+
+    def _normed(self, k):
+        return self.norm is not None and k + 1 < len(self.convs)
+
+    def _norm(self, k, x):
+        """relu(layer_norm(x) * gamma_k + beta_k) of the rows a part holds (aggr.LayerNormRelu): a function of one row, so
+        any partition gives the same numbers"""
+        return aggr.LayerNormRelu.apply(x, self.norms[k].gamma, self.norms[k].beta, self.norm_eps, True)
 
     @staticmethod
     def _drop(drop, sl, x, k, owned):
@@ -417,8 +458,11 @@ class DistSAGEModel(nn.Module):
         for k, conv in enumerate(self.convs):
             sl = slices[L - 1 - k]
             hidden = k + 1 < len(self.convs)
+            normed = self._normed(k)
             if len(parts) == 1 and sl[parts[0]].n_parts == 1 and not _NO_LOCAL_FUSE and x[parts[0]].shape[1] % 4 == 0:
-                x = {parts[0]: conv.layer_local(sl[parts[0]], x[parts[0]], hidden)}
+                x = {parts[0]: conv.layer_local(sl[parts[0]], x[parts[0]], hidden and not normed)}
+                if normed:
+                    x = {parts[0]: self._norm(k, x[parts[0]])}
                 if drop is not None and hidden:
                     x = {parts[0]: self._drop(drop, sl[parts[0]], x[parts[0]], k, False)}
                 continue
@@ -426,7 +470,9 @@ class DistSAGEModel(nn.Module):
             send = {g: conv.boundary(sl[g], agg[g]) for g in parts}
             for g in parts:
                 agg[g] = conv.merge(sl[g], agg[g], [send[p][g] if p != g else None for p in parts])
-            x = {g: conv.finish_fused(sl[g], agg[g], x[g], hidden) for g in parts}
+            x = {g: conv.finish_fused(sl[g], agg[g], x[g], hidden and not normed) for g in parts}
+            if normed:
+                x = {g: self._norm(k, x[g]) for g in parts}
             if drop is not None and hidden:
                 x = {g: self._drop(drop, sl[g], x[g], k, True) for g in parts}
         return x
@@ -440,10 +486,15 @@ class DistSAGEModel(nn.Module):
             args = []
             for k, conv in enumerate(self.convs):
                 args += [conv.fc.weight, conv.fc.bias, slices[L - 1 - k][part]]
-            return _SageModelLocal.apply(feat_table, L, drop, *args)
+            if self.norm is not None:
+                for m in self.norms:
+                    args += [m.gamma, m.beta]
+            return _SageModelLocal.apply(feat_table, L, drop, self.norm_eps if self.norm is not None else None, *args)
         x, rowmap = feat_table, slices[L - 1][part].in_nodes
         for k, conv in enumerate(self.convs):
-            x = conv.layer_local(slices[L - 1 - k][part], x, k + 1 < len(self.convs), rowmap)
+            x = conv.layer_local(slices[L - 1 - k][part], x, k + 1 < len(self.convs) and not self._normed(k), rowmap)
+            if self._normed(k):
+                x = self._norm(k, x)
             if drop is not None and k + 1 < len(self.convs):
                 x = self._drop(drop, slices[L - 1 - k][part], x, k, False)
             rowmap = None
@@ -460,7 +511,10 @@ class DistSAGEModel(nn.Module):
             # aggregation + boundary exchange + merge of a layer are ONE autograd node (`_RankAggregate`): 5 launches
             # forward whatever the number of peers (the op chain local / boundary / merge of forward_parts is
             # 2 + 2 (P - 1) launches and as many autograd nodes)
-            x = conv.finish_fused(sl, _RankAggregate.apply(x, sl, comm, bool(overlap)), x, k + 1 < len(self.convs))
+            x = conv.finish_fused(sl, _RankAggregate.apply(x, sl, comm, bool(overlap)), x,
+                                  k + 1 < len(self.convs) and not self._normed(k))
+            if self._normed(k):
+                x = self._norm(k, x)
             if drop is not None and k + 1 < len(self.convs):
                 x = self._drop(drop, sl, x, k, True)
         return x

@@ -80,7 +80,7 @@ def step_plan(kind, world, rank_path, n_layers, F, hidden, n_classes, heads, fan
     trainer's probability -- above 0 the rank path runs its autograd step (the native rank sequencer has no dropout), with
     the engine flags that step has always asked for; every other row is what it is at 0.  multilabel: the trainer's --
     the native rank sequencer has no sigmoid-BCE loss either, so with True its row moves the same way and no other does.
-    (The attention model's dropout: step_plan_gat_drop below.)"""
+    (The attention model's dropout: step_plan_gat_drop below; layer normalisation: step_plan_norm.)"""
     sage, gat = kind == "sage", kind == "gat"
     single = not rank_path and world == 1      # one part in one process, no collective
     want = table_f32 if gat_input is None else gat_input     # (None: a 16-bit table keeps the numbers its runs have had)
@@ -143,6 +143,17 @@ def step_plan_gat_drop(feat_dropout=0.0, attn_dropout=0.0, *, kind, gat_input, *
 # order the constructor calls them (of two bad arguments the earlier group's error is raised): pure -- numpy and
 # _abi.noreplace_max_fanout() only, no device, no engine -- and each returns its arguments normalised.
 
+def step_plan_norm(norm=None, **cfg):
+    """step_plan_gat_drop(**cfg) under the trainer's `norm` (None / "layer"); with None it IS that plan.  The
+    native rank sequencer has no layer normalisation, as it has no dropout: with norm="layer" the row that `dropout` moves
+    (`native_rank` -> the rank's autograd step, planned as CSLICER_PY_STEP plans it, engine flags included) moves the same
+    way, and no other row does."""
+    plan = step_plan_gat_drop(**cfg)
+    if norm is None or plan.path != "native_rank":
+        return plan
+    return step_plan_gat_drop(**dict(cfg, sw=cfg.get("sw", Switches())._replace(py_step=True)))
+
+
 def _check_labels(labels, multilabel, num_nodes, n_classes):
     """multilabel as a bool; with it, a host `labels` (a callable's rows are checked when they are loaded) must be a
     [num_nodes, n_classes] matrix of 0 / 1"""
@@ -180,6 +191,20 @@ def _check_dropouts(model, hidden, dropout, feat_dropout, attn_dropout, gat_inpu
         raise ValueError("attn_dropout > 0 with gat_input=True: the aggregate-then-project input layer has no attention "
                          "dropout (gat_input=None turns it off)")
     return dropout, feat_dropout, attn_dropout
+
+
+def _check_norm(model, hidden, n_layers, norm, norm_eps):
+    """(norm, norm_eps): None or "layer", and eps as a float > 0"""
+    if norm not in (None, "layer"):
+        raise ValueError("norm must be None or 'layer', not %r" % (norm,))
+    norm_eps = float(norm_eps)
+    if not norm_eps > 0:
+        raise ValueError("norm_eps must be > 0, not %r" % (norm_eps,))
+    if norm is not None and model == "gat":
+        raise ValueError("norm: the attention model has no normalisation layer (model='sage' only)")
+    if norm is not None and hidden % 4 != 0:
+        raise ValueError("norm: hidden must be a multiple of 4 (the kernels move float4 columns), not %d" % hidden)
+    return norm, norm_eps
 
 
 def _check_optimizer(weight_decay, max_grad_norm, lr_schedule):
@@ -319,7 +344,7 @@ class Trainer(object):
                  feature_dtype="float32", gat_input=None, replace=True, dropout=0.0, dropout_seed=None,
                  multilabel=False, weight_decay=0.0, decoupled_weight_decay=True, decay_bias=False, max_grad_norm=None,
                  lr_schedule=None, class_weight=None, label_smoothing=0.0, feat_dropout=0.0, attn_dropout=0.0,
-                 edge_weight=None):
+                 edge_weight=None, norm=None, norm_eps=1e-5):
         """Part `rank` of `world`.  Ownership = the engine's workload table (`workload` int32 [N], the METIS map of
         python/utils/sampler.py:64-134 / partition_map_opt.bin; None = v % world like pyfrontend.cpp:57): the rank
         keeps the feature and label rows of the nodes it owns, in ascending node order.
@@ -355,6 +380,13 @@ class Trainer(object):
         include/cslicer_dropout.h -- with the step counted by `self.steps_done`, so that a node's mask never repeats
         across epochs and is the same on one GPU and on any number of ranks; dropout_seed=None takes `seed`.  0 (default)
         runs no dropout code at all; evaluate() / predict() never drop (inverted scaling makes inference the identity).
+
+        norm: None (default) or "layer": layer normalisation of every GraphSAGE layer's result but the last, before its ReLU
+        and dropout (SAGEConv's `norm`; torch.nn.LayerNorm over the hidden width, biased variance, norm_eps inside the root;
+        DESIGN 4.13, include/cslicer_layernorm.h).  gamma_k (ones) and beta_k (zeros) are parameters behind the layers' own;
+        they are clipped and all-reduced like every other and never weight-decayed, not even with decay_bias=True.  A
+        function of one node's row only: the same numbers on one GPU and on any number of ranks, and evaluate() / predict()
+        normalise with the same kernel.  GraphSAGE only, hidden % 4 == 0.  None runs none of that code.
 
         multilabel: False (default): one class per node, `labels` int [N], softmax cross-entropy.  True: a node carries a
         SET of classes (PPI, ogbn-proteins, Yelp, Amazon): `labels` is a host array [N, n_classes] of 0 / 1 (bool or
@@ -424,6 +456,7 @@ class Trainer(object):
         self.n_classes = int(n_classes)
         self.multilabel = _check_labels(labels, multilabel, N, n_classes)
         dropout, feat_dropout, attn_dropout = _check_dropouts(model, hidden, dropout, feat_dropout, attn_dropout, gat_input)
+        self.norm, self.norm_eps = _check_norm(model, hidden, len(fanouts), norm, norm_eps)
         weight_decay, max_grad_norm = _check_optimizer(weight_decay, max_grad_norm, lr_schedule)
         label_smoothing, class_weight = _check_loss(label_smoothing, class_weight, self.n_classes, self.multilabel)
         edge_weight = _check_sampling(edge_weight, replace, fanouts, np.shape(indices)[0])
@@ -457,11 +490,11 @@ class Trainer(object):
         F = f_own.shape[1] if feat_dim is None else feat_dim
         # -- 3. how this configuration trains, 4. the engine it needs.  One process per part: only this rank's slices are
         # materialised (the sampling itself is replicated)
-        self.plan = step_plan_gat_drop(feat_dropout, attn_dropout, kind=model, world=world, rank_path=self.rank_path,
-                                       n_layers=self.L, F=F, hidden=hidden, n_classes=n_classes, heads=heads,
-                                       fanout=fanouts[-1], table_f32=fdt == torch.float32, gat_input=gat_input,
-                                       replace=replace, sw=sw, width_known=F_early is not None, dropout=dropout,
-                                       multilabel=self.multilabel)
+        self.plan = step_plan_norm(self.norm, feat_dropout=feat_dropout, attn_dropout=attn_dropout, kind=model, world=world,
+                                   rank_path=self.rank_path, n_layers=self.L, F=F, hidden=hidden, n_classes=n_classes,
+                                   heads=heads, fanout=fanouts[-1], table_f32=fdt == torch.float32, gat_input=gat_input,
+                                   replace=replace, sw=sw, width_known=F_early is not None, dropout=dropout,
+                                   multilabel=self.multilabel)
         self.gat_input, self.replace = self.plan.gat_input, bool(replace)
         self.edge_weighted = edge_weight is not None
         cdf = l0.edge_cdf(indptr, edge_weight) if self.edge_weighted else None
@@ -491,14 +524,18 @@ class Trainer(object):
         torch.manual_seed(seed)      # identical replicated weights on every rank
         self.kind = model
         if model == "sage":
-            self.model = splitgnn.DistSAGEModel(F, hidden, n_classes, n_layers=self.L).to(self.dev)
+            norm_kw = {} if self.norm is None else {"norm": self.norm, "norm_eps": self.norm_eps}
+            self.model = splitgnn.DistSAGEModel(F, hidden, n_classes, n_layers=self.L, **norm_kw).to(self.dev)
         else:
             self.model = splitgnn.DistGATModel(F, hidden, n_classes, heads=heads, n_layers=self.L).to(self.dev)
         # -- 6. torch.optim.Adam's update in one HIP launch per step (the library's for-each form is eight small
         # launches, ~0.1 ms of GPU time per step; its fused form one of 42 us for these six small tensors)
         params = list(self.model.parameters())
+        # (a normalised model's gamma and beta are never decayed, not even with decay_bias)
+        undecayed = {id(p) for m in getattr(self.model, "norms", ()) for p in m.parameters()}
         self.opt = aggr.Adam(params, lr=lr, decoupled=bool(decoupled_weight_decay), max_grad_norm=max_grad_norm,
-                             weight_decay=[weight_decay if (decay_bias or p.dim() >= 2) else 0.0 for p in params])
+                             weight_decay=[weight_decay if (decay_bias or p.dim() >= 2) and id(p) not in undecayed else 0.0
+                                           for p in params])
         # data-parallel replicas: called with the flat gradient, sums it over the ranks' shares of the minibatch
         self.grad_sync = None
         # rank path, autograd step: called with the flat gradient right after its all-reduce (what the optimizer applies)
@@ -875,7 +912,7 @@ class Trainer(object):
                 "rng_seed": self.rng_seed, "fanouts": list(self.fanouts), "batch": int(self.B), "streams": int(self.S),
                 "replace": self.replace, "world": int(self.world), "feature_dtype": self.feature_dtype,
                 "dropout": self.dropout, "feat_dropout": self.feat_dropout, "attn_dropout": self.attn_dropout,
-                "edge_weighted": self.edge_weighted}
+                "edge_weighted": self.edge_weighted, **({} if self.norm is None else {"norm": self.norm})}
 
     def _checkpoint_peers(self):
         """(whether this process writes the file, the torch.distributed module to meet the others at, or None)"""
@@ -1096,6 +1133,10 @@ def _parser():
     ap.add_argument("--attn-dropout", type=float, default=None,
                     help="(extra) --model-name gat: dropout on the normalised attention coefficients "
                          "(`Trainer(attn_dropout=...)`); --gat-input auto then turns the input layer off")
+    ap.add_argument("--norm", choices=("layer",), default=None,
+                    help="(extra) layer normalisation of every GraphSAGE layer's result but the last, before its ReLU "
+                         "(`Trainer(norm='layer')`)")
+    ap.add_argument("--norm-eps", type=float, default=None, metavar="E", help="(extra) --norm: eps inside the root (default 1e-5)")
     ap.add_argument("--max-steps", type=int, default=0, help="(extra) stop an epoch after this many minibatches")
     ap.add_argument("--partition", choices=("mod", "file"), default="mod",
                     help="(extra) node ownership: `mod` = v %% world (pyfrontend.cpp:57), `file` = the L0 directory's "
@@ -1313,6 +1354,10 @@ def _trainer_kw(a, g, train_nodes, steps_per_epoch, edge_weight):
         kw["feat_dropout"] = a.feat_dropout
     if a.attn_dropout is not None:
         kw["attn_dropout"] = a.attn_dropout
+    if a.norm is not None:
+        kw["norm"] = a.norm
+    if a.norm_eps is not None:
+        kw["norm_eps"] = a.norm_eps
     kw.update(_loss_kw(a, g.labels, train_nodes, g.indptr.shape[0] - 1, g.n_classes))
     if edge_weight is not None:
         kw["edge_weight"] = edge_weight
@@ -1389,6 +1434,8 @@ def main(argv=None):
     (cslicer.l0), a preset name (arxiv-like, products-like, papers-like) or `synthetic`.
     --dropout: `Trainer(dropout=...)`, between the GraphSAGE layers as models/factory.py:41 applies it (the default, 0,
     runs none; the attention model refuses a value above 0).
+    --norm layer [--norm-eps E] (extra): `Trainer(norm="layer", norm_eps=E)`: layer normalisation of every GraphSAGE layer's
+    result but the last, before its ReLU and dropout; without it no norm code runs; the attention model refuses it.
     --feat-dropout P, --attn-dropout P (extra): `Trainer(feat_dropout=P)`, `Trainer(attn_dropout=P)`, --model-name gat only:
     dropout on every hidden attention layer's output (after its ELU) and on the normalised attention coefficients (DESIGN
     4.11); both keyed by the run's seed and the step.  --attn-dropout above 0 takes the deepest layer off the
@@ -1448,6 +1495,7 @@ def main(argv=None):
         python -m cslicer.train --graph products-like --multilabel --eval-split holdout --max-steps 50
         python -m cslicer.train --graph products-like --edge-weight inv-degree --eval-split holdout --max-steps 50
         python -m cslicer.train --graph products-like --dropout 0.5 --weight-decay 5e-4 --clip-grad-norm 1 --lr-warmup 100 --lr-schedule cosine
+        python -m cslicer.train --graph products-like --norm layer --dropout 0.5 --lr-warmup 100 --lr-schedule cosine
         python -m cslicer.train --graph <L0 dir> --feature-dtype bfloat16 --eval-split holdout
         python -m cslicer.train --graph products-like --model-name gat --feature-dtype bfloat16 --gat-input on
         python -m cslicer.train --graph products-like --model-name gat --feat-dropout 0.6 --attn-dropout 0.6 --eval-split holdout"""

@@ -1,7 +1,7 @@
 // sage_step.hip -- forward, loss and backward of the GraphSAGE model for one minibatch as ONE call behind the C ABI: the
 // sequence of this library's fused kernels and plain GEMMs that python/train.py:56-88 + python/layers/dist_sageconv.py:42-84
-// amount to, on ONE part that holds every node (cslicer_aggr.h: csl_sage_fwd_bwd_f32, its _x16, _dropout, _multilabel and
-// _ce forms) and on one RANK of the split-parallel job (csl_sage_rank_fwd_bwd_f32 / _x16 / _ce).  No kernels here, only
+// amount to, on ONE part that holds every node (cslicer_aggr.h: csl_sage_fwd_bwd_f32, its _x16, _dropout, _multilabel, _ce
+// and _norm forms) and on one RANK of the split-parallel job (csl_sage_rank_fwd_bwd_f32 / _x16 / _ce).  No kernels here, only
 // sequencing.
 //
 // Why a native sequencer: the step is ~25 kernel launches and 8 GEMMs of 5-90 us each.  Issued from Python (one ctypes
@@ -10,11 +10,12 @@
 // from here a step is ~0.15 ms of host time and the GPU sets the pace (a rank: the 2 L callbacks plus ~0.25 ms instead of
 // ~1.2 ms of interpreter + autograd work, which is what bounds a rank once the GPU work is split N ways).
 //
-// ONE layout (Layout, lay_out) and ONE body (sage_step) serve both; the eight entry points check their own arguments and
+// ONE layout (Layout, lay_out) and ONE body (sage_step) serve both; the nine entry points check their own arguments and
 // call it.  Per model layer k (deepest hop first; slice k = the engine's layer n_layers-1-k, graph mode):
 //   forward   cat_k = [x[self] | mean_{CSR row} x[src]]       csl_sage_cat_f32 (k = 0 reads the resident feature table
 //             y_k   = cat_k W_k^T + b_k (ReLU for k < L-1)     through the slice's in_nodes)      + csl_gemm_f32
 //             (k = 0, widths allowing: both as csl_sage_fwd_mfma_f32); dropout on y_k in place (k < L-1)
+//             normalised (csl_sage_fwd_bwd_norm): the ReLU above off, y_k = relu(gamma_k * layer_norm(y_k) + beta_k) in place
 //   loss      csl_softmax_ce_partial_f32 / csl_sigmoid_bce_partial_f32 / csl_softmax_ce_w_partial_f32 (class weights,
 //             label smoothing: the _ce entry points) on y_{L-1} (forward, gradient = the top layer's padded gy, bias
 //             column sums)
@@ -36,7 +37,8 @@
 //   - the gather by source reads g2 (gcat in out-row order, the peers' rows filled in by the reverse exchange), not gcat;
 //   - gcat is kept for layer 0 too, more than 256 classes are refused (no separate column-sum pass), an empty layer
 //     below defers a reduction over no blocks where the single-GPU step zero-fills, and nothing is timed;
-//   - no dropout and no multi-label loss yet: its entry points pass neither (what adding them takes).
+//   - no dropout, no multi-label loss and no layer normalisation yet: its entry points pass none of them (DESIGN.md 4.8,
+//     4.13: what adding them takes).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -50,6 +52,7 @@
 #include "cslicer_dropout.h"
 #include "cslicer_feat16.h"
 #include "cslicer_hip.h"
+#include "cslicer_layernorm.h"
 #include "cslicer_loss.h"
 #include "cslicer_multilabel.h"
 #include "dev_common.h"
@@ -111,10 +114,13 @@ struct Layout {
   bool slabbed[CSL_MAX_LAYERS];
   bool top_cols;                    // the loss pass also leaves the top layer's bias column sums
   int64_t g, scratch, total;        // single GPU, more than 256 classes: the logits' gradient and the column-sum scratch
+  // layer normalisation (csl_sage_fwd_bwd_norm), k < L-1: what the forward keeps for the backward, and the backward's two
+  // first stages ([lnblocks][out] each: dgamma_k, and gb_k now that bpart is dbeta_k's)
+  int64_t xhat[CSL_MAX_LAYERS], rstd[CSL_MAX_LAYERS], gpart[CSL_MAX_LAYERS], zpart[CSL_MAX_LAYERS], lnblocks[CSL_MAX_LAYERS];
 };
 
 // bump allocation of the step's buffers (floats); returns false for an unsupported model
-bool lay_out(int32_t L, const int32_t* dims, const Layers& lv, int64_t row_pad, int32_t n_slabs, Layout& o) {
+bool lay_out(int32_t L, const int32_t* dims, const Layers& lv, int64_t row_pad, int32_t n_slabs, Layout& o, bool norm = false) {
   if (!dims || !lv.ok || n_slabs < 1) return false;
   const Layer* v = lv.v;
   int64_t at = 0;
@@ -181,13 +187,23 @@ bool lay_out(int32_t L, const int32_t* dims, const Layers& lv, int64_t row_pad, 
     o.wpack = wp > 0 ? at : -1;
     if (wp > 0) at += up4(wp);
   }
+  // (behind everything else: without norm every offset and the total are what they always were)
+  for (int k = 0; norm && k + 1 < L; k++) {
+    const int64_t out = dims[k + 1], part = csl_layernorm_bwd_scratch(o.mp[k], (int32_t)out);
+    if (part < 0) return false;
+    o.xhat[k] = at, at += up4(v[k].rows * out);
+    o.rstd[k] = at, at += up4(v[k].rows);
+    o.lnblocks[k] = part / out;
+    o.gpart[k] = at, at += up4(part);
+    o.zpart[k] = at, at += up4(part);
+  }
   o.total = at;
   return true;
 }
 
-int64_t workspace_floats_of(int32_t L, const int32_t* dims, const Layers& lv, int64_t row_pad, int32_t n_slabs) {
+int64_t workspace_floats_of(int32_t L, const int32_t* dims, const Layers& lv, int64_t row_pad, int32_t n_slabs, bool norm = false) {
   Layout o;
-  return lay_out(L, dims, lv, row_pad, n_slabs, o) ? o.total : (int64_t)CSL_E_INVALID;
+  return lay_out(L, dims, lv, row_pad, n_slabs, o, norm) ? o.total : (int64_t)CSL_E_INVALID;
 }
 
 // ---- diagnostics: device time of the step's launches by group (csl_sage_step_timing / _read): HIP events around every
@@ -258,32 +274,45 @@ bool workspace_fits(int64_t total, const float* workspace, int64_t workspace_flo
   return false;
 }
 
-// where each parameter's gradient sits in the flat buffer: W_0, b_0, W_1, b_1, ...
+// where each parameter's gradient sits in the flat buffer: W_0, b_0, W_1, b_1, ..., then (a normalised model's)
+// gamma_0, beta_0, gamma_1, beta_1, ... of every layer but the last
 struct GradSlots {
-  float *gW[CSL_MAX_LAYERS], *gb[CSL_MAX_LAYERS];
+  float *gW[CSL_MAX_LAYERS], *gb[CSL_MAX_LAYERS], *ggamma[CSL_MAX_LAYERS], *gbeta[CSL_MAX_LAYERS];
   GradSlots(float* grads, int L, const int32_t* dims) {
     int64_t at = 0;
     for (int j = 0; j < L; j++) {
       gW[j] = grads + at, at += (int64_t)dims[j + 1] * 2 * dims[j];
       gb[j] = grads + at, at += dims[j + 1];
     }
+    for (int j = 0; j + 1 < L; j++) {
+      ggamma[j] = grads + at, at += dims[j + 1];
+      gbeta[j] = grads + at, at += dims[j + 1];
+    }
   }
 };
 
 // the second stages of a step's reductions, collected as (source, blocks, width, destination) and finished by ONE launch
-// (a step defers at most 2 L + 1 of them: see the static_assert above)
+// (a step defers at most 2 L + 1 of them: see the static_assert above); a normalised model adds two per layer but the last,
+// which at four layers is more than one launch takes: a second launch finishes what the first left
+constexpr int DEFER_MAX = 4 * CSL_MAX_LAYERS - 1;
+static_assert(DEFER_MAX <= 2 * CSL_REDUCE_MULTI_MAX, "two csl_reduce_multi_f32 launches take a normalised step's second stages");
 struct Deferred {
-  const float* src[CSL_REDUCE_MULTI_MAX];
-  float* dst[CSL_REDUCE_MULTI_MAX];
-  int64_t nblk[CSL_REDUCE_MULTI_MAX];
-  int32_t h[CSL_REDUCE_MULTI_MAX];
+  const float* src[DEFER_MAX];
+  float* dst[DEFER_MAX];
+  int64_t nblk[DEFER_MAX];
+  int32_t h[DEFER_MAX];
   int n = 0;
   void add(const float* s, int64_t blocks, int32_t width, float* d) {
-    if (n >= CSL_REDUCE_MULTI_MAX) return;   // (cannot happen: asserted at compile time)
+    if (n >= DEFER_MAX) return;   // (cannot happen: asserted at compile time)
     src[n] = s, nblk[n] = blocks, h[n] = width, dst[n] = d;
     n++;
   }
-  int finish(void* stream) { return csl_reduce_multi_f32(n, src, nblk, h, dst, stream); }
+  int finish(void* stream) {
+    const int first = n < CSL_REDUCE_MULTI_MAX ? n : CSL_REDUCE_MULTI_MAX;
+    const int rc = csl_reduce_multi_f32(first, src, nblk, h, dst, stream);
+    if (rc < 0 || first == n) return rc;
+    return csl_reduce_multi_f32(n - first, src + first, nblk + first, h + first, dst + first, stream);
+  }
 };
 
 // dropout between the layers (csl_sage_fwd_bwd_dropout, cslicer_dropout.h): layer k's out-node ids, the probability and the
@@ -304,6 +333,13 @@ struct MultiArgs {
 struct LossArgs {
   const float* class_weight;
   float label_smoothing;
+};
+
+// layer normalisation on the result of every layer but the last (csl_sage_fwd_bwd_norm, cslicer_layernorm.h)
+struct NormArgs {
+  const float* const* gammas;
+  const float* const* betas;
+  float eps;
 };
 
 // a rank's boundary exchange: the caller's callbacks.  `wait` given: `exchange` only STARTS the exchange (on a stream of
@@ -365,10 +401,10 @@ int sage_step(int32_t n_layers, const int32_t* dims, const Layers& lv, const flo
               const void* feat, int32_t kind, int64_t ldf, const int32_t* feat_rows, const int32_t* seed_ids,
               const int32_t* label_rows, const int64_t* labels, float scale, int64_t row_pad, int32_t n_slabs,
               const Exchange* xc, float* grads, float* loss, float* workspace, int64_t workspace_floats, void* stream,
-              const DropArgs* drop, const MultiArgs* multi, const LossArgs* lossw = nullptr) {
+              const DropArgs* drop, const MultiArgs* multi, const LossArgs* lossw = nullptr, const NormArgs* norm = nullptr) {
   s_err[0] = 0;
   Layout o;
-  if (!weights || !biases || !grads || !loss || (lv.rank && !xc->exchange) || !lay_out(n_layers, dims, lv, row_pad, n_slabs, o)) {
+  if (!weights || !biases || !grads || !loss || (lv.rank && !xc->exchange) || !lay_out(n_layers, dims, lv, row_pad, n_slabs, o, norm != nullptr)) {
     if (lv.rank)
       snprintf(s_err, sizeof(s_err), "bad argument or unsupported model (widths multiples of 4, <= 256 classes, 1..%d layers, "
                "n_in of a layer = n_owned of the layer below)", CSL_MAX_LAYERS);
@@ -406,7 +442,7 @@ int sage_step(int32_t n_layers, const int32_t* dims, const Layers& lv, const flo
       // gather [self | mean] into LDS, multiply on the fp32 matrix cores, bias + ReLU on the way out; the operand is
       // also written (the weight gradient reads it), but never read back by the forward
       STEP(t_fused, k, rd::sage_fwd_mfma(s.indptr, s.indices, s.self_ids_in, feat_rows, feat, kind, ldf, weights[0], ldc, biases[0],
-                                         m, mp, in, out, 0, L > 1 ? 1 : 0, ws + o.cat[0], ldc, ws + o.y[0], out, ws + o.wpack,
+                                         m, mp, in, out, 0, L > 1 && !norm ? 1 : 0, ws + o.cat[0], ldc, ws + o.y[0], out, ws + o.wpack,
                                          stream));
     } else {
       if (r) {
@@ -423,8 +459,12 @@ int sage_step(int32_t n_layers, const int32_t* dims, const Layers& lv, const flo
                                      ws + o.cat[k], ldc, in, 0, stream));
       }
       STEP(t_gemm, k, csl_gemm_f32(0, 1, mp, out, ldc, ws + o.cat[k], ldc, 0, weights[k], ldc, 0, ws + o.y[k], out, 0, 1, biases[k],
-                                   k + 1 < L ? 1 : 0, stream));
+                                   k + 1 < L && !norm ? 1 : 0, stream));
     }
+    // normalised: the layer ran with its ReLU off; y_k = relu(gamma * xhat + beta) in place, xhat_k and rstd_k kept
+    if (norm && k + 1 < L)
+      STEP(t_other, k, csl_layernorm_relu_fwd_f32(ws + o.y[k], out, norm->gammas[k], norm->betas[k], norm->eps, m, out, ws + o.y[k], out,
+                                                  ws + o.xhat[k], out, ws + o.rstd[k], 1, stream));
     // y_k is stored after its ReLU and read as it is by the layer above and by the backward's mask (y_k > 0): dropped in
     // place it carries relu' * mask by itself
     if (drop && k + 1 < L)
@@ -503,6 +543,21 @@ int sage_step(int32_t n_layers, const int32_t* dims, const Layers& lv, const flo
     } else {
       STEP(t_aggr, k, gather_by_source(s, o.hub[k], s.indptr, ws + o.gcat[k], in, y_below, mp_below, gy_below, bpart, stream));
     }
+    if (norm) {
+      // normalised: gy_{k-1} holds mask * gradient w.r.t. the normalised row and its column sums are dbeta_{k-1}; the
+      // backward of the norm turns it into dz in place and leaves the first stages of dgamma_{k-1} and gb_{k-1}
+      if (o.bblocks[k - 1] > 0) {
+        later.add(bpart, o.bblocks[k - 1], in, gs.gbeta[k - 1]);
+        STEP(t_other, k, csl_layernorm_bwd_f32(gy_below, in, ws + o.xhat[k - 1], in, ws + o.rstd[k - 1], norm->gammas[k - 1], s.n_in,
+                                               mp_below, in, ws + o.gpart[k - 1], ws + o.zpart[k - 1], stream));
+        later.add(ws + o.gpart[k - 1], o.lnblocks[k - 1], in, gs.ggamma[k - 1]);
+        later.add(ws + o.zpart[k - 1], o.lnblocks[k - 1], in, gs.gb[k - 1]);
+      } else {
+        for (float* g0 : {gs.gb[k - 1], gs.ggamma[k - 1], gs.gbeta[k - 1]})
+          if (hipMemsetAsync(g0, 0, sizeof(float) * in, (hipStream_t)stream) != hipSuccess) return CSL_E_HIP;
+      }
+      continue;
+    }
     // gb_{k-1}.  An empty layer below (no blocks): a rank defers a reduction over none, the single-GPU step zero-fills
     if (r || o.bblocks[k - 1] > 0) later.add(bpart, o.bblocks[k - 1], in, gs.gb[k - 1]);
     else if (hipMemsetAsync(gs.gb[k - 1], 0, sizeof(float) * in, (hipStream_t)stream) != hipSuccess) return CSL_E_HIP;
@@ -512,9 +567,10 @@ int sage_step(int32_t n_layers, const int32_t* dims, const Layers& lv, const flo
   if (drop && L > 1) {
     // the backward crossed L-1-j dropped layers on its way to layer j with the mask alone: the factor s of each, which
     // commutes with everything downstream of it, goes onto the finished gradients
-    float* seg[CSL_SCALE_SEGMENTS_MAX];
-    int64_t cnt[CSL_SCALE_SEGMENTS_MAX];
-    float fac[CSL_SCALE_SEGMENTS_MAX];
+    // (gamma_j and beta_j take W_j's factor; with them four layers have more segments than one launch takes)
+    float* seg[2 * CSL_SCALE_SEGMENTS_MAX];
+    int64_t cnt[2 * CSL_SCALE_SEGMENTS_MAX];
+    float fac[2 * CSL_SCALE_SEGMENTS_MAX];
     const double s1 = (double)(float)(1.0 / (1.0 - (double)drop->p));
     double f = 1.0;
     int ns = 0;
@@ -523,7 +579,13 @@ int sage_step(int32_t n_layers, const int32_t* dims, const Layers& lv, const flo
       seg[ns] = gs.gW[j], cnt[ns] = (int64_t)dims[j + 1] * 2 * dims[j], fac[ns] = (float)f, ns++;
       seg[ns] = gs.gb[j], cnt[ns] = dims[j + 1], fac[ns] = (float)f, ns++;
     }
-    STEP(t_other, -1, csl_scale_segments_f32(ns, seg, cnt, fac, stream));
+    for (int j = L - 2; norm && j >= 0; j--) {
+      seg[ns] = gs.ggamma[j], cnt[ns] = dims[j + 1], fac[ns] = fac[2 * (L - 2 - j)], ns++;
+      seg[ns] = gs.gbeta[j], cnt[ns] = dims[j + 1], fac[ns] = fac[2 * (L - 2 - j)], ns++;
+    }
+    const int first = ns < CSL_SCALE_SEGMENTS_MAX ? ns : CSL_SCALE_SEGMENTS_MAX;
+    STEP(t_other, -1, csl_scale_segments_f32(first, seg, cnt, fac, stream));
+    if (ns > first) STEP(t_other, -1, csl_scale_segments_f32(ns - first, seg + first, cnt + first, fac + first, stream));
   }
   return CSL_OK;
 }
@@ -700,6 +762,48 @@ int csl_sage_rank_fwd_bwd_ce(int32_t n_layers, const int32_t* dims, const csl_sa
   const LossArgs lossw = {class_weight, label_smoothing};
   return sage_step(n_layers, dims, Layers(n_layers, sl), weights, biases, feat, kind, ldf, feat_rows, seed_ids, label_rows, labels,
                    scale, row_pad, n_slabs, &xc, grads, loss, workspace, workspace_floats, stream, nullptr, nullptr, &lossw);
+}
+
+int64_t csl_sage_fwd_bwd_norm_workspace(int32_t n_layers, const int32_t* dims, const csl_sage_slice* slices, int64_t row_pad,
+                                        int32_t n_slabs) {
+  return workspace_floats_of(n_layers, dims, Layers(n_layers, slices), row_pad, n_slabs, true);
+}
+
+int csl_sage_fwd_bwd_norm(int32_t n_layers, const int32_t* dims, const csl_sage_slice* sl, const float* const* weights,
+                          const float* const* biases, const void* feat, int32_t kind, int64_t ldf, const int32_t* feat_rows,
+                          const int32_t* seed_ids, const int64_t* labels, const float* class_weight, float label_smoothing,
+                          float scale, int64_t row_pad, int32_t n_slabs, float* grads, float* loss, float* workspace,
+                          int64_t workspace_floats, const int32_t* const* out_ids, float p, int64_t seed, int64_t step,
+                          const int32_t* label_words, int64_t ldw, const float* const* gammas, const float* const* betas,
+                          float eps, void* stream) {
+  if (kind != 0 && table16_refused(feat, kind, ldf)) return CSL_E_INVALID;
+  if (!label_words && loss_refused(n_layers, dims, labels, label_smoothing)) return CSL_E_INVALID;
+  const bool plain = p == 0.f && !out_ids;
+  bool ok = n_layers >= 1 && n_layers <= CSL_MAX_LAYERS && sl && dims && (plain || (p > 0.f && p < 1.f && (n_layers == 1 || out_ids)));
+  for (int k = 0; ok && !plain && k + 1 < n_layers; k++) ok = sl[k].n_out <= 0 || out_ids[k];
+  if (ok && label_words) ok = dims[n_layers] >= 1 && dims[n_layers] <= 4096 && ldw >= (dims[n_layers] + 31) / 32;
+  if (!ok) {
+    snprintf(s_err, sizeof(s_err), "norm step: 1..%d layers; either p == 0 without out-node ids or 0 < p < 1 with those of every "
+             "layer but the last; packed label words of at least ceil(C / 32) per row, 1 <= C <= 4096 (p = %g)",
+             CSL_MAX_LAYERS, (double)p);
+    return CSL_E_INVALID;
+  }
+  ok = eps > 0.f && (n_layers == 1 || (gammas && betas));
+  for (int k = 0; ok && k + 1 < n_layers; k++) ok = gammas[k] && betas[k] && aligned16(gammas[k]) && aligned16(betas[k]);
+  if (!ok) {
+    snprintf(s_err, sizeof(s_err), "norm: eps > 0 and a 16-byte aligned gamma and beta for every layer but the last expected "
+             "(eps = %g)", (double)eps);
+    return CSL_E_INVALID;
+  }
+  const DropArgs drop = {out_ids, p, seed, step};
+  const MultiArgs multi = {label_words, ldw};
+  const LossArgs lossw = {class_weight, label_smoothing};
+  const NormArgs norm = {gammas, betas, eps};
+  return sage_step(n_layers, dims, Layers(n_layers, sl), weights, biases, feat, kind, ldf, feat_rows, seed_ids, nullptr,
+                   label_words ? nullptr : labels, scale, row_pad, n_slabs, nullptr, grads, loss, workspace, workspace_floats, stream,
+                   plain ? nullptr : &drop, label_words ? &multi : nullptr,
+                   label_words || (!class_weight && label_smoothing == 0.f) ? nullptr : &lossw,   // (no option: the plain loss pass)
+                   n_layers > 1 ? &norm : nullptr);
 }
 
 }  // extern "C"
