@@ -106,7 +106,7 @@ EXCHANGE_WAIT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_vo
 # the headers whose prototypes are taken from their text (cslicer_hip.h keeps its typed pointers, written out in load())
 HEADERS = ("cslicer_aggr.h", "cslicer_feat16.h", "cslicer_infer.h", "cslicer_infer_parts.h", "cslicer_infer16.h",
            "cslicer_gat_in16.h", "cslicer_dropout.h", "cslicer_multilabel.h", "cslicer_optim.h", "cslicer_loss.h",
-           "cslicer_gat_dropout.h", "cslicer_layernorm.h")
+           "cslicer_gat_dropout.h", "cslicer_layernorm.h", "cslicer_smooth.h")
 BOUND = {}     # header -> the names bind_header bound from it, in header order (filled by load())
 _SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "float": C.c_float}
 _PROTOTYPE = re.compile(r"^((?:const\s+)?\w+\s*\*?)\s*(csl_\w+)\s*\(([^()]*)\)\s*;", re.M)

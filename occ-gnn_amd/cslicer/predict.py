@@ -1,6 +1,7 @@
 """Apply a saved model to a graph: full-neighbour inference (cslicer.infer) of a checkpoint file, without a trainer.
 
     python -m cslicer.predict --model run.ckpt --graph <L0 dir> --out preds.npy [--nodes FILE] [--logits] [--feature-dtype T]
+                              [--correct-smooth [--train-nodes FILE] [--cs-layers T1,T2] [--cs-alpha A1,A2] [--cs-scale auto|NUMBER]]
 """
 import os
 import time
@@ -8,7 +9,7 @@ import time
 import numpy as np
 import torch
 
-from . import aggr, checkpoint, l0
+from . import aggr, checkpoint, l0, smooth
 
 
 def _parser():
@@ -20,19 +21,47 @@ def _parser():
     ap.add_argument("--nodes", type=str, default=None, metavar="FILE",
                     help="the nodes to predict, in this order: a .npy array or a raw int64 binary (as train_idx.bin); "
                          "default: every node")
-    ap.add_argument("--logits", action="store_true", help="write the float32 logits [n, n_classes] instead of classes")
+    ap.add_argument("--logits", action="store_true",
+                    help="write the float32 logits [n, n_classes] instead of classes (with --correct-smooth: the smoothed class "
+                         "scores in [0, 1], which are not logits)")
     ap.add_argument("--feature-dtype", choices=tuple(aggr.FEATURE_DTYPES), default=None,
                     help="element type of the feature table on the device (default: what the directory's meta.txt says)")
+    ap.add_argument("--correct-smooth", action="store_true",
+                    help="Correct and Smooth (cslicer.smooth) over the predictions of every node, with the directory's labels.bin "
+                         "on the training nodes; classes or --logits are then written from the smoothed scores")
+    ap.add_argument("--train-nodes", type=str, default=None, metavar="FILE",
+                    help="--correct-smooth: the labelled nodes, a file as --nodes takes (default: the directory's train_idx.bin)")
+    smooth.add_options(ap)
     return ap
 
 
-def read_nodes(path, num_nodes):
-    """int64 node ids of --nodes FILE; SystemExit for ids outside the graph"""
+def read_nodes(path, num_nodes, option="--nodes"):
+    """int64 node ids of --nodes FILE (or of `option`'s); SystemExit for ids outside the graph"""
     ids = np.load(path) if path.endswith(".npy") else np.fromfile(path, dtype=np.int64)
     ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
     if ids.size and (ids.min() < 0 or ids.max() >= num_nodes):
-        raise SystemExit("--nodes %s: node ids outside [0, %d)" % (path, num_nodes))
+        raise SystemExit("%s %s: node ids outside [0, %d)" % (option, path, num_nodes))
     return ids
+
+
+def _smooth_inputs(a, mb, num_nodes):
+    """--correct-smooth: (training nodes, their labels, correct_and_smooth's keywords), None without it.  SystemExit for
+    a multi-label model and for a directory without the labels or the training nodes."""
+    kw = smooth.options_of(a)
+    if kw is None:
+        if a.train_nodes is not None:
+            raise SystemExit("--train-nodes belongs to --correct-smooth")
+        return None
+    if mb["multilabel"]:
+        raise SystemExit("--correct-smooth: %s holds a multi-label model, which has no one-hot labels to propagate" % a.model)
+    path = a.train_nodes or os.path.join(a.graph, "train_idx.bin")
+    labels = os.path.join(a.graph, "labels.bin")
+    for need in (path, labels):
+        if not os.path.isfile(need):
+            raise SystemExit("--correct-smooth needs %s" % need)
+    train = read_nodes(path, num_nodes, "--train-nodes")
+    lab = np.memmap(labels, dtype=np.int32, mode="r", shape=(num_nodes,))
+    return train, np.asarray(lab[train]).astype(np.int64), kw
 
 
 def main(argv=None):
@@ -42,7 +71,10 @@ def main(argv=None):
     with EVERY neighbour (cslicer.infer.full_inference), as `Trainer.evaluate` applies it.  A directory whose feature_dim /
     num_classes are not the model's is refused before its features are read.  --feature-dtype: the table's element type on
     the device (default: as stored); a model trained on a 16-bit table predicts bitwise what its trainer did on the same
-    type.  Prints one summary line."""
+    type.  --correct-smooth: the model is applied to EVERY node and its predictions go through
+    cslicer.smooth.correct_and_smooth with the labels (labels.bin) of --train-nodes (default: train_idx.bin); the rows of
+    --nodes are then taken from the smoothed scores: their argmax, or with --logits the scores themselves (float32 in
+    [0, 1], not logits).  Prints one summary line."""
     a = _parser().parse_args(argv)
     if not os.path.isfile(a.model):
         raise SystemExit("--model %s: no such file" % a.model)
@@ -58,6 +90,7 @@ def main(argv=None):
         if meta.get(key) != have:       # (before the features are loaded)
             raise SystemExit("--graph %s has %s = %r, the model in %s was trained with %d"
                              % (a.graph, key, meta.get(key), a.model, have))
+    cs = _smooth_inputs(a, mb, meta["num_nodes"])        # (refused before the graph is read)
     from . import infer
     t0 = time.time()
     indptr, indices, meta = l0.read_l0(a.graph, mmap=False)
@@ -69,7 +102,12 @@ def main(argv=None):
     feats = feats.to(aggr.FEATURE_DTYPES[a.feature_dtype or stored]).contiguous()
     dev = torch.device("cuda", torch.cuda.current_device())
     model = checkpoint.model_from(ck, dev)
-    logits = infer.full_inference(model, indptr, indices, feats, nodes=nodes)
+    logits = infer.full_inference(model, indptr, indices, feats, nodes=nodes if cs is None else None)
+    if cs is not None:
+        try:
+            logits = smooth.correct_and_smooth(logits, indptr, indices, cs[0], cs[1], nodes=nodes, **cs[2])
+        except ValueError as ex:
+            raise SystemExit("--correct-smooth: %s" % ex)
     if a.logits:
         out = logits.cpu().numpy()
     elif mb["multilabel"]:

@@ -905,6 +905,33 @@ class Trainer(object):
             return infer.evaluate_parts(*args, self.comm, nodes, self.labels, owner=self.owner, **kw)
         return infer.evaluate(*args, labels=self.labels, **kw)
 
+    def correct_and_smooth(self, eval_nodes, train_nodes, **options):
+        """{"accuracy", "base_accuracy", "n"} on `eval_nodes`: the argmax accuracy of the current weights' predictions
+        after Correct and Smooth (cslicer.smooth.correct_and_smooth, DESIGN 4.14: the residuals of `train_nodes` against
+        the trainer's labels spread over the graph, the corrected scores smoothed) and, as base_accuracy, before it.  The
+        logits are predict()'s over all nodes; like it, this neither submits to the engine nor draws random numbers nor
+        touches the optimizer state.  options: correct_and_smooth's keywords (num_correction_layers, correction_alpha,
+        num_smoothing_layers, smoothing_alpha, autoscale, scale, chunk_rows).  ValueError, before any device work, for a
+        multi-label trainer and on the rank path (propagation over split ranks is not built: DESIGN 8)."""
+        if self.multilabel:
+            raise ValueError("correct_and_smooth: a multi-label trainer has no one-hot labels to propagate (DESIGN 8)")
+        if self.rank_path or self.n_own != self.N:
+            raise ValueError("correct_and_smooth runs in a single process that holds every node's row; propagation on the "
+                             "rank path is not built (DESIGN 8)")
+        from . import infer, smooth
+        ev, trn = infer._node_ids(eval_nodes), infer._node_ids(train_nodes)
+        for ids in (ev, trn):
+            if ids.size and (ids.min() < 0 or ids.max() >= self.N):
+                raise ValueError("correct_and_smooth: nodes outside [0, %d)" % self.N)
+        logits = self.predict()
+        dev_ev, dev_trn = torch.from_numpy(ev).to(self.dev), torch.from_numpy(trn).to(self.dev)
+        want = self.labels[dev_ev]
+        scores = smooth.correct_and_smooth(logits, self.eng.indptr, self.eng.indices, trn, self.labels[dev_trn], nodes=ev,
+                                           **options)
+        n = int(ev.shape[0])
+        plain, smoothed = infer.eval_head(logits[dev_ev], want)[1], infer.eval_head(scores, want)[1]
+        return {"accuracy": smoothed / max(n, 1), "base_accuracy": plain / max(n, 1), "n": n}
+
     # -- persistence: one file (cslicer.checkpoint, DESIGN 4.12)
     def checkpoint_fields(self):
         """the `trainer` block of a checkpoint: where the run stands and what it was built with (plain values only)"""
@@ -1191,6 +1218,11 @@ def _parser():
     ap.add_argument("--resume", type=str, default=None, metavar="FILE",
                     help="(extra) continue the run that wrote FILE with --save: same command line, same --num-epochs; the "
                          "epochs it had finished are replayed through the slicer only (`Trainer.skip`), not trained")
+    ap.add_argument("--correct-smooth", action="store_true",
+                    help="(extra) after every evaluation, Correct and Smooth (`Trainer.correct_and_smooth`): label propagation "
+                         "of the training nodes' residuals and labels over the graph; needs --eval-split, one process")
+    from . import smooth
+    smooth.add_options(ap)
     return ap
 
 
@@ -1259,6 +1291,14 @@ def _refuse_early(a):
             raise SystemExit("--no-replace: --fan-out %s exceeds the limit of %d neighbours per row" % (a.fan_out, lim))
     if a.save is not None and (a.save_every < 1 or not os.path.isdir(os.path.dirname(os.path.abspath(a.save)))):
         raise SystemExit("--save %s: --save-every must be >= 1 and the file's directory must exist" % a.save)
+    from . import smooth
+    if smooth.options_of(a) is not None:
+        if a.eval_split == "none":
+            raise SystemExit("--correct-smooth propagates the training nodes' labels to the evaluation nodes: it needs --eval-split")
+        if a.multilabel:
+            raise SystemExit("--correct-smooth: a multi-label run has no one-hot labels to propagate")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise SystemExit("--correct-smooth runs in a single process (propagation over split ranks is not built)")
 
 
 def _resume_epochs(a):
@@ -1420,6 +1460,12 @@ def _train_epochs(a, tr, first_epoch, train_nodes, eval_nodes, rank):
                     print("Eval F1 %.4f | loss %.4f | %d nodes in %.2f s" % (ev["micro_f1"], ev["loss"], ev["n"], time.time() - t0))
                 else:
                     print("Eval Acc %.4f | loss %.4f | %d nodes in %.2f s" % (ev["accuracy"], ev["loss"], ev["n"], time.time() - t0))
+            if a.correct_smooth:
+                from . import smooth
+                t0 = time.time()
+                cs = tr.correct_and_smooth(eval_nodes, train_nodes, **smooth.options_of(a))
+                if rank == 0:
+                    print("Eval Acc C&S %.4f (plain %.4f) | %d nodes in %.2f s" % (cs["accuracy"], cs["base_accuracy"], cs["n"], time.time() - t0))
 
 
 def main(argv=None):
@@ -1488,6 +1534,9 @@ def main(argv=None):
     shape class, from the recorded plans or else by timing: DESIGN 4.12), otherwise equal up to float32 summation order.  Rank 0 prints `resumed from FILE: epoch E, S steps`, and one line for every recorded setting
     (fan-outs, batch size, --no-replace, ...) the command line changes: such a run continues, but as another run.  A file that already
     holds --num-epochs epochs is reported (`nothing is left to train`) and not replayed.
+    --correct-smooth [--cs-layers T1,T2] [--cs-alpha A1,A2] [--cs-scale auto|NUMBER] (extra): after every `Eval Acc` line rank 0
+    prints `Eval Acc C&S %.4f (plain %.4f) | %d nodes in %.2f s`: `Trainer.correct_and_smooth` on the evaluation nodes, with the
+    training nodes' labels (defaults 50,50 / 0.8,0.8 / auto).  Needs --eval-split; not with --multilabel, one process.
 
         python -m cslicer.train --graph products-like --num-epochs 20 --eval-split holdout --save run.ckpt
         python -m cslicer.train --graph products-like --num-epochs 20 --eval-split holdout --save run.ckpt --resume run.ckpt
@@ -1497,6 +1546,7 @@ def main(argv=None):
         python -m cslicer.train --graph products-like --dropout 0.5 --weight-decay 5e-4 --clip-grad-norm 1 --lr-warmup 100 --lr-schedule cosine
         python -m cslicer.train --graph products-like --norm layer --dropout 0.5 --lr-warmup 100 --lr-schedule cosine
         python -m cslicer.train --graph <L0 dir> --feature-dtype bfloat16 --eval-split holdout
+        python -m cslicer.train --graph products-like --eval-split holdout --correct-smooth --cs-layers 50,50 --cs-alpha 0.8,0.8
         python -m cslicer.train --graph products-like --model-name gat --feature-dtype bfloat16 --gat-input on
         python -m cslicer.train --graph products-like --model-name gat --feat-dropout 0.6 --attn-dropout 0.6 --eval-split holdout"""
     a = _parser().parse_args(argv)
